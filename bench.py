@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — trajectory sample-points/s of the batched hot path on N MI355X (one rank per GPU).
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c3|c5|c2|c4] [--dtype f32|f64]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c3|c5|c2|c4] [--dtype f32|f64] [--full]
+                    [--dump-outputs DIR]
         (N > 1 without a launcher: the script starts its own N ranks as a child torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -9,8 +10,14 @@
 A step = one pass of the hot path (fit -> arc-length LUT -> sampling -> forward/backward velocity
 pass) over this rank's batch of synthetic paths, inputs already resident in HBM.  Paths are
 independent, so the batch is sharded over ranks with NO data-path collective (weak scaling: every
-rank processes the same number of paths); RCCL only broadcasts the constraints before and gathers
-per-path summaries after the timed region.
+rank processes the same number of paths); RCCL only broadcasts the constraints before the timed region (and, with
+--full, gathers per-path summaries after it).
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit, ms_per_step, ...).
+Everything else it can measure or check runs only with --full, after the timed region: per-kernel stage times and the
+roofline, the communicator record and the per-path summary all-gather, parity against the CPU oracle, the other
+recurrence arithmetic, the config-1 drop-in leg and the CPU baseline.  --dump-outputs DIR writes what the last timed
+step computed as DIR/<name>.npy (see dump_outputs).
 
 Workloads (BASELINE.json configs):
   c3 (default): 4096 paths x 32 waypoints x 10 000 samples per GPU  — the config the metric
@@ -252,6 +259,41 @@ def launch_ranks(n):
     return subprocess.call(cmd, env=env)
 
 
+DUMP_ROW_BYTES = 48 << 20     # the sampled rows; meta and flags of every path add at most DUMP_ALL_PATHS_BYTES
+DUMP_ALL_PATHS_BYTES = 12 << 20
+DUMP_MAX_PATHS = 128
+
+
+def dump_outputs(out_dir, out, fields=("x", "y", "heading", "curvature", "velocity")):
+    """What the timed step hands its caller, as <out_dir>/<name>.npy: the (B, S) rows x, y, heading, curvature, velocity in
+    the run's dtype, meta (B, 4) fp64 and flags (B,) as float32.  The rows of a fixed, seeded sample of paths (at most
+    DUMP_MAX_PATHS, sorted; all of them when B is smaller) and — when those rows would pass DUMP_ROW_BYTES — of a fixed,
+    seeded, sorted sample of sample columns; meta and flags of every path (of the sampled ones past
+    DUMP_ALL_PATHS_BYTES).  The sample depends on B and S only, so two builds' dumps compare entry for entry."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    B, S = out["velocity"].shape
+    rows = [f for f in fields if f in out]
+    esz = out["velocity"].element_size()
+    rng = np.random.default_rng(20240607)
+    n = min(B, DUMP_MAX_PATHS, max(1, DUMP_ROW_BYTES // (len(rows) * S * esz)))
+    paths = np.arange(B) if n == B else np.sort(rng.choice(B, n, replace=False))
+    cols = None
+    if n * len(rows) * S * esz > DUMP_ROW_BYTES:
+        cols = np.sort(rng.choice(S, DUMP_ROW_BYTES // (n * len(rows) * esz), replace=False))
+    dev = out["velocity"].device
+    pi = torch.as_tensor(paths, device=dev)
+    ci = None if cols is None else torch.as_tensor(cols, device=dev)
+    for f in rows:
+        a = out[f].index_select(0, pi)
+        if ci is not None:
+            a = a.index_select(1, ci)
+        np.save(os.path.join(out_dir, f + ".npy"), a.cpu().numpy())
+    keep = slice(None) if B * (4 * 8 + 4) <= DUMP_ALL_PATHS_BYTES else pi
+    np.save(os.path.join(out_dir, "meta.npy"), out["meta"][keep].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "flags.npy"), out["flags"][keep].cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -289,7 +331,15 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"),
                     help="process-group backend; gloo + --share-device rehearses the multi-rank path on a 1-GPU box")
     ap.add_argument("--share-device", action="store_true", help="(rehearsal) every rank uses cuda:0")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure and check what the headline figure does not need: per-kernel "
+                         "stage times and roofline, communicator record, per-path summaries, parity, the other recurrence "
+                         "arithmetic, the config-1 drop-in leg, the CPU baseline (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's batch) as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks (one per GPU) as a CHILD torch.distributed.run and
@@ -334,8 +384,9 @@ def main():
     # (synth.make_waypoints_block: block 0 is the 1-GPU batch; no rank builds another rank's paths, no waypoint scatter)
     wp = torch.tensor(make_waypoints_block(B, W, wl["seed"], rank, dtype=np.float32 if args.dtype == "f32" else np.float64),
                       dtype=tdt, device=dev)
-    # what the communicator itself reports (RCCL saw N ranks: world size and an all-reduce of ones), before the timed region
-    comm = vdist.comm_record(dev)
+    # --full: what the communicator itself reports (RCCL saw N ranks: world size and an all-reduce of ones), before the timed
+    # region
+    comm = vdist.comm_record(dev) if args.full else None
 
     residual = bool(args.time_domain_residual or args.time_domain)
     gen = BatchedTrajectoryGenerator(local_rank, args.dtype, recurrence=args.recurrence, time_domain_residual=residual)
@@ -374,16 +425,19 @@ def main():
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
 
-    # per-kernel durations, HIP events on the library's stream (averaged over the same K steps)
-    gen.ctx.set_timing(True)
-    acc = {}
-    for _ in range(args.steps):
-        step()
-        for k, v in gen.timing().items():
-            acc[k] = acc.get(k, 0.0) + v / args.steps
-    gen.ctx.set_timing(False)
+    # what the last timed step computed, as its caller receives it
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
-    flags = int(out["flags"].abs().max().item())
+    # --full: per-kernel durations, HIP events on the library's stream (averaged over K more steps)
+    acc = {}
+    if args.full:
+        gen.ctx.set_timing(True)
+        for _ in range(args.steps):
+            step()
+            for k, v in gen.timing().items():
+                acc[k] = acc.get(k, 0.0) + v / args.steps
+        gen.ctx.set_timing(False)
     # after the timed region, outside `value`: the time-domain resample of the same batch (SURVEY §8(f)-1,
     # what generate_motion_profile does with the velocity rows), on request
     time_domain = None
@@ -401,26 +455,28 @@ def main():
         ms = e0.elapsed_time(e1) / 3
         time_domain = {"ms": ms, "rows": n_rows, "rows_per_s": n_rows / (ms * 1e-3), "dt_s": 0.01,
                        "truncated_paths": int((tp["counts"][:, 0] >= cap_rows).sum().item())}
-    # after the timed region: all-gather per-path summaries (length, samples, traversal time) over RCCL —
-    # 24 B/path, what a caller ranking candidate trajectories needs from the other GPUs
-    summ = vdist.all_gather_rows(vdist.path_summaries(out["meta"], out["velocity"]), B * world)
-    total_len = float(summ[:, 0].sum().item())
-    best_time = float(summ[:, 2].min().item())
+    # after the timed region, --full: the flags of the batch, and an all-gather of per-path summaries (length, samples,
+    # traversal time) over RCCL — 24 B/path, what a caller ranking candidate trajectories needs from the other GPUs
+    if args.full:
+        flags = int(out["flags"].abs().max().item())
+        summ = vdist.all_gather_rows(vdist.path_summaries(out["meta"], out["velocity"]), B * world)
+        total_len = float(summ[:, 0].sum().item())
+        best_time = float(summ[:, 2].min().item())
 
     # after the timed region, rank 0, N = 1: BASELINE config 1 through the drop-in path, for the record
     dropin_c1 = None
-    if rank == 0 and world == 1 and not args.no_dropin_c1:
+    if args.full and rank == 0 and world == 1 and not args.no_dropin_c1:
         dropin_c1 = dropin_config1()
 
     # parity of the mode just timed: the first paths of rank 0's batch against the oracle (CPU, after the timed region)
     parity = None
-    if rank == 0 and args.parity_paths > 0:
+    if args.full and rank == 0 and args.parity_paths > 0:
         parity = parity_check(out, wp, S, constraints, min(args.parity_paths, B), args.dtype)
 
     # after the timed region, N = 1, fp32 rows only: the OTHER recurrence arithmetic on the same batch, for the record —
     # never `value`.  (default mode: fp64 recurrence, holds 1e-5 everywhere; "f32": round 1's, faster, leaves the bound)
     other_mode = None
-    if world == 1 and args.dtype == "f32" and not args.no_other_mode:
+    if args.full and world == 1 and args.dtype == "f32" and not args.no_other_mode:
         orec = "f32" if args.recurrence == "f64" else "f64"
         ogen = BatchedTrajectoryGenerator(local_rank, "f32", recurrence=orec, time_domain_residual=residual)
         oout = None
@@ -482,14 +538,6 @@ def main():
 
     if rank == 0:
         points = B * S * world
-        esz = 4 if args.dtype == "f32" else 8
-        bytes_per_point = 5 * esz + (12 * esz * (W - 1)) / S   # 20 B + 48*G/S (fp32)
-        stage_bytes = {"sample": 4 * esz + (12 * esz * (W - 1)) / S, "velocity": esz,
-                       "fit": (12 * esz * (W - 1)) / S, "lut": 0.0}
-        dom = max(("fit", "lut", "sample", "velocity"), key=lambda k: acc.get(k, 0.0))
-        dom_ms = acc[dom]
-        achieved = stage_bytes[dom] * B * S / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-        traffic, traffic_note = profiled_traffic(dom, args.workload, args.dtype, B, args.recurrence)
         line = {
             "metric": "trajectory sample-points/sec (batched paths)",
             "value": points / elapsed * args.steps,
@@ -502,28 +550,38 @@ def main():
                        "grid": "dd_p = L_p / (S - 1.5), the reference's running sum from 0 plus its appended end sample",
                        "recurrence": ("f64 behind fp32 rows" if args.recurrence == "f64" else "f32") if args.dtype == "f32" else "f64",
                        "time_domain_residual": residual,
-                       "global_paths": B * world, "parallelism": f"paths sharded x{world}, no data-path collective",
-                       "flags_or": flags, "sum_path_length_ft": total_len,
-                       "fastest_traversal_s": best_time},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
-                         "kernel_ms": dom_ms, "algorithmic_bytes_per_point": stage_bytes[dom]},
-            "comm": comm,
-            "kernel_source_sha": kernel_source_sha(),
-            "pipeline": {"bytes_per_point": bytes_per_point,
-                         "traffic": profiled_pipeline_traffic(args.workload, args.dtype, B, args.recurrence),
-                         "achieved_GBs": bytes_per_point * B * S / (acc["total"] * 1e-3) / 1e9,
-                         "frac_of_hbm_peak": bytes_per_point * B * S / (acc["total"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "stage_ms": {k: round(v, 4) for k, v in acc.items()}},
+                       "global_paths": B * world, "parallelism": f"paths sharded x{world}, no data-path collective"},
         }
-        # the counted bytes as a rate: how hard the memory system is actually being driven (the algorithmic fraction above
-        # says how much of that is bytes the caller asked for)
-        if traffic:
-            line["roofline"]["traffic_GBs"] = traffic / (dom_ms * 1e-3) / 1e9
-            line["roofline"]["traffic_frac_of_peak"] = line["roofline"]["traffic_GBs"] / HBM_PEAK_GBS
-        if line["pipeline"]["traffic"]:
-            line["pipeline"]["traffic_GBs"] = line["pipeline"]["traffic"] / (acc["total"] * 1e-3) / 1e9
-            line["pipeline"]["traffic_frac_of_peak"] = line["pipeline"]["traffic_GBs"] / HBM_PEAK_GBS
+        if args.full:
+            line["config"].update({"flags_or": flags, "sum_path_length_ft": total_len, "fastest_traversal_s": best_time})
+            esz = 4 if args.dtype == "f32" else 8
+            bytes_per_point = 5 * esz + (12 * esz * (W - 1)) / S   # 20 B + 48*G/S (fp32)
+            stage_bytes = {"sample": 4 * esz + (12 * esz * (W - 1)) / S, "velocity": esz,
+                           "fit": (12 * esz * (W - 1)) / S, "lut": 0.0}
+            dom = max(("fit", "lut", "sample", "velocity"), key=lambda k: acc.get(k, 0.0))
+            dom_ms = acc[dom]
+            achieved = stage_bytes[dom] * B * S / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+            traffic, traffic_note = profiled_traffic(dom, args.workload, args.dtype, B, args.recurrence)
+            line.update({
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
+                             "kernel_ms": dom_ms, "algorithmic_bytes_per_point": stage_bytes[dom]},
+                "comm": comm,
+                "kernel_source_sha": kernel_source_sha(),
+                "pipeline": {"bytes_per_point": bytes_per_point,
+                             "traffic": profiled_pipeline_traffic(args.workload, args.dtype, B, args.recurrence),
+                             "achieved_GBs": bytes_per_point * B * S / (acc["total"] * 1e-3) / 1e9,
+                             "frac_of_hbm_peak": bytes_per_point * B * S / (acc["total"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             "stage_ms": {k: round(v, 4) for k, v in acc.items()}},
+            })
+            # the counted bytes as a rate: how hard the memory system is actually being driven (the algorithmic fraction above
+            # says how much of that is bytes the caller asked for)
+            if traffic:
+                line["roofline"]["traffic_GBs"] = traffic / (dom_ms * 1e-3) / 1e9
+                line["roofline"]["traffic_frac_of_peak"] = line["roofline"]["traffic_GBs"] / HBM_PEAK_GBS
+            if line["pipeline"]["traffic"]:
+                line["pipeline"]["traffic_GBs"] = line["pipeline"]["traffic"] / (acc["total"] * 1e-3) / 1e9
+                line["pipeline"]["traffic_frac_of_peak"] = line["pipeline"]["traffic_GBs"] / HBM_PEAK_GBS
         if parity is not None:
             line["parity"] = parity
         if other_mode is not None:
@@ -537,7 +595,7 @@ def main():
         if dropin_c1 is not None:
             line["dropin_c1"] = dropin_c1
             line["dropin_c1_ms"] = dropin_c1["median_ms"]   # (mean, min and max are in the object: a full Python GC pass — ~40 ms with torch imported — lands in one call of a few dozen)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(wl)
             # context, not measured here: the reference's own Python cannot travel to this box
             line["cpu_baseline"]["reference_python"] = {"value": 5.3e3, "unit": "sample-points/s", "cores": 1,

@@ -38,6 +38,7 @@ from vexautonomousplanner_amd.synth import (DEFAULT_CONSTRAINTS, DEFAULT_DD, END
                                              START_VEL, make_waypoints)
 
 OUT = os.path.join(ROOT, "tests", "golden")
+ROW_PIECE = 1 << 18
 NODE_FIELDS = ("is_reverse_node", "turn", "wait_time", "stop", "max_velocity", "max_acceleration")
 
 
@@ -185,6 +186,14 @@ def run_case(mods, name, wp, dd=DEFAULT_DD, samples=None, node_attrs=None, actio
         d["profile_coords"] = np.array([np.asarray(p, dtype=np.float64) for p in res[8]])
     os.makedirs(OUT, exist_ok=True)
     path = os.path.join(OUT, name + ".npz")
+    if "velocity_full" in d:
+        # the whole row goes beside the fixture in pieces of 2^18 samples (a committed file stays under 1 MiB);
+        # tests/golden_util.load joins them
+        full = d.pop("velocity_full")
+        os.makedirs(os.path.join(OUT, "rows"), exist_ok=True)
+        for k in range(0, len(full), ROW_PIECE):
+            np.savez_compressed(os.path.join(OUT, "rows", f"{name}.velocity_full.{k // ROW_PIECE}.npz"),
+                                rows=full[k:k + ROW_PIECE])
     np.savez_compressed(path, **d)
     print(f"{name}: W={W} N={len(vel)} L={total:.6f} dd={dd:.6g} "
           f"{os.path.getsize(path) / 1024:.0f} KiB  {time.time() - t0:.1f}s", flush=True)

@@ -122,7 +122,7 @@ def test_bench_starts_its_own_ranks(torch_mod):
     import json
     import subprocess
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device", "--steps", "3",
-           "--warmup", "1", "--paths-per-gpu", "256", "--no-cpu-baseline", "--parity-paths", "0"]
+           "--warmup", "1", "--full", "--paths-per-gpu", "256", "--no-cpu-baseline", "--parity-paths", "0"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -152,7 +152,7 @@ def test_bench_one_rank_over_rccl_under_the_launcher(torch_mod):
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full",
            "--workload", "c5", "--paths-per-gpu", "2048", "--tolerance-sweep", "--no-cpu-baseline", "--parity-paths", "0"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -165,3 +165,42 @@ def test_bench_one_rank_over_rccl_under_the_launcher(torch_mod):
     assert rec["config"]["flags_or"] == 0
     assert rec["comm"]["backend"].startswith("rccl") and rec["comm"]["world_size"] == 1 and rec["comm"]["ranks_reporting"] == 1
     assert rec["comm"]["rccl"] not in (None, "unknown"), rec["comm"]
+
+
+def test_bench_plain_run_and_its_dumped_outputs(torch_mod, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` prints the headline line without what --full adds, and
+    --dump-outputs writes what its last timed step computed: the same files as the same batch through the generator
+    directly, entry for entry."""
+    import json
+    import subprocess
+    torch = torch_mod
+    sys.path.insert(0, ROOT)
+    import bench
+    from vexautonomousplanner_amd.batch import BatchedTrajectoryGenerator
+    from vexautonomousplanner_amd.synth import DEFAULT_CONSTRAINTS, make_waypoints_block
+    B, W, S, seed = 300, 8, 1024, 5
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "c5",
+           "--paths-per-gpu", str(B), "--dump-outputs", str(tmp_path / "bench")]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "trajectory sample-points/sec (batched paths)" and rec["unit"] == "sample-points/s"
+    assert rec["higher_is_better"] is True and rec["dtype"] == "f32" and rec["steps"] == 3
+    assert rec["ms_per_step"] > 0 and abs(rec["value"] - B * S / (rec["ms_per_step"] * 1e-3)) <= 1e-6 * rec["value"]
+    assert not {"roofline", "pipeline", "comm", "parity", "other_mode", "dropin_c1", "cpu_baseline"} & set(rec)
+
+    wp = make_waypoints_block(B, W, seed, 0, dtype=np.float32)
+    gen = BatchedTrajectoryGenerator(0, "f32", time_domain_residual=False)
+    ref = gen.profile(torch.tensor(wp, device=gen.device), constraints=list(DEFAULT_CONSTRAINTS), samples=S)
+    torch.cuda.synchronize()
+    bench.dump_outputs(str(tmp_path / "direct"), ref)
+    names = sorted(os.listdir(tmp_path / "direct"))
+    assert sorted(os.listdir(tmp_path / "bench")) == names and "velocity.npy" in names
+    for n in names:
+        a, b = np.load(tmp_path / "bench" / n), np.load(tmp_path / "direct" / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and np.array_equal(a, b), n
+    assert np.load(tmp_path / "bench" / "velocity.npy").shape == (bench.DUMP_MAX_PATHS, S)
+    assert not np.load(tmp_path / "bench" / "flags.npy").any()

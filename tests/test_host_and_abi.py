@@ -251,3 +251,41 @@ def test_generated_chain_loops_match_their_generator(tmp_path):
     subprocess.run([sys.executable, os.path.join(root, "tools", "gen_chain_asm.py"), str(out)], check=True, capture_output=True)
     committed = open(os.path.join(root, "vexautonomousplanner_amd", "csrc", "vap_chain_asm.h")).read()
     assert out.read_text() == committed
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """bench.py --dump-outputs: the rows of a seeded sample of paths (and of sample columns when a row is too long), meta and
+    flags, as float32 / float64 .npy within 64 MB; the same (B, S) picks the same entries, so two builds compare entry for
+    entry.  Host tensors stand in for the device rows here."""
+    import sys
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def fake(B, S, dt):
+        g = torch.Generator().manual_seed(B * 7 + S)
+        out = {f: torch.rand((B, S), generator=g, dtype=dt) for f in ("x", "y", "heading", "curvature", "velocity")}
+        out["meta"] = torch.rand((B, 4), generator=g, dtype=torch.float64)
+        out["flags"] = torch.randint(0, 16, (B,), generator=g, dtype=torch.int32)
+        return out
+
+    for B, S, dt in ((1024, 10000, torch.float32), (37, 200, torch.float64), (1, 1500000, torch.float64)):
+        out = fake(B, S, dt)
+        a, b = tmp_path / f"a{B}", tmp_path / f"b{B}"
+        bench.dump_outputs(str(a), out)
+        bench.dump_outputs(str(b), fake(B, S, dt))
+        names = sorted(os.listdir(a))
+        assert names == sorted(os.listdir(b)) == sorted(f + ".npy" for f in ("x", "y", "heading", "curvature", "velocity",
+                                                                               "meta", "flags"))
+        assert sum(os.path.getsize(a / n) for n in names) <= 64e6
+        for n in names:
+            x, y = np.load(a / n), np.load(b / n)
+            assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+        v = np.load(a / "velocity.npy")
+        assert v.dtype == out["velocity"].numpy().dtype and v.shape[0] == min(B, bench.DUMP_MAX_PATHS)
+        assert np.array_equal(np.load(a / "meta.npy"), out["meta"].numpy())
+        assert np.array_equal(np.load(a / "flags.npy"), out["flags"].numpy().astype(np.float32))
+        if v.shape[1] == S:                                              # whole rows: they are rows of the batch
+            assert all((out["velocity"].numpy() == r).all(axis=1).any() for r in v[:4])
+        else:                                                            # a sample of one long row's columns
+            assert B == 1 and v.shape[1] < S and np.isin(v[0], out["velocity"].numpy()[0]).all()

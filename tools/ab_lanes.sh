@@ -6,7 +6,7 @@ for rep in 1 2 3; do
   for v in 8 12; do
     cp $root/vexautonomousplanner_amd/libvap$v.so.ab $root/vexautonomousplanner_amd/libvap.so
     for w in "$@"; do
-      python3 $root/bench.py --workload $w --steps 20 --warmup 3 --no-cpu-baseline --no-other-mode --parity-paths 0 2>/dev/null | python3 -c "
+      python3 $root/bench.py --full --workload $w --steps 20 --warmup 3 --no-cpu-baseline --no-other-mode --parity-paths 0 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['pipeline']['stage_ms']
 print('waves=$v rep=$rep $w step %.4f sample %.4f velocity %.4f' % (d['ms_per_step'], s['sample'], s['velocity']))"

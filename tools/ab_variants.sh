@@ -29,7 +29,7 @@ for rep in 1 2; do
   for v in "$@"; do
     cp $root/vexautonomousplanner_amd/libvap_$v.so.ab $root/vexautonomousplanner_amd/libvap.so
     for w in "${wl[@]}"; do
-      python3 $root/bench.py --workload $w --steps 20 --warmup 3 --no-cpu-baseline --no-other-mode --no-dropin-c1 --parity-paths 0 2>/dev/null | python3 -c "
+      python3 $root/bench.py --full --workload $w --steps 20 --warmup 3 --no-cpu-baseline --no-other-mode --no-dropin-c1 --parity-paths 0 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['pipeline']['stage_ms']
 print('$v rep=$rep $w step %.4f lut %.4f sample %.4f velocity %.4f' % (d['ms_per_step'], s['lut'], s['sample'], s['velocity']))"

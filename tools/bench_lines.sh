@@ -12,9 +12,9 @@ line() {   # name, bench args...
     grep '^{"metric"' $root/gpurun_out/bench_line_$name.log | tail -1 > $out/${tag}_bench_$name.json
     echo "$name: $(python3 -c "import json,sys; d=json.load(open('$out/${tag}_bench_$name.json')); print(round(d['ms_per_step'],4), 'ms', '%.3g' % d['value'], 'points/s', d['pipeline']['stage_ms'])")"
 }
-line c2 --workload c2 --steps 20 --warmup 3 --no-cpu-baseline --no-other-mode
-line c4 --workload c4 --steps 20 --warmup 3 --no-cpu-baseline --no-other-mode
-line c5 --workload c5 --steps 10 --warmup 2 --no-cpu-baseline --no-other-mode --tolerance-sweep
-line f64 --dtype f64 --steps 20 --warmup 3 --no-cpu-baseline
-line f32rec --recurrence f32 --steps 20 --warmup 3 --no-cpu-baseline --no-other-mode
-line timedomain --steps 10 --warmup 2 --no-cpu-baseline --no-other-mode --time-domain
+line c2 --full --workload c2 --steps 20 --warmup 3 --no-cpu-baseline --no-other-mode
+line c4 --full --workload c4 --steps 20 --warmup 3 --no-cpu-baseline --no-other-mode
+line c5 --full --workload c5 --steps 10 --warmup 2 --no-cpu-baseline --no-other-mode --tolerance-sweep
+line f64 --full --dtype f64 --steps 20 --warmup 3 --no-cpu-baseline
+line f32rec --full --recurrence f32 --steps 20 --warmup 3 --no-cpu-baseline --no-other-mode
+line timedomain --full --steps 10 --warmup 2 --no-cpu-baseline --no-other-mode --time-domain

@@ -7,6 +7,8 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import golden_util as gu
 import numpy as np
 import torch
 
@@ -15,7 +17,7 @@ from vexautonomousplanner_amd.batch import BatchedTrajectoryGenerator
 
 files = sorted(glob.glob("tests/golden/big_w2048_p*.npz") + glob.glob("tests/golden_tmp/big_w2048_p*.npz"))
 for f in files:
-    g = np.load(f)
+    g = gu.load(os.path.basename(f)[:-4], os.path.dirname(f))     # (the whole velocity row is stored in pieces)
     N = int(g["n_samples"])
     ref = g["velocity_full"]
     op = oracle.OraclePath(g["waypoints"])
