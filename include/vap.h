@@ -440,6 +440,33 @@ int vap_route_motion_profile(vap_route *route, const vap_constraints *c, double 
                              double *h_rows, long *n_rows, long *h_nodes_map, int *n_nodes_map,
                              long *h_actions_map, int *n_actions_map);
 
+/* ---- closest point on a path (gui/path.py:658-727 PathWidget.find_closest_point_on_path) -------------
+ * VAP_CLOSEST_GUI: the GUI's own search, reproduced exactly — a coarse pass over percent = i / (25 * len(nodes)),
+ *   i = 0..25*len(nodes), then 501 steps over [max(0, cp - 0.02), min(1, cp + 0.02)] around the coarse winner's percent
+ *   cp, each step percent_to_parameter (SM:277-289, quirk Q6) + get_point_at_parameter (SM:204-215) + hypot; min_dist
+ *   carries over into the fine pass and '<' is strict, so the first index at the minimum wins.
+ * VAP_CLOSEST_EXACT: the global minimiser of |P(t) - q| over t in [0, W-1], across every spline of a route (per segment
+ *   the roots of (P - q) . P', isolated by Bernstein sign variations, against the segment endpoints); on an exact tie
+ *   the smallest parameter wins.
+ * Outputs per query (fp64, any pointer may be NULL): parameter t; point P(t) [2] (= vap_route_eval order 0 at t, bit
+ * for bit); distance |q - P(t)|; arc_length s at t from the path's own lookup table (the inverse of distance_to_time's
+ * lerp, SM:291-318); cross_track = +distance when q lies left of P'(t) (cross(P', q - P) > 0), -distance otherwise.
+ * A path of zero length (the GUI's early return, gui/path.py:670-679) gets NaN outputs. */
+#define VAP_CLOSEST_GUI 0
+#define VAP_CLOSEST_EXACT 1
+/* gui/path.py:658-727 for the context's last vap_profile_batch / vap_profile_routes batch (same B and W).
+ *   d_queries   [B][Q][2] feet, or [Q][2] for every path with shared_queries != 0
+ *   d_parameter, d_distance, d_arc_length, d_cross_track [B][Q]; d_point [B][Q][2]
+ *   d_flags     [B], optional, in / out: the profile call's flags — a path flagged VAP_FLAG_BAD_ROUTE gets NaN outputs;
+ *               a path of zero length gets NaN outputs and VAP_FLAG_DEGENERATE.
+ * Q = 0 is a no-op. */
+int vap_closest_points(vap_ctx *ctx, int B, int W, int Q, int mode, int shared_queries, const double *d_queries,
+                       double *d_parameter, double *d_point, double *d_distance, double *d_arc_length,
+                       double *d_cross_track, uint32_t *d_flags);
+/* gui/path.py:658-727 on one route, host buffers: one copy each way and one launch.  h_queries [n][2] feet;
+ * h_out [n][6] = t, x, y, distance, arc_length, cross_track (NaN rows for a route of zero length). */
+int vap_route_closest(vap_route *route, int mode, int n, const double *h_queries, double *h_out);
+
 #ifdef __cplusplus
 }
 #endif

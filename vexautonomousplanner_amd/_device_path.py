@@ -343,6 +343,16 @@ class DeviceRoute:
                                             out.ctypes.data_as(dp)), "vap_route_lookup")
         return out
 
+    def closest(self, mode, queries):
+        """gui/path.py:658-727 on this route (vap_route_closest): queries (n, 2) feet -> (n, 6) rows
+        {parameter, x, y, distance, arc_length, cross_track}; NaN rows for a route of zero length."""
+        qs = np.ascontiguousarray(np.asarray(queries, dtype=np.float64).reshape(-1, 2))
+        out = np.empty((len(qs), 6))
+        dp = C.POINTER(C.c_double)
+        _lib.check(self._L.vap_route_closest(self.handle, _lib.closest_mode(mode), len(qs), qs.ctypes.data_as(dp),
+                                             out.ctypes.data_as(dp)), "vap_route_closest")
+        return out
+
     # -- the batch kernels with B = 1 ------------------------------------------------------------------------------
     # The route's sampling, limits, velocity pass, time-domain resample and event insertion are what the batched entry
     # points do for B routes (vap_profile_routes -> vap_route_limits + vap_velocity_pass_limits -> vap_time_profile_routes

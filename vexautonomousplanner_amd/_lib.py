@@ -36,6 +36,18 @@ VELOCITY_LANES, VELOCITY_LANES_16, VELOCITY_LANES_32, VELOCITY_LANES_64 = 6, 7, 
 VELOCITY_RELAX_ROUNDS = 10
 LUT_SAMPLES = 1000
 SAMPLES_PER_NODE = 1000
+CLOSEST_GUI, CLOSEST_EXACT = 0, 1
+CLOSEST_MODES = {"gui": CLOSEST_GUI, "exact": CLOSEST_EXACT}
+
+
+def closest_mode(mode):
+    """"gui" | "exact" (or VAP_CLOSEST_GUI / VAP_CLOSEST_EXACT) -> the C-ABI value."""
+    if mode in (CLOSEST_GUI, CLOSEST_EXACT) and not isinstance(mode, bool):
+        return int(mode)
+    try:
+        return CLOSEST_MODES[str(mode).lower()]
+    except KeyError:
+        raise ValueError(f"closest-point mode must be 'gui' or 'exact' (got {mode!r})") from None
 
 # every symbol include/vap.h declares; tests check the library exports exactly these
 EXPORTS = (
@@ -48,6 +60,7 @@ EXPORTS = (
     "vap_route_lookup", "vap_route_sample_count", "vap_route_forward_backward", "vap_route_motion_profile",
     "vap_grid_distances", "vap_route_limits", "vap_velocity_pass_limits", "vap_time_insert_waits", "vap_fit_ex",
     "vap_profile_routes", "vap_time_profile_routes", "vap_time_insert_events", "vap_limit_rows_dtype",
+    "vap_closest_points", "vap_route_closest",
 )
 
 
@@ -150,6 +163,8 @@ def lib():
                                              C.c_int, ip, dp, dp, dp, dp, dp, dp]
     L.vap_route_motion_profile.argtypes = [vp, C.POINTER(Constraints), C.c_double, C.c_double, C.c_long, dp, lp,
                                            lp, ip, lp, ip]
+    L.vap_closest_points.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 7
+    L.vap_route_closest.argtypes = [vp, C.c_int, C.c_int, dp, dp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("vap_version", "vap_device_count"):

@@ -395,5 +395,46 @@ class BatchedTrajectoryGenerator:
         out["actions_map"] = out["actions_map"][:, :M]
         return out
 
+    def closest_points(self, result, queries, mode="gui", out=None):
+        """Closest point on every path of the batch ``profile`` / ``profile_routes`` has just produced with this
+        generator (vap_closest_points; gui/path.py:658-727 PathWidget.find_closest_point_on_path).
+
+          queries  fp64 tensor on this device, feet: (B, Q, 2) per path, or (Q, 2) shared by every path
+          mode     "gui": the GUI's two-pass search reproduced exactly (25*W+1 coarse steps, 501 fine ones around the
+                   coarse winner, first index wins); "exact": the true nearest point of the whole path
+        Returns a dict of fp64 tensors: parameter (B, Q), point (B, Q, 2), distance, arc_length (s at the parameter, from
+        the path's own lookup table) and cross_track (B, Q) (+distance when the query lies left of the path's direction),
+        plus flags (B,): the result's flags, with VAP_FLAG_DEGENERATE for a path of zero length.  Paths flagged
+        VAP_FLAG_BAD_ROUTE or of zero length get NaN rows.  ``out``: an optional dict of tensors of these shapes to fill."""
+        last = getattr(self, "_last_shape", None)
+        if last is None:
+            raise ValueError("closest_points needs the result of this generator's last profile() call")
+        self._check_current(result, "closest_points")
+        B, W = last[0], last[1]
+        q = queries
+        if not isinstance(q, torch.Tensor) or q.device != self.device or q.dtype != torch.float64:
+            raise ValueError(f"queries must be an fp64 tensor on {self.device}")
+        if q.dim() == 3 and q.shape[0] == B and q.shape[2] == 2:
+            shared, Q = 0, int(q.shape[1])
+        elif q.dim() == 2 and q.shape[1] == 2:
+            shared, Q = 1, int(q.shape[0])
+        else:
+            raise ValueError(f"queries must be ({B}, Q, 2) or (Q, 2), got {tuple(q.shape)}")
+        q = q.contiguous()
+        m = _lib.closest_mode(mode)
+        res = {} if out is None else out
+        shapes = {"parameter": (B, Q), "point": (B, Q, 2), "distance": (B, Q), "arc_length": (B, Q), "cross_track": (B, Q)}
+        for k, shp in shapes.items():
+            t = res.get(k)
+            if t is None or tuple(t.shape) != shp or t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous():
+                res[k] = torch.empty(shp, dtype=torch.float64, device=self.device)
+        res["flags"] = result["flags"].clone()
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._L.vap_closest_points(self.ctx.handle, B, W, Q, m, shared, ptr(q), ptr(res["parameter"]),
+                                              ptr(res["point"]), ptr(res["distance"]), ptr(res["arc_length"]),
+                                              ptr(res["cross_track"]), ptr(res["flags"])), "vap_closest_points")
+        return res
+
     def timing(self):
         return self.ctx.last_timing()

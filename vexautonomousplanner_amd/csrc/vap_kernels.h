@@ -141,4 +141,23 @@ hipError_t launch_basis(hipStream_t st, int order, int n, const double *t, doubl
 hipError_t launch_lookup(hipStream_t st, int W, const double *seg, double t_max, const double *lut, int what,
                          int n, const double *in, double *out);
 
+// Closest-point projection (vap_closest.hip).  A batch on the context (sptab NULL: plain paths, one spline each) or the
+// one route of vap_route_closest (r_* arrays: its per-spline tables, B = 1).
+struct ClosestSrc {
+    int W = 0;
+    const double *seg = nullptr;     // [B][W-1][12]
+    const double *lut = nullptr;     // path b's tables at lut + b * lut_stride: [n_spl][lut_n]
+    size_t lut_stride = 0;
+    int lut_n = 0;
+    const double *sptab = nullptr;   // batch of routes: [B][NS][kSplineStride], nspl [B]
+    const int *nspl = nullptr;
+    int NS = 0;
+    const double *r_tmax = nullptr, *r_dist0 = nullptr, *r_param0 = nullptr;   // one route: [r_nspl] each
+    const int *r_seg0 = nullptr;
+    int r_nspl = 0;
+    int seg_lds = 0;                 // (set by the launcher)
+};
+hipError_t launch_closest(hipStream_t st, ClosestSrc src, int B, int Q, int mode, int shared_queries, const double *queries,
+                          double *t, double *pt, double *d, double *s, double *ct, uint32_t *flags);
+
 }  // namespace vap

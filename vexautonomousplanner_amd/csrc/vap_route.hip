@@ -878,6 +878,49 @@ int vap_route_lookup(vap_route *rt, int what, int n, const double *h_in, double 
     return route_vector_call(rt, 1, what, n, h_in, h_out, 1);
 }
 
+// gui/path.py:658-727 on this route (vap_closest.hip): queries in, rows {t, x, y, distance, s, cross_track} out
+int vap_route_closest(vap_route *rt, int mode, int n, const double *h_queries, double *h_out)
+{
+    if (!rt) return vap_fail(VAP_ERR_UNFITTED, "No splines have been initialized");
+    VAP_TRY(vap_set_device(rt->ctx));
+    if (mode != VAP_CLOSEST_GUI && mode != VAP_CLOSEST_EXACT) return vap_fail(VAP_ERR_INVALID, "mode must be VAP_CLOSEST_GUI or VAP_CLOSEST_EXACT");
+    if (n < 0 || (n > 0 && (!h_queries || !h_out))) return vap_fail(VAP_ERR_INVALID, "bad argument");
+    if (n == 0) return VAP_OK;
+    hipStream_t st = rt->ctx->stream;
+    vap_ctx *ctx = rt->ctx;
+    VAP_TRY(ctx->ensure(ctx->small_in, sizeof(double) * 2 * (size_t)n));
+    VAP_TRY(ctx->ensure(ctx->small_out, sizeof(double) * 6 * (size_t)n));
+    double *din = (double *)ctx->small_in.ptr, *dout = (double *)ctx->small_out.ptr;
+    HIP_TRY(hipMemcpyAsync(din, h_queries, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, st));
+    vap::ClosestSrc src;
+    src.W = rt->W;
+    src.seg = rt->d.seg;
+    src.lut = rt->d.lut;
+    src.lut_stride = 0;
+    src.lut_n = rt->d.lut_n;
+    src.r_tmax = rt->d.sp_tmax;
+    src.r_dist0 = rt->d.sp_dist0;
+    src.r_param0 = rt->d.sp_param0;
+    src.r_seg0 = rt->d.sp_seg0;
+    src.r_nspl = rt->n_splines;
+    // column blocks t | x,y | distance | s | cross_track, interleaved into rows on the host
+    HIP_TRY(vap::launch_closest(st, src, 1, n, mode, 0, din, dout, dout + n, dout + 3 * (size_t)n, dout + 4 * (size_t)n,
+                                dout + 5 * (size_t)n, nullptr));
+    std::vector<double> cols(6 * (size_t)n);
+    HIP_TRY(hipMemcpyAsync(cols.data(), dout, sizeof(double) * 6 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i = 0; i < n; i++) {
+        double *o = h_out + 6 * (size_t)i;
+        o[0] = cols[i];
+        o[1] = cols[(size_t)n + 2 * i];
+        o[2] = cols[(size_t)n + 2 * i + 1];
+        o[3] = cols[3 * (size_t)n + i];
+        o[4] = cols[4 * (size_t)n + i];
+        o[5] = cols[5 * (size_t)n + i];
+    }
+    return VAP_OK;
+}
+
 // lays out and fills the distance-domain arrays in rt->work; returns pointers through `a`
 struct RouteArrays {
     double *t, *kap, *th, *x, *y, *vinit, *acc_f, *acc_b, *maxacc, *scal, *vel;

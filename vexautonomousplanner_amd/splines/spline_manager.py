@@ -7,6 +7,7 @@ What runs where (SM = the reference's splines/spline_manager.py):
   precompute_path_properties      -> nothing is materialised: get_curvature / get_heading evaluate
                                      the table entry the reference's step lookup would read    SM:477-580
   get_*_at_parameter, distance_to_time, get_curvature, get_heading -> vap_route_eval / vap_route_lookup
+  find_closest_point(s)           -> vap_route_closest (the GUI's closest-point search, gui/path.py:658-727)
 """
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
@@ -91,6 +92,23 @@ class QuinticHermiteSplineManager:
         """Vector form (one launch) of get_point_at_parameter — what a redraw wants (gui/path.py:370-373)."""
         self._require()
         return self._route.eval(0, ts)
+
+    def find_closest_point(self, point, mode="gui"):
+        """PathWidget.find_closest_point_on_path (gui/path.py:658-727) in feet, one launch: (point (2,), parameter), or
+        (None, None) for a path of zero length (gui/path.py:670-679).  mode "gui" is the GUI's own two-pass search
+        exactly; "exact" the true nearest point of the whole path."""
+        self._require()
+        row = self._route.closest(mode, np.asarray(point, dtype=np.float64).reshape(1, 2))[0]
+        if np.isnan(row[0]):
+            return None, None
+        return row[1:3].copy(), float(row[0])
+
+    def find_closest_points(self, points, mode="gui"):
+        """Vector form of find_closest_point: points (n, 2) feet -> (closest points (n, 2), parameters (n,)); NaN rows
+        for a path of zero length."""
+        self._require()
+        rows = self._route.closest(mode, points)
+        return rows[:, 1:3].copy(), rows[:, 0].copy()
 
     def get_magnitudes_at_parameter(self, idx):
         """SM:174-202."""
