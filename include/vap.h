@@ -105,7 +105,7 @@ int vap_ctx_synchronize(vap_ctx *ctx);
  * direction; RELAX_ROUNDS forces the earlier form of that kernel (one launch per super-round, convergence checked
  * on the host) — the same rows bit for bit (tests). */
 enum { VAP_OPT_VELOCITY_KERNEL = 0, VAP_OPT_F32_RECURRENCE = 1, /* 2: retired (sampling inside the velocity kernel, rounds 3-4) */
-       VAP_OPT_TIME_DOMAIN_RESIDUAL = 3, VAP_OPT_TIME_KERNEL = 4 };
+       VAP_OPT_TIME_DOMAIN_RESIDUAL = 3, VAP_OPT_TIME_KERNEL = 4, VAP_OPT_FOOTPRINT_CULL = 5 };
 enum { VAP_VELOCITY_AUTO = 0, VAP_VELOCITY_SEQ_LITERAL = 1, VAP_VELOCITY_SEQ_FAST = 2, VAP_VELOCITY_RELAX = 3,
        VAP_VELOCITY_RELAX_BLOCK = 4 /* workgroup per path */, VAP_VELOCITY_RELAX_WAVE = 5 /* wave per path, fp32 */,
        VAP_VELOCITY_LANES = 6 /* lane per path, fp64 recurrence */, VAP_VELOCITY_LANES_16 = 7, VAP_VELOCITY_LANES_32 = 8,
@@ -132,6 +132,9 @@ enum { VAP_RECURRENCE_F64 = 0, VAP_RECURRENCE_F32 = 1 };
  * the shadow of the recurrence); AUTO takes it while that is at most one workgroup per CU (B <= 16 x CUs), and batches of
  * routes (vap_time_profile_routes) never do. */
 enum { VAP_TIME_KERNEL_AUTO = 0, VAP_TIME_KERNEL_LANE = 1, VAP_TIME_KERNEL_QUAD = 2, VAP_TIME_KERNEL_FUSED = 3 };
+/* VAP_OPT_FOOTPRINT_CULL (1 = on, the default; 0 = off): vap_footprint_clearance skips, per row, every element whose
+ * bounding-circle lower bound exceeds the row's running minimum (plus a small slack).  A skipped element could not have
+ * become the row's minimum, so every output is the same bit for bit either way; 0 tests every element (tests). */
 int vap_ctx_set_option(vap_ctx *ctx, int option, int value);
 /* Enable/disable per-stage hipEvent timing (replaces the reference's time.time() log lines,
  * SM:587-594, MPG:398-411).  Off by default. */
@@ -466,6 +469,49 @@ int vap_closest_points(vap_ctx *ctx, int B, int W, int Q, int mode, int shared_q
 /* gui/path.py:658-727 on one route, host buffers: one copy each way and one launch.  h_queries [n][2] feet;
  * h_out [n][6] = t, x, y, distance, arc_length, cross_track (NaN rows for a route of zero length). */
 int vap_route_closest(vap_route *route, int mode, int n, const double *h_queries, double *h_out);
+
+/* ---- robot-footprint clearance of time-domain rows --------------------------------------------------------------
+ * Is a batch of trajectories drivable: does the robot's body stay on the field and off the field elements at every row?
+ * The reference only previews the footprint (gui/path.py:764-809 PathWidget.draw_rect: the robot rectangle rotated to the
+ * path direction, robot.width / robot.length in inches from config.yaml, gui/settings_widget.py:101-107); it never
+ * checks it.  Units: feet, in the rows' own frame (the GUI's field frame: origin at the field centre, y down the image).
+ *
+ *   rows      d_rows [B][capacity][8] fp64 = {time, position, velocity, acceleration, heading, angular_vel, x, y} as
+ *             vap_time_profile[_routes] / vap_time_insert_events write them; only rows r < d_counts[b * counts_stride]
+ *             exist (counts_stride = 2 for the time-profile counts, 3 for the event-insertion counts; a count outside
+ *             [0, capacity] is clamped to it).  The kernel reads columns 4, 6 and 7 only.
+ *   pose      position (x, y); body angle phi = -heading.  The reference writes heading = -wrap(atan2(dy, dx) - pi *
+ *             reversed) (MPG:555-563), so phi is the direction the robot's front faces: the direction of travel on
+ *             forward segments, its opposite on reversed ones, the turning heading on in-place turn rows.  A body-frame
+ *             point v sits at (x, y) + R(phi) v, R(phi) = [[cos, -sin], [sin, cos]].
+ *   footprint h_footprint [n_foot][2], body frame (+x = the robot's front), convex, counter-clockwise, 3..16 vertices.
+ *   scene     shared by every route of the call:
+ *             h_field  [4] = xmin, ymin, xmax, ymax (NULL = no walls);
+ *             polygons h_poly_xy [h_poly_start[n_poly]][2], polygon i = vertices h_poly_start[i] .. h_poly_start[i+1]-1,
+ *                      convex, counter-clockwise, 3..16 vertices each (h_poly_start[0] = 0);
+ *             circles  h_circles [n_circle][3] = cx, cy, r (r > 0).
+ *             Collinear or duplicate vertices, clockwise or non-convex polygons, a non-positive radius, an empty or
+ *             non-finite box: VAP_ERR_INVALID.  More than 256 polygons, 4096 polygon vertices or 256 circles:
+ *             VAP_ERR_UNSUPPORTED.  The scene is host memory; it is validated and uploaded once per call.
+ *   clearance of a row against one element, signed (negative = contact):
+ *             wall     min over footprint vertices p of min(p.x - xmin, xmax - p.x, p.y - ymin, ymax - p.y);
+ *             polygon  separated: the Euclidean distance (min of the vertex-to-edge distances both ways); overlapping:
+ *                      minus the smallest projection overlap over the edge normals of both polygons (the separating-axis
+ *                      test); touching gives 0;
+ *             circle   the signed distance from the centre to the footprint polygon (positive outside), minus r.
+ *             Element ids: the wall -1, polygons 0..n_poly-1, circles n_poly..n_poly+n_circle-1.  A row's clearance is the
+ *             minimum over every element; on an exact tie the smallest id wins.
+ *   outputs   per route [B], any pointer may be NULL: d_min_clearance (minimum over the route's rows), d_min_row (the first
+ *             row at that minimum), d_min_element (the element at that row), d_first_row (the first row with clearance <
+ *             margin, or -1), d_n_below (rows with clearance < margin).  A route without rows gets NaN, -1, -1, -1, 0.
+ *             d_row_clearance [B][capacity] (optional): each row's clearance, NaN from counts[b] on.
+ * The check is discrete at the rows' dt: motion between two rows is not swept.  A caller who wants a guard band passes
+ * margin > 0 (one 10 ms row moves at most max_vel * dt, 0.04 ft at 4 ft/s).  B = 0 is a no-op. */
+int vap_footprint_clearance(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride,
+                            int n_foot, const double *h_footprint, const double *h_field, int n_poly, const int *h_poly_start,
+                            const double *h_poly_xy, int n_circle, const double *h_circles, double margin,
+                            double *d_row_clearance, double *d_min_clearance, int *d_min_row, int *d_min_element,
+                            int *d_first_row, int *d_n_below);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,7 @@ OPT_VELOCITY_KERNEL = 0
 OPT_TIME_DOMAIN_RESIDUAL = 3
 OPT_F32_RECURRENCE = 1
 OPT_TIME_KERNEL = 4
+OPT_FOOTPRINT_CULL = 5
 TIME_KERNEL_AUTO, TIME_KERNEL_LANE, TIME_KERNEL_QUAD, TIME_KERNEL_FUSED = 0, 1, 2, 3
 RECURRENCE_F64, RECURRENCE_F32 = 0, 1
 VELOCITY_AUTO, VELOCITY_SEQ_LITERAL, VELOCITY_SEQ_FAST, VELOCITY_RELAX = 0, 1, 2, 3
@@ -60,7 +61,7 @@ EXPORTS = (
     "vap_route_lookup", "vap_route_sample_count", "vap_route_forward_backward", "vap_route_motion_profile",
     "vap_grid_distances", "vap_route_limits", "vap_velocity_pass_limits", "vap_time_insert_waits", "vap_fit_ex",
     "vap_profile_routes", "vap_time_profile_routes", "vap_time_insert_events", "vap_limit_rows_dtype",
-    "vap_closest_points", "vap_route_closest",
+    "vap_closest_points", "vap_route_closest", "vap_footprint_clearance",
 )
 
 
@@ -165,6 +166,8 @@ def lib():
                                            lp, ip, lp, ip]
     L.vap_closest_points.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 7
     L.vap_route_closest.argtypes = [vp, C.c_int, C.c_int, dp, dp]
+    L.vap_footprint_clearance.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_int, dp, dp, C.c_int, ip, dp,
+                                          C.c_int, dp, C.c_double] + [vp] * 6
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("vap_version", "vap_device_count"):

@@ -436,5 +436,16 @@ class BatchedTrajectoryGenerator:
                                               ptr(res["cross_track"]), ptr(res["flags"])), "vap_closest_points")
         return res
 
+    def footprint_clearance(self, tp, footprint, scene, margin=0.0, per_row=False, out=None, cull=True):
+        """Robot-footprint clearance of the rows of ``tp`` — the dict ``time_profile`` or ``insert_waits`` returned —
+        against ``scene`` (vap_footprint_clearance on this generator's context and torch's current stream; see
+        footprint.clearance for the definitions and the returned dict of (B,) tensors).  ``footprint``: (n, 2) body-frame
+        polygon in feet, e.g. footprint.rectangle(width_in, length_in)."""
+        from . import footprint as fp
+        rows, counts = tp["rows"], tp["counts"]
+        if rows.device != self.device:
+            raise ValueError(f"rows must be on {self.device}")
+        return fp.clearance(rows, counts, footprint, scene, margin=margin, per_row=per_row, out=out, ctx=self.ctx, cull=cull)
+
     def timing(self):
         return self.ctx.last_timing()

@@ -253,13 +253,15 @@ int vap_ctx_destroy(vap_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     VapBuffer *bufs[] = {&ctx->sptab, &ctx->nspl, &ctx->k64, &ctx->dth64, &ctx->ufwd, &ctx->vhi, &ctx->vres, &ctx->lstate, &ctx->lcount, &ctx->seg, &ctx->power, &ctx->lut, &ctx->slopes, &ctx->aux, &ctx->runs, &ctx->meta, &ctx->dth, &ctx->flags, &ctx->small_in,
-                      &ctx->small_out, &ctx->small_seg, &ctx->small_lut};
+                      &ctx->small_out, &ctx->small_seg, &ctx->small_lut, &ctx->scene};
     for (VapBuffer *b : bufs)
         if (b->ptr) (void)hipFree(b->ptr);
     for (VapBuffer &b : ctx->io)
         if (b.ptr) (void)hipFree(b.ptr);
     for (auto &e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
+    if (ctx->scene_ev) (void)hipEventDestroy(ctx->scene_ev);
+    if (ctx->scene_host) (void)hipHostFree(ctx->scene_host);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return VAP_OK;
@@ -293,6 +295,10 @@ int vap_ctx_set_option(vap_ctx *ctx, int option, int value)
     }
     if (option == VAP_OPT_TIME_KERNEL && value >= VAP_TIME_KERNEL_AUTO && value <= VAP_TIME_KERNEL_FUSED) {
         ctx->time_kernel = value;
+        return VAP_OK;
+    }
+    if (option == VAP_OPT_FOOTPRINT_CULL && (value == 0 || value == 1)) {
+        ctx->footprint_cull = value;
         return VAP_OK;
     }
     if (option == VAP_OPT_F32_RECURRENCE && (value == VAP_RECURRENCE_F64 || value == VAP_RECURRENCE_F32)) {

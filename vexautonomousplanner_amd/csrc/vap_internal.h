@@ -59,6 +59,13 @@ struct vap_ctx {
     //   !rows_hi: dth holds the |dtheta| rows in rows_dt (the fused call only; curvature comes from the caller)
     bool rows_valid = false, rows_hi = false;
     int rows_dt = 0;
+    // vap_footprint_clearance: the packed scene is built in pinned host memory and uploaded on the stream; scene_ev marks
+    // the end of the last upload, which the next call waits for before it rewrites the host block
+    int footprint_cull = 1;           // VAP_OPT_FOOTPRINT_CULL
+    VapBuffer scene;
+    void *scene_host = nullptr;
+    size_t scene_host_cap = 0;
+    hipEvent_t scene_ev = nullptr;
 
     int ensure(VapBuffer &b, size_t bytes)
     {

@@ -1,0 +1,225 @@
+"""Robot-footprint clearance of time-domain rows (vap_footprint_clearance, include/vap.h).
+
+Which candidate trajectories are drivable: does the robot's body stay on the field and off the field elements at every
+row?  The reference only previews the footprint (gui/path.py:764-809 PathWidget.draw_rect: the robot rectangle rotated to
+the path direction, robot.width / robot.length in inches from config.yaml, gui/settings_widget.py:101-107); this module
+checks it, on the device, for a whole batch of rows from ``BatchedTrajectoryGenerator.time_profile`` / ``insert_waits``.
+
+Frame and pose (all lengths in feet, in the rows' own frame: the GUI's field frame, origin at the field centre, y down
+the image): a row's robot sits at (x, y) = columns 6 and 7 with body angle phi = -heading (column 4; the reference writes
+heading = -wrap(atan2(dy, dx) - pi * reversed), MPG:555-563, so phi is the direction the robot's front faces).  A body
+point v maps to (x, y) + R(phi) v.
+
+Clearance (signed, negative = contact) of a row against the wall (id -1), each convex polygon (ids 0..P-1) and each
+circle (ids P..P+C-1) is defined in include/vap.h; a row's clearance is the minimum over them (the smallest id on a tie).
+The check is discrete at the rows' dt: motion between rows is not swept; pass ``margin > 0`` for a guard band (one 10 ms
+row moves at most max_vel * dt, 0.04 ft at 4 ft/s).
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+
+# gui/path.py:366-367: the 2000 px field image spans 12.1090395251 ft
+FIELD_FT = 12.1090395251
+DEFAULT_FIELD = (-FIELD_FT / 2, -FIELD_FT / 2, FIELD_FT / 2, FIELD_FT / 2)
+MAX_VERTICES = 16          # footprint and each polygon
+MAX_POLYGONS = 256
+MAX_POLYGON_VERTICES = 4096
+MAX_CIRCLES = 256
+ELEMENT_WALL = -1
+
+
+def rectangle(width_in, length_in, forward_offset_in=0.0):
+    """The robot's rectangle in the body frame, feet, counter-clockwise (4, 2): ``length_in`` runs along body x (the
+    robot's front), ``width_in`` along body y, both in inches as in config.yaml's robot.length / robot.width; the
+    rectangle's centre sits ``forward_offset_in`` inches ahead of the tracked point.
+
+    The GUI's preview (gui/path.py:787-797) puts ``width`` along the path instead; both default to 18 in there, which
+    hides the swap.  This helper follows the names: length is front to back."""
+    w, l, o = float(width_in) / 12.0, float(length_in) / 12.0, float(forward_offset_in) / 12.0
+    if not (w > 0 and l > 0) or not np.isfinite([w, l, o]).all():
+        raise ValueError(f"robot width and length must be positive and finite (got {width_in!r}, {length_in!r})")
+    return np.array([[o - l / 2, -w / 2], [o + l / 2, -w / 2], [o + l / 2, w / 2], [o - l / 2, w / 2]], dtype=np.float64)
+
+
+def convex_polygon(vertices, what="polygon"):
+    """``vertices`` (n, 2) as a convex, counter-clockwise fp64 array: a clockwise polygon is reversed; collinear or
+    duplicate vertices, a non-convex or self-intersecting outline, fewer than 3 or more than 16 vertices raise
+    ValueError (the checks of vap_footprint_clearance, which rejects clockwise input itself)."""
+    v = np.array(vertices, dtype=np.float64)
+    if v.ndim != 2 or v.shape[1] != 2:
+        raise ValueError(f"{what}: vertices must be (n, 2), got {v.shape}")
+    n = v.shape[0]
+    if n < 3 or n > MAX_VERTICES:
+        raise ValueError(f"{what}: {n} vertices (3..{MAX_VERTICES})")
+    if not np.isfinite(v).all():
+        raise ValueError(f"{what}: non-finite vertex")
+    area2 = float(np.sum(v[:, 0] * np.roll(v[:, 1], -1) - np.roll(v[:, 0], -1) * v[:, 1]))
+    if area2 < 0:
+        v = v[::-1].copy()
+    e1 = np.roll(v, -1, axis=0) - v
+    e2 = np.roll(e1, -1, axis=0)
+    l1, l2 = np.hypot(e1[:, 0], e1[:, 1]), np.hypot(e2[:, 0], e2[:, 1])
+    if (l1 == 0).any():
+        raise ValueError(f"{what}: duplicate vertex")
+    cr = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+    if (np.abs(cr) <= 1e-12 * l1 * l2).any():
+        raise ValueError(f"{what}: collinear vertices")
+    if (cr < 0).any():
+        raise ValueError(f"{what}: not convex")
+    turn = np.sum(np.arctan2(cr, e1[:, 0] * e2[:, 0] + e1[:, 1] * e2[:, 1]))
+    if abs(turn - 2 * np.pi) > 1e-6:
+        raise ValueError(f"{what}: not a simple polygon (winds {turn / (2 * np.pi):.3f} times)")
+    return v
+
+
+class Scene:
+    """The geometry every route of a clearance call is checked against.
+
+      field     (xmin, ymin, xmax, ymax) feet; "default" = the GUI image's extent +-12.1090395251/2 ft
+                (gui/path.py:366-367); None = no walls
+      polygons  sequence of (n, 2) convex polygons, 3..16 vertices each (clockwise ones are reversed; decompose
+                non-convex field elements into convex pieces)
+      circles   (C, 3) array-like of (cx, cy, r), r > 0
+    Validated here; more than 256 polygons, 4096 polygon vertices or 256 circles raise ValueError."""
+
+    def __init__(self, field="default", polygons=(), circles=()):
+        if isinstance(field, str):
+            if field != "default":
+                raise ValueError(f"field must be 'default', None or (xmin, ymin, xmax, ymax), got {field!r}")
+            field = DEFAULT_FIELD
+        if field is not None:
+            f = np.array(field, dtype=np.float64).reshape(-1)
+            if f.shape != (4,) or not np.isfinite(f).all() or not (f[0] < f[2] and f[1] < f[3]):
+                raise ValueError(f"field must be a finite, non-empty (xmin, ymin, xmax, ymax), got {field!r}")
+            field = f
+        self.field = field
+        polys = list(polygons)
+        if len(polys) > MAX_POLYGONS:
+            raise ValueError(f"{len(polys)} polygons: at most {MAX_POLYGONS}")
+        self.polygons = [convex_polygon(p, f"polygon {i}") for i, p in enumerate(polys)]
+        nv = sum(len(p) for p in self.polygons)
+        if nv > MAX_POLYGON_VERTICES:
+            raise ValueError(f"{nv} polygon vertices: at most {MAX_POLYGON_VERTICES}")
+        c = np.array(circles, dtype=np.float64).reshape(-1, 3) if len(circles) else np.zeros((0, 3))
+        if len(c) > MAX_CIRCLES:
+            raise ValueError(f"{len(c)} circles: at most {MAX_CIRCLES}")
+        if not np.isfinite(c).all():
+            raise ValueError("circles must be finite")
+        if (c[:, 2] <= 0).any():
+            raise ValueError("circle radii must be > 0")
+        self.circles = c
+        self.poly_start = np.cumsum([0] + [len(p) for p in self.polygons]).astype(np.int32)
+        self.poly_xy = (np.concatenate(self.polygons) if self.polygons else np.zeros((0, 2))).astype(np.float64)
+
+    @property
+    def n_polygons(self):
+        return len(self.polygons)
+
+    @property
+    def n_circles(self):
+        return len(self.circles)
+
+    def element_name(self, eid):
+        """'wall', 'polygon k' or 'circle k' for an element id."""
+        eid = int(eid)
+        if eid == ELEMENT_WALL:
+            return "wall"
+        if 0 <= eid < self.n_polygons:
+            return f"polygon {eid}"
+        if self.n_polygons <= eid < self.n_polygons + self.n_circles:
+            return f"circle {eid - self.n_polygons}"
+        raise ValueError(f"no element {eid}")
+
+
+def _dptr(a):
+    return a.ctypes.data_as(_lib.dp) if a is not None and a.size else None
+
+
+def clearance(rows, counts, footprint, scene, margin=0.0, per_row=False, out=None, device=0, ctx=None, cull=True):
+    """Footprint clearance of a batch of time-domain rows (vap_footprint_clearance).
+
+      rows       (B, capacity, 8) fp64 rows of time_profile / insert_waits — a device tensor (used in place) or a host
+                 array (uploaded once); (n, 8) for a single trajectory
+      counts     (B, k) int counts of that call (column 0 = rows), or (B,); None for a single trajectory (all n rows)
+      footprint  (n, 2) body-frame polygon in feet (e.g. ``rectangle(18, 18)``), +x = the robot's front
+      scene      a Scene
+      margin     rows with clearance < margin count as below (first_row, n_below, feasible)
+      per_row    also return row_clearance (B, capacity), NaN past counts
+      out        optional dict of tensors of the shapes below to fill
+      ctx        an _lib.Context (default: the device's shared context); cull: VAP_OPT_FOOTPRINT_CULL (outputs are the
+                 same either way)
+    Returns a dict of (B,) tensors: min_clearance, min_row, min_element, min_time (time of min_row), first_row,
+    first_time, n_below, feasible (n_below == 0), and row_clearance if asked.  A route without rows gets NaN / -1 / 0
+    (feasible).  Single trajectories give 0-d tensors (row_clearance (n,)).  Work runs on torch's current stream and is
+    not synchronised."""
+    if not isinstance(scene, Scene):
+        raise TypeError("scene must be a footprint.Scene")
+    foot = convex_polygon(footprint, "footprint")
+    if isinstance(rows, torch.Tensor):
+        dev = rows.device
+        if dev.type != "cuda" or rows.dtype != torch.float64:
+            raise ValueError("rows must be an fp64 tensor on a HIP device (or a host array)")
+    else:
+        dev = torch.device("cuda", device)
+        rows = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.float64), device=dev)
+    single = rows.dim() == 2
+    if single:
+        rows = rows.unsqueeze(0)
+    if rows.dim() != 3 or rows.shape[2] != 8:
+        raise ValueError(f"rows must be (B, capacity, 8) or (n, 8), got {tuple(rows.shape)}")
+    rows = rows.contiguous()
+    B, cap = int(rows.shape[0]), int(rows.shape[1])
+    if counts is None:
+        if not single:
+            raise ValueError("counts is needed for a batch of rows")
+        counts = torch.full((1, 1), cap, dtype=torch.int32, device=dev)
+    elif isinstance(counts, torch.Tensor):
+        counts = counts.to(device=dev, dtype=torch.int32)
+    else:
+        counts = torch.as_tensor(np.asarray(counts, dtype=np.int32), device=dev)
+    if counts.dim() < 2:
+        counts = counts.reshape(B, 1)
+    if counts.dim() != 2 or counts.shape[0] != B:
+        raise ValueError(f"counts must be ({B}, k) or ({B},), got {tuple(counts.shape)}")
+    counts = counts.contiguous()
+    res = {} if out is None else out
+    shapes = {"min_clearance": ((B,), torch.float64), "min_row": ((B,), torch.int32), "min_element": ((B,), torch.int32),
+              "first_row": ((B,), torch.int32), "n_below": ((B,), torch.int32)}
+    if per_row:
+        shapes["row_clearance"] = ((B, cap), torch.float64)
+    for k, (shp, dt) in shapes.items():
+        t = res.get(k)
+        if t is None or tuple(t.shape) != shp or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            res[k] = torch.empty(shp, dtype=dt, device=dev)
+    if ctx is None:
+        ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    ctx.set_option(_lib.OPT_FOOTPRINT_CULL, 1 if cull else 0)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    field = scene.field
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    _lib.check(ctx._L.vap_footprint_clearance(
+        ctx.handle, B, cap, ptr(rows), ptr(counts), int(counts.shape[1]), len(foot), _dptr(foot),
+        _dptr(field), scene.n_polygons, scene.poly_start.ctypes.data_as(_lib.ip), _dptr(scene.poly_xy), scene.n_circles,
+        _dptr(scene.circles), float(margin), ptr(res.get("row_clearance") if per_row else None), ptr(res["min_clearance"]),
+        ptr(res["min_row"]), ptr(res["min_element"]), ptr(res["first_row"]), ptr(res["n_below"])), "vap_footprint_clearance")
+    res["feasible"] = res["n_below"] == 0
+    res["min_time"] = _time_at(rows, res["min_row"])
+    res["first_time"] = _time_at(rows, res["first_row"])
+    if single:
+        for k in list(res):
+            res[k] = res[k][0]
+    return res
+
+
+def _time_at(rows, idx):
+    """rows[b, idx[b], 0], NaN where idx[b] < 0."""
+    B, cap = rows.shape[0], rows.shape[1]
+    if cap == 0:
+        return torch.full((B,), float("nan"), dtype=torch.float64, device=rows.device)
+    i = idx.long().clamp(0, cap - 1)
+    t = rows[torch.arange(B, device=rows.device), i, 0]
+    return torch.where(idx >= 0, t, torch.full_like(t, float("nan")))
