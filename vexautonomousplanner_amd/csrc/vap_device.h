@@ -206,6 +206,22 @@ __device__ __forceinline__ int lut_search_left(const double *__restrict__ D, dou
     }
     return lo;
 }
+// The same position without a loop: ten fixed halvings (kLutN < 2^10), one compare-and-select each, no exec-mask
+// bookkeeping.  For a non-decreasing table the count of entries below s is built bit by bit: a probe past the end reads
+// D[kLutN-1] (it accepts only when every entry is below s, and the count is clamped to kLutN), so the result is the
+// binary search's exactly.
+__device__ __forceinline__ int lut_search_left_fixed(const double *__restrict__ D, double s)
+{
+    static_assert(kLutN <= 1024 && kLutN >= 992, "ten halvings, the first five always inside the table");
+    int lo = 0;
+#pragma unroll
+    for (int step = 512; step > 0; step >>= 1) {
+        const int j = lo + step;
+        const int r = step >= 32 ? j - 1 : (j < kLutN ? j : kLutN) - 1;
+        lo = D[r] < s ? j : lo;
+    }
+    return lo < kLutN ? lo : kLutN;
+}
 
 // SM:291-318 distance_to_time.  D = lookup_table.distances (LDS or global), parameters are
 // linspace(0, t_max, 1000) (SM:443).  `end_param` = len(nodes)-1.

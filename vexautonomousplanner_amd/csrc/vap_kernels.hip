@@ -802,14 +802,48 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
         double tA[kSPT], sA[kSPT];
         int idxA[kSPT];
         bool redo[kSPT], any_redo = false;
+        // A1: distances and table entries.  The first sample searches the table (fixed halvings, no loop); each following
+        // one walks on from its predecessor's entry, which it passes at most once or twice where a table interval is longer
+        // than dd (config 3: ~10 samples per interval) — two entries in one LDS read, two compare-and-selects.  A sample
+        // that took both steps may have further to go: ONE rarely taken block after the four finishes the walk
+        // (`while (idx < kLutN - 1 && sD[idx] < s) idx++`, the same entry in every case).
+        bool walk_on[kSPT], any_walk = false;
 #pragma unroll
         for (int i = 0; i < kSPT; i++) {
             const int k = INTERIOR ? kbase + i : (kbase + i < N - 1 ? kbase + i : N - 1);
             if (i > 0) sk = sk + dd;
             const double s = INTERIOR ? sk : ((k == N - 1) ? total : sk);
-            if (i == 0) idx = lut_search_left(sD, s);
-            else while (idx < kLutN - 1 && sD[idx] < s) idx++;
-            if constexpr (!INTERIOR) idx = idx < 1 ? 1 : idx;
+            walk_on[i] = false;
+            if (i == 0) {
+                idx = lut_search_left_fixed(sD, s);
+                if constexpr (!INTERIOR) idx = idx < 1 ? 1 : idx;
+            } else {   // (idx >= 1 already: the walk only moves on)
+                const int i1 = idx + 1 < kLutN - 1 ? idx + 1 : kLutN - 1;
+                const double a0 = sD[idx], a1 = sD[i1];
+                const bool st1 = idx < kLutN - 1 && a0 < s;
+                const bool st2 = st1 && idx + 1 < kLutN - 1 && a1 < s;
+                idx += (int)st1 + (int)st2;
+                walk_on[i] = st2;
+                any_walk |= st2;
+            }
+            sA[i] = s;
+            idxA[i] = idx;
+        }
+        if (__builtin_expect(any_walk, 0)) {
+#pragma unroll
+            for (int i = 1; i < kSPT; i++) {
+                if (walk_on[i]) {
+                    int ix = idxA[i];
+                    while (ix < kLutN - 1 && sD[ix] < sA[i]) ix++;
+                    idxA[i] = ix;
+                }
+            }
+        }
+        // A2: parameters and property-table entries
+#pragma unroll
+        for (int i = 0; i < kSPT; i++) {
+            const double s = sA[i];
+            const int idx = idxA[i];
             const double d0 = sD[idx - 1];
             const double t0 = (double)(idx - 1) * lstep;
             const bool exact = INTERIOR ? false : (s <= 0.0 || s >= total);
@@ -825,8 +859,6 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
             bool near;
             jjv[i] = table_index_fast(t, tab_n, inv_tstep, near);
             tA[i] = t;
-            sA[i] = s;
-            idxA[i] = idx;
             redo[i] = near && !exact;
             any_redo |= redo[i];
         }
@@ -855,7 +887,17 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
             const double fx = horner3(c + kCoefD2, lt), fy = horner3(c + kCoefD2 + 4, lt);     // P''
             const double ss = fma(ex, ex, ey * ey);                               // SM:517
             const double num = fma(ex, fy, -(ey * fx));                           // SM:523
-            const double kap = (ss >= 1e-10) ? curvature_of(num, ss) : 0.0;       // SM:526-527
+            // SM:526-527.  HI: straight-line, the curvature of every sample, then the select (kept from being sunk back into
+            // a branch around P'' and the curvature, whose exec-mask bookkeeping costs more than it skips).  The other modes
+            // keep the branch: speculated, the curvature costs them registers they do not have (fp64: 130 spills).
+            double kap;
+            if constexpr (HI) {
+                double kc = curvature_of(num, ss);
+                asm volatile("" : "+v"(kc));
+                kap = (ss >= 1e-10) ? kc : 0.0;
+            } else {
+                kap = (ss >= 1e-10) ? curvature_of(num, ss) : 0.0;
+            }
             vk[i] = (OT)kap;
             if constexpr (HI) {
                 vd64[i] = 0.0;
