@@ -7,6 +7,7 @@ reference's own public functions on seeded synthetic waypoints and stores inputs
 
     python oracle/gen_golden.py            # all small cases (~1 min)
     python oracle/gen_golden.py --c2       # additionally the 256-waypoint x 1e6-sample case (~4 min)
+    python oracle/gen_golden.py --geom     # only the structured-geometry cases of tests/golden/geom/ (~1 min)
 
 What is captured per case (all fp64; waypoints are fp32-representable so that the fp32 device path
 and the fp64 reference see identical inputs):
@@ -20,6 +21,11 @@ and the fp64 reference see identical inputs):
   runsum : (case runsum_w2000) the samples where the running sum current_dist += dd selects another table
            entry than k*dd would
   profile: (case c1 only) the 9-tuple of generate_motion_profile (motion_profile_generator.py:389)
+
+The --geom leg runs the same capture on a fixed list of paths from tests/path_families.py (straight and
+axis-aligned runs, exact cusps, uneven steps, far / tiny coordinates, circles, zig-zags, two routes) and
+writes them to the subdirectory tests/golden/geom/, so golden_util.names() and the tests parametrised over it do
+not change.
 """
 import argparse
 import os
@@ -32,6 +38,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import refimport  # noqa: E402
 from vexautonomousplanner_amd.synth import (DEFAULT_CONSTRAINTS, DEFAULT_DD, END_VEL,  # noqa: E402
@@ -99,8 +106,9 @@ def node_arrays(W, node_attrs):
 
 
 def run_case(mods, name, wp, dd=DEFAULT_DD, samples=None, node_attrs=None, action_points=None,
-             constraints=DEFAULT_CONSTRAINTS, full_profile=False, keep="all"):
+             constraints=DEFAULT_CONSTRAINTS, full_profile=False, keep="all", out_dir=None):
     sm_mod, _, mpg = mods
+    out_dir = out_dir or OUT
     t0 = time.time()
     wp = np.asarray(wp, dtype=np.float64)
     W = len(wp)
@@ -184,15 +192,15 @@ def run_case(mods, name, wp, dd=DEFAULT_DD, samples=None, node_attrs=None, actio
         for nm, arr in zip(names, res[:8]):
             d["profile_" + nm] = np.array(arr, dtype=np.float64)
         d["profile_coords"] = np.array([np.asarray(p, dtype=np.float64) for p in res[8]])
-    os.makedirs(OUT, exist_ok=True)
-    path = os.path.join(OUT, name + ".npz")
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, name + ".npz")
     if "velocity_full" in d:
         # the whole row goes beside the fixture in pieces of 2^18 samples (a committed file stays under 1 MiB);
         # tests/golden_util.load joins them
         full = d.pop("velocity_full")
-        os.makedirs(os.path.join(OUT, "rows"), exist_ok=True)
+        os.makedirs(os.path.join(out_dir, "rows"), exist_ok=True)
         for k in range(0, len(full), ROW_PIECE):
-            np.savez_compressed(os.path.join(OUT, "rows", f"{name}.velocity_full.{k // ROW_PIECE}.npz"),
+            np.savez_compressed(os.path.join(out_dir, "rows", f"{name}.velocity_full.{k // ROW_PIECE}.npz"),
                                 rows=full[k:k + ROW_PIECE])
     np.savez_compressed(path, **d)
     print(f"{name}: W={W} N={len(vel)} L={total:.6f} dd={dd:.6g} "
@@ -374,10 +382,87 @@ def run_table_size_pins(mods):
     print(f"api/pin_table_sizes: {len(d)} arrays, {os.path.getsize(path) / 1024:.0f} KiB", flush=True)
 
 
+def geom_cases():
+    """The fixed list of tests/golden/geom/: (name, waypoints, run_case keywords).  Every family of tests/path_families.py
+    two or three times, one fixed grid (S = 64 or 257) and one reference grid (dd = 0.005 or 0.011) each; by construction
+    among them exactly east / west / north / south straight paths, a 2-waypoint straight path, exact cusps (the cusp
+    node an entry of the property table), a path at -1000 ft, one shorter than 0.2 ft, a 2-turn circle, two cases on which
+    the reference is discontinuous (a +-1 fp64 ulp change of the waypoints moves a velocity by > 1e-9:
+    straight_disc_*, manhattan_disc_*), and two routes (a reverse node on the cusp, 90-degree turns on corners)."""
+    import path_families as pf
+    cases = []
+
+    def add(name, wp, **kw):
+        cases.append((name, np.asarray(wp, dtype=np.float64), kw))
+
+    st5, st8 = pf.make("straight", 5, 5, 1), pf.make("straight", 5, 8, 2)          # east, north, west, south, random
+    add("straight_east_w5_S64", st5[0], samples=64, full_profile=True)
+    add("straight_north_w5_S257", st5[1], samples=257)
+    add("straight_west_w8_dd011", st8[2], dd=0.011)
+    add("straight_south_w8_dd005", st8[3], dd=0.005)
+    add("straight_w2_S64", pf.make("straight", 5, 2, 3)[4], samples=64)
+    add("straight_disc_w13_S257", pf.make("straight", 1, 13, 7)[0], samples=257)
+    mh = pf.make("manhattan", 10, 13, 7)
+    add("manhattan_w8_S257", pf.make("manhattan", 1, 8, 1)[0], samples=257)
+    add("manhattan_w13_dd005", mh[0], dd=0.005, full_profile=True)
+    add("manhattan_disc_w13_dd011", mh[9], dd=0.011)
+    add("uneven_w8_S257", pf.make("uneven", 1, 8, 1)[0], samples=257)
+    add("uneven_w5_dd011", pf.make("uneven", 1, 5, 2)[0], dd=0.011)
+    rv4, rv13, rv5 = pf.make("reversal", 3, 4, 1), pf.make("reversal", 3, 13, 1), pf.make("reversal", 3, 5, 1)
+    add("reversal_f1_w4_S257", rv4[0], samples=257)                                 # factor 1: node i+1 = node i-1
+    add("reversal_f1_w13_dd011", rv13[0], dd=0.011)
+    add("reversal_half_w5_S64", rv5[1], samples=64)
+    # a grid that READS the cusp's table entry: the step lookup returns the entry at a node only for a sample whose
+    # parameter is the node's exactly (SM:550-580), so dd is a quarter of the arc-length table's distance at the node
+    (node, _factor), = pf.reversal_cusps(1, 4, 1)
+    add("reversal_f1_w4_ddcusp", rv4[0], dd_to_node=(node, 4))
+    sc = pf.make("scale", 3, 8, 1)
+    add("scale_minus1000_w8_S257", sc[2], samples=257)
+    add("scale_plus100_w8_dd011", sc[1], dd=0.011)
+    add("scale_tiny_w5_dd005", pf.f32(make_waypoints(1, 5, 41)[0].astype(np.float64) * 0.02), dd=0.005)
+    th = np.arange(13) * 1.05                                                       # 12.6 rad: two turns of the unit circle
+    add("loops_two_turns_w13_S257", pf.f32(np.stack([np.cos(th), np.sin(th)], axis=1)), samples=257)
+    add("loops_w8_dd005", pf.make("loops", 1, 8, 1)[0], dd=0.005, full_profile=True)
+    add("west_w8_S64", pf.make("west", 1, 8, 1)[0], samples=64)
+    add("west_w5_dd011", pf.make("west", 1, 5, 2)[0], dd=0.011)
+    add("zigzag_w8_S257", pf.make("zigzag", 1, 8, 1)[0], samples=257)
+    add("zigzag_w5_dd005", pf.make("zigzag", 1, 5, 2)[0], dd=0.005)
+    # routes as users drive them: back up at the cusp, turn on the spot at corners
+    (node, _factor), = pf.reversal_cusps(1, 8, 3)
+    na = [{} for _ in range(8)]
+    na[node] = {"is_reverse_node": True}
+    add("route_reversal_w8", pf.make("reversal", 1, 8, 3)[0], node_attrs=na, full_profile=True)
+    wp, turns = pf.manhattan_turns(pf.make("manhattan", 4, 8, 5)[3])
+    na = [{} for _ in range(8)]
+    for i in np.nonzero(turns)[0][:2]:
+        na[int(i)] = {"turn": float(turns[i])}
+    add("route_manhattan_w8", wp, node_attrs=na, full_profile=True)
+    return cases
+
+
+def run_geom(mods, want):
+    out = os.path.join(OUT, "geom")
+    total = 0
+    for name, wp, kw in geom_cases():
+        if want(name):
+            if "dd_to_node" in kw:
+                node, div = kw.pop("dd_to_node")
+                mgr = build_manager(mods[0], wp)
+                mgr.rebuild_tables()
+                par = np.asarray(mgr.lookup_table.parameters)
+                j = int(np.argmin(np.abs(par - node)))
+                assert par[j] == float(node)
+                kw["dd"] = float(np.asarray(mgr.lookup_table.distances)[j]) / div
+            run_case(mods, name, wp, out_dir=out, **kw)
+            total += os.path.getsize(os.path.join(out, name + ".npz"))
+    print(f"geom: {total / 1024:.0f} KiB", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--c2", action="store_true", help="also run the 1e6-sample single-path case")
     ap.add_argument("--big", action="store_true", help="also the 2048-waypoint cases big_w2048_p* (~1-2 min of reference each)")
+    ap.add_argument("--geom", action="store_true", help="only the structured-geometry cases (tests/golden/geom/)")
     ap.add_argument("--only", default=None)
     ap.add_argument("--out", default=None, help="write the fixtures here instead of tests/golden/")
     args = ap.parse_args()
@@ -391,6 +476,10 @@ def main():
 
     def want(name):
         return args.only is None or args.only in name
+
+    if args.geom:
+        run_geom(mods, want)
+        return
 
     # plain-node paths at the reference's native grid (dd = 0.005 ft)
     for W in (2, 5, 8, 32):

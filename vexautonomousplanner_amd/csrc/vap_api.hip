@@ -391,7 +391,7 @@ int vap_sample(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, double dd, const
     HIP_TRY(vap::launch_sample(ctx->stream, dt == VAP_F64, B, W, S, (const double *)ctx->power.ptr, d_lut,
                                nullptr, d_meta, (const double *)ctx->aux.ptr,
                                (const double *)ctx->runs.ptr, d_x, d_y, d_heading, d_curvature, d_dtheta,
-                               hi ? (double *)ctx->k64.ptr : nullptr, hi ? (double *)ctx->dth64.ptr : nullptr));
+                               hi ? (double *)ctx->k64.ptr : nullptr, hi ? (double *)ctx->dth64.ptr : nullptr, d_segments));
     ctx->grid_B = B;
     ctx->grid_W = W;
     ctx->grid_S = S;
@@ -527,7 +527,7 @@ int vap_profile_batch(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, double dd
         HIP_TRY(vap::launch_sample(ctx->stream, f64, B, W, S, (const double *)ctx->power.ptr, (const double *)ctx->lut.ptr, nullptr,
                                    meta, (const double *)ctx->aux.ptr, (const double *)ctx->runs.ptr, d_x, d_y, d_heading,
                                    curv, hi ? nullptr : ctx->dth.ptr, hi ? (double *)ctx->k64.ptr : nullptr,
-                                   hi ? (double *)ctx->dth64.ptr : nullptr));
+                                   hi ? (double *)ctx->dth64.ptr : nullptr, (const double *)ctx->seg.ptr));
         tm.mark(VAP_T_SAMPLE);
         if (hi)
             VAP_TRY(run_velocity(ctx, true, false, B, S, cc, start_vel, end_vel, meta, ctx->k64.ptr, ctx->dth64.ptr, nullptr,
@@ -624,12 +624,13 @@ int vap_profile_routes(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, double d
         HIP_TRY(vap::launch_sample(ctx->stream, f64, B, W, S, (const double *)ctx->power.ptr, (const double *)ctx->lut.ptr,
                                    nullptr, meta, (const double *)ctx->aux.ptr,
                                    (const double *)ctx->runs.ptr, d_x, d_y, d_heading, curv, hi ? nullptr : ctx->dth.ptr,
-                                   hi ? (double *)ctx->k64.ptr : nullptr, hi ? (double *)ctx->dth64.ptr : nullptr));
+                                   hi ? (double *)ctx->k64.ptr : nullptr, hi ? (double *)ctx->dth64.ptr : nullptr,
+                                   (const double *)ctx->seg.ptr));
     else
         HIP_TRY(vap::launch_sample_routes(ctx->stream, f64, B, W, NS, S, (const double *)ctx->power.ptr, (const double *)ctx->lut.ptr,
                                           sptab, nspl, meta, (const double *)ctx->aux.ptr, (const double *)ctx->runs.ptr, d_x, d_y,
                                           d_heading, curv, hi ? nullptr : ctx->dth.ptr, hi ? (double *)ctx->k64.ptr : nullptr,
-                                          hi ? (double *)ctx->dth64.ptr : nullptr));
+                                          hi ? (double *)ctx->dth64.ptr : nullptr, (const double *)ctx->seg.ptr));
     tm.mark(VAP_T_SAMPLE);
     if (hi)
         VAP_TRY(run_velocity(ctx, true, false, B, S, cc, start_vel, end_vel, meta, ctx->k64.ptr, ctx->dth64.ptr, nullptr,

@@ -384,7 +384,7 @@ __device__ __forceinline__ float dtheta_f32(double ax, double ay, double bx, dou
                              -3.33329491539e-1f);
         dl = fmaf(p * z2, z, z);
     } else {
-        dl = atan2_f32(cr, dt);
+        dl = (cr == 0.0f && dt == 0.0f) ? thb - tha : atan2_f32(cr, dt);   // a zero vector: the raw difference (see dtheta_f64_general)
     }
     const float n = rintf(((thb - tha) - dl) * 0.15915494309189535f);
     return fabsf(fmaf(n, 6.283185307179586f, dl));
@@ -397,6 +397,16 @@ __device__ __forceinline__ float dtheta_f32(double ax, double ay, double bx, dou
 // (the general atan2 is the rare branch of dtheta_f64: kept out of line so that its register needs do not weigh on
 // the sampling kernel's straight path)
 __device__ __attribute__((noinline)) double atan2_out_of_line(double y, double x) { return atan2(y, x); }
+
+// The rare branch.  A zero derivative vector (the table entry of an exact cusp, SM:526-527) has no angle: the reference's
+// heading there is atan2(0, 0) = 0, so its difference to the neighbour's is the neighbour's raw heading — the difference
+// of the two atan2 values, not the angle between the vectors (cross = dot = 0 would give 0).
+__device__ __forceinline__ double dtheta_f64_general(double ax, double ay, double bx, double by)
+{
+    const double cr = fma(ax, by, -(ay * bx)), dt = fma(ax, bx, ay * by);
+    if (cr == 0.0 && dt == 0.0) return atan2_out_of_line(by, bx) - atan2_out_of_line(ay, ax);
+    return atan2_out_of_line(cr, dt);
+}
 
 __device__ __forceinline__ double dtheta_f64(double ax, double ay, double bx, double by, float tha, float thb)
 {
@@ -413,7 +423,7 @@ __device__ __forceinline__ double dtheta_f64(double ax, double ay, double bx, do
         const double p = fma(fma(fma(fma(fma(-1.0 / 11.0, z2, 1.0 / 9.0), z2, -1.0 / 7.0), z2, 1.0 / 5.0), z2, -1.0 / 3.0), z2, 1.0);
         dl = z * p;
     } else {
-        dl = atan2_out_of_line(cr, dt);
+        dl = dtheta_f64_general(ax, ay, bx, by);
     }
     const double n = rint(((double)(thb - tha) - dl) * 0.15915494309189535);
     return fabs(fma(n, 6.283185307179586, dl));
@@ -434,10 +444,6 @@ __device__ __forceinline__ double dtheta_f64_series(double ax, double ay, double
     const double z2 = z * z;
     const double p = fma(fma(fma(fma(fma(-1.0 / 11.0, z2, 1.0 / 9.0), z2, -1.0 / 7.0), z2, 1.0 / 5.0), z2, -1.0 / 3.0), z2, 1.0);
     return z * p;
-}
-__device__ __forceinline__ double dtheta_f64_general(double ax, double ay, double bx, double by)
-{
-    return atan2_out_of_line(fma(ax, by, -(ay * bx)), fma(ax, bx, ay * by));
 }
 __device__ __forceinline__ double dtheta_f64_wrap(double dl, float tha, float thb)
 {

@@ -56,13 +56,14 @@ hipError_t launch_route_offsets(hipStream_t st, int B, int W, int NS, int S, dou
                                 const int *nspl, double *meta, double *aux, double *runs, uint32_t *flags);
 hipError_t launch_sample_routes(hipStream_t st, bool f64, int B, int W, int NS, int S, const double *pw, const double *lut,
                                 const double *sptab, const int *nspl, const double *meta, const double *aux, const double *runs,
-                                void *x, void *y, void *h, void *k, void *dth, double *k64, double *dth64);
+                                void *x, void *y, void *h, void *k, void *dth, double *k64, double *dth64, const double *seg);
 hipError_t launch_lut_slopes(hipStream_t st, int B, const double *lut, const double *meta, double *slopes);
 hipError_t launch_grid(hipStream_t st, int B, int W, int S, double dd, double *meta, double *aux, double *runs,
                        uint32_t *flags);
 hipError_t launch_sample(hipStream_t st, bool f64, int B, int W, int S, const double *pw, const double *lut,
                          const double *slopes, const double *meta, const double *aux, const double *runs, void *x,
-                         void *y, void *h, void *k, void *dth, double *k64 = nullptr, double *dth64 = nullptr);
+                         void *y, void *h, void *k, void *dth, double *k64, double *dth64,
+                         const double *seg);   // seg: the paths' segment rows (the end tangent in the reference's form, k_sample)
 // per-sample max_acceleration rows of a batch of routes (vap_limits.hip makes them); all NULL for plain paths
 struct AccRowsV {
     const void *fwd = nullptr;   // [B][S] dtype: max_acc (= max_dec) of the forward step from sample i, MPG:194-196

@@ -566,6 +566,7 @@ __global__ void k_lut_slopes(int B, const double *__restrict__ lut, const double
 template <typename OT, bool COEF_LDS, bool HI, int PPB = 1>
 __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int S, int tile, int tiles_per_block,
                                                            const double *__restrict__ power,
+                                                           const double *__restrict__ seg_rows,
                                                            const double *__restrict__ lut,
                                                            const double *__restrict__ slopes,
                                                            const double *__restrict__ meta,
@@ -618,6 +619,17 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
         // for memory a second time)
         run_touch += runs[(size_t)b * kGridRunDoubles + (tid < 120 ? tid : 0)];
     }
+    // (the last segment's end-tangent row d1 for the end tangent below: asked for now, with the meta loads — it depends on
+    // the path's index alone — so that the one lane that uses it does not wait for memory once more)
+    __shared__ double s_end[PPB][2];
+    double end_d1x = 1.0, end_d1y = 1.0;
+    {
+        const int pp = tid < PPB ? tid : 0;
+        if (seg_rows && tid < PPB && p_live[pp]) {
+            end_d1x = seg_rows[((size_t)p_b[pp] * G + (G - 1)) * 12 + 6];
+            end_d1y = seg_rows[((size_t)p_b[pp] * G + (G - 1)) * 12 + 7];
+        }
+    }
     // the paths' tables are staged once and serve every tile of this workgroup; all loads first
     {
         constexpr int ITER = 4;
@@ -635,6 +647,26 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
             }
         }
         static_assert(ITER * kSampleThreads >= kLutN, "one pass covers the table");
+        // (here, between asking for the tables and using them: the lane's arithmetic runs while the workgroup waits for memory)
+        // The table's last entry (read by the path's last sample only) sits at the end of the last segment, where the
+        // reference's basis sum gives the end tangent exactly — a component that is an exact zero there (a path that ends
+        // along an axis) keeps its sign into atan2 (SM:536) — while the power form leaves a residue of either sign: -pi for
+        // +pi.  One lane per path evaluates the reference's form once; a component it puts at the zero level replaces the
+        // power form's in that sample (NaN: keep the power form's, bit for bit what it always was — taking both components
+        // from the reference's form on every path moves the last bits of an ordinary path's last heading and curvature, and with
+        // them the rows pinned by tests/test_gpu_sample_rows.py).  seg_rows is NULL only where a caller has no segment rows.
+#pragma unroll
+        for (int pp = 0; pp < PPB; pp++) {
+            if (tid == pp) {
+                double rx = 1.0, ry = 1.0;
+                // (P'(end) is the row d1 up to roundings and a parameter an ulp short of the end: only a path whose d1 has a
+                // component near zero can have one at the zero level, and only it pays for the reference's basis sum)
+                if (fabs(end_d1x) <= 1e-9 * fabs(end_d1y) || fabs(end_d1y) <= 1e-9 * fabs(end_d1x))
+                    hermite_eval_ref(seg_rows + (size_t)p_b[pp] * G * 12, p_tmax[pp], G, 1, (double)(W - 1), rx, ry);
+                s_end[pp][0] = fabs(rx) <= 1e-12 * fabs(ry) ? rx : __builtin_nan("");
+                s_end[pp][1] = fabs(ry) <= 1e-12 * fabs(rx) ? ry : __builtin_nan("");
+            }
+        }
         if constexpr (COEF_LDS) {
 #pragma unroll
             for (int pp = 0; pp < PPB; pp++)
@@ -883,7 +915,14 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
             int sg;
             normalize_inside(tp, G, lt, sg);
             const double *c = coef + sg * kCoefDoubles;
-            const double ex = horner4(c + kCoefD1, lt), ey = horner4(c + kCoefD1 + 5, lt);     // P'
+            double ex = horner4(c + kCoefD1, lt), ey = horner4(c + kCoefD1 + 5, lt);           // P'
+            if constexpr (!INTERIOR) {
+                if (__builtin_expect(jj == tab_n - 1, 0)) {   // the path's last sample (s_end: staged above; NaN = keep)
+                    const double rx = s_end[pp][0], ry = s_end[pp][1];
+                    ex = rx == rx ? rx : ex;
+                    ey = ry == ry ? ry : ey;
+                }
+            }
             const double fx = horner3(c + kCoefD2, lt), fy = horner3(c + kCoefD2 + 4, lt);     // P''
             const double ss = fma(ex, ex, ey * ey);                               // SM:517
             const double num = fma(ex, fy, -(ey * fx));                           // SM:523
@@ -2610,7 +2649,7 @@ hipError_t launch_grid(hipStream_t st, int B, int W, int S, double dd, double *m
 
 hipError_t launch_sample(hipStream_t st, bool f64, int B, int W, int S, const double *pw, const double *lut,
                          const double *slopes, const double *meta, const double *aux, const double *runs, void *x,
-                         void *y, void *h, void *k, void *dth, double *k64, double *dth64)
+                         void *y, void *h, void *k, void *dth, double *k64, double *dth64, const double *seg)
 {
     const bool hi = !f64 && k64 && dth64;
     // one workgroup stages a path's tables once and walks tiles_per_block consecutive tiles; paths are
@@ -2633,7 +2672,7 @@ hipError_t launch_sample(hipStream_t st, bool f64, int B, int W, int S, const do
     const size_t n_waves = (size_t)grid.x * grid.y * 4;
     if (want_stats) (void)hipMalloc(&stats, n_waves * 4 * sizeof(long long));
 #define VAP_SAMPLE(OT_, LDS_, HI_, PPB_)                                                                            \
-    hipLaunchKernelGGL((k_sample<OT_, LDS_, HI_, PPB_>), grid, dim3(kSampleThreads), lds, st, B, W, S, tile, tiles_per_block, pw, lut, \
+    hipLaunchKernelGGL((k_sample<OT_, LDS_, HI_, PPB_>), grid, dim3(kSampleThreads), lds, st, B, W, S, tile, tiles_per_block, pw, seg, lut, \
                        slopes, meta, aux, runs, (OT_ *)x, (OT_ *)y, (OT_ *)h, (OT_ *)k, (OT_ *)dth, k64, dth64, stats)
     if (ppb == 2) {
         if (f64) VAP_SAMPLE(double, true, false, 2);

@@ -246,6 +246,7 @@ __global__ void k_route_offsets(int B, int W, int NS, int S, double dd, const do
 constexpr int kRouteSPT = 4, kRouteThreads = 256, kRouteChunk = kRouteSPT * kRouteThreads;
 template <typename OT, bool HI>
 __global__ __launch_bounds__(kRouteThreads) void k_sample_routes(int W, int NS, int S, const double *__restrict__ power,
+                                                                 const double *__restrict__ seg_rows,
                                                                  const double *__restrict__ lut, const double *__restrict__ sptab,
                                                                  const int *__restrict__ nspl, const double *__restrict__ meta,
                                                                  const double *__restrict__ aux, const double *__restrict__ runs,
@@ -339,6 +340,14 @@ __global__ __launch_bounds__(kRouteThreads) void k_sample_routes(int W, int NS, 
         lutv_map_parameter(v, W, tp, sg, lt);
         const double *c = pw + (size_t)sg * kCoefDoubles;
         e.ex = horner4(c + kCoefD1, lt); e.ey = horner4(c + kCoefD1 + 5, lt);
+        if (__builtin_expect(jj == tab_n - 1, 0)) {
+            // the route's last table entry, read by its last sample only: the end of the last spline's last segment, where a
+            // component of the reference's end tangent that is an exact zero keeps its sign into atan2 (k_sample's rule)
+            double rx, ry;
+            hermite_d1_ref(seg_rows + ((size_t)b * G + sg) * 12, lt, rx, ry);
+            if (fabs(rx) <= 1e-12 * fabs(ry)) e.ex = rx;
+            if (fabs(ry) <= 1e-12 * fabs(rx)) e.ey = ry;
+        }
         const double fx = horner3(c + kCoefD2, lt), fy = horner3(c + kCoefD2 + 4, lt);
         const double ss = fma(e.ex, e.ex, e.ey * e.ey);
         const double num = fma(e.ex, fy, -(e.ey * fx));
@@ -452,13 +461,13 @@ hipError_t launch_route_offsets(hipStream_t st, int B, int W, int NS, int S, dou
 
 hipError_t launch_sample_routes(hipStream_t st, bool f64, int B, int W, int NS, int S, const double *pw, const double *lut,
                                 const double *sptab, const int *nspl, const double *meta, const double *aux, const double *runs,
-                                void *x, void *y, void *h, void *k, void *dth, double *k64, double *dth64)
+                                void *x, void *y, void *h, void *k, void *dth, double *k64, double *dth64, const double *seg)
 {
     const dim3 grid((S + kRouteChunk - 1) / kRouteChunk, B);
     const bool hi = !f64 && k64 && dth64;
     const size_t lds = sizeof(double) * (size_t)NS * (kSplineStride + 1);
 #define VAP_SR(OT_, HI_)                                                                                                     \
-    hipLaunchKernelGGL((k_sample_routes<OT_, HI_>), grid, dim3(kRouteThreads), lds, st, W, NS, S, pw, lut, sptab, nspl, meta, aux, runs, \
+    hipLaunchKernelGGL((k_sample_routes<OT_, HI_>), grid, dim3(kRouteThreads), lds, st, W, NS, S, pw, seg, lut, sptab, nspl, meta, aux, runs, \
                        (OT_ *)x, (OT_ *)y, (OT_ *)h, (OT_ *)k, (OT_ *)dth, k64, dth64)
     if (f64) VAP_SR(double, false);
     else if (hi) VAP_SR(float, true);
