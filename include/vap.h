@@ -134,7 +134,8 @@ enum { VAP_RECURRENCE_F64 = 0, VAP_RECURRENCE_F32 = 1 };
 enum { VAP_TIME_KERNEL_AUTO = 0, VAP_TIME_KERNEL_LANE = 1, VAP_TIME_KERNEL_QUAD = 2, VAP_TIME_KERNEL_FUSED = 3 };
 /* VAP_OPT_FOOTPRINT_CULL (1 = on, the default; 0 = off): vap_footprint_clearance skips, per row, every element whose
  * bounding-circle lower bound exceeds the row's running minimum (plus a small slack).  A skipped element could not have
- * become the row's minimum, so every output is the same bit for bit either way; 0 tests every element (tests). */
+ * become the row's minimum, so every output is the same bit for bit either way; 0 tests every element (tests).
+ * vap_footprint_conflicts: the same switch for its block and row bounds (0 tests every row of every pair exactly). */
 int vap_ctx_set_option(vap_ctx *ctx, int option, int value);
 /* Enable/disable per-stage hipEvent timing (replaces the reference's time.time() log lines,
  * SM:587-594, MPG:398-411).  Off by default. */
@@ -512,6 +513,48 @@ int vap_footprint_clearance(vap_ctx *ctx, int B, long capacity, const double *d_
                             const double *h_poly_xy, int n_circle, const double *h_circles, double margin,
                             double *d_row_clearance, double *d_min_clearance, int *d_min_row, int *d_min_element,
                             int *d_first_row, int *d_n_below);
+
+/* ---- robot-to-robot clearance between two batches of time-domain rows ---------------------------------------------
+ * Which of my candidates get along with my partner's routine?  vap_footprint_clearance treats the field as empty of other
+ * robots; this call poses two footprints, one per side, at the same instants and takes the clearance between them.
+ *
+ *   sides     A: d_rows_a [Ba][cap_a][8], d_counts_a with stride_a, footprint h_foot_a [n_foot_a][2];
+ *             O ("others"): d_rows_o [Bo][cap_o][8], d_counts_o with stride_o, footprint h_foot_o [n_foot_o][2].
+ *             Rows, counts (clamped to [0, capacity]) and the pose are vap_footprint_clearance's: only columns 4, 6, 7 are
+ *             read; position (x, y), body angle phi = -heading.  Both row sets must be on the same time step (the caller
+ *             guarantees it): row r of both sides is the same instant.  The two sides may be the same buffers (all pairs
+ *             inside one batch; the diagonal is then a robot against itself, for the caller to ignore).
+ *   shift     shift_rows (any sign): side O starts that many rows later.  With n_a, n_o the row counts,
+ *               pose_a(r) = row min(r, n_a - 1) of a,   pose_o(r) = row clamp(r - shift_rows, 0, n_o - 1) of o:
+ *             a robot that has not started, or has finished, stays on the field at its first or last pose.  A pair is
+ *             examined at rows r = 0 .. T - 1, T = max(n_a, n_o + shift_rows, 1).
+ *   clearance of a pair at a row: the polygon clearance above between the two posed footprints — separated: the Euclidean
+ *             distance; overlapping: minus the smallest projection overlap over the edge normals of both; touching: 0.
+ *             Symmetric in the two sides.  It saturates at minus the narrower footprint's extent once one projection
+ *             contains the other, so deep overlaps tie exactly over many rows.
+ *   pairing   VAP_CONFLICT_ALL_PAIRS: every (a, o), P = Bo.  VAP_CONFLICT_MATCHED: Ba == Bo, pairs (i, i) only, P = 1.
+ *   outputs   per pair [Ba][P], any pointer may be NULL: d_pair_clearance (the minimum over the pair's rows), d_pair_row
+ *             (the first row at that minimum), d_pair_first_row (the first row with clearance < margin, or -1).  A pair
+ *             with n_a == 0 or n_o == 0 gets NaN, -1, -1 and takes part in nothing below.
+ *             per A route [Ba], any pointer may be NULL: d_min_clearance (the minimum over its pairs), d_min_other (the
+ *             smallest o at that minimum), d_min_row (that pair's row), d_n_conflicts (pairs whose minimum is below
+ *             margin), d_first_row (the earliest pair first row >= 0, or -1).  A route without a valid pair gets NaN, -1,
+ *             -1, 0, -1.
+ * Footprints are host memory, validated as vap_footprint_clearance validates its footprint (VAP_ERR_INVALID).  MATCHED
+ * with Ba != Bo, a null row or count pointer with B > 0, a negative capacity: VAP_ERR_INVALID.  A capacity, or a horizon
+ * max(cap_a, cap_o + shift_rows) rounded up to 64 rows, above INT_MAX: VAP_ERR_UNSUPPORTED.  Ba = 0 or Bo = 0 is a no-op.
+ * Works on the context's stream and does not synchronise.  Context scratch grows with (Ba + Bo) x horizon x 32 B and with
+ * Ba x ceil(Bo / 16), never with Ba x Bo.  Outputs do not depend on scheduling: two calls on the same inputs give the same
+ * bits.  VAP_OPT_FOOTPRINT_CULL governs culling here too (block and row bounding circles before the exact pair); outputs
+ * are bit for bit the same either way.  Discrete at the rows' dt like the static check: pass margin > 0 for a guard band. */
+enum { VAP_CONFLICT_ALL_PAIRS = 0, VAP_CONFLICT_MATCHED = 1 };
+int vap_footprint_conflicts(vap_ctx *ctx, int pairing, int shift_rows, double margin,
+                            int Ba, long cap_a, const double *d_rows_a, const int *d_counts_a, int stride_a, int n_foot_a,
+                            const double *h_foot_a,
+                            int Bo, long cap_o, const double *d_rows_o, const int *d_counts_o, int stride_o, int n_foot_o,
+                            const double *h_foot_o,
+                            double *d_pair_clearance, int *d_pair_row, int *d_pair_first_row,
+                            double *d_min_clearance, int *d_min_other, int *d_min_row, int *d_n_conflicts, int *d_first_row);
 
 #ifdef __cplusplus
 }

@@ -39,6 +39,7 @@ LUT_SAMPLES = 1000
 SAMPLES_PER_NODE = 1000
 CLOSEST_GUI, CLOSEST_EXACT = 0, 1
 CLOSEST_MODES = {"gui": CLOSEST_GUI, "exact": CLOSEST_EXACT}
+CONFLICT_ALL_PAIRS, CONFLICT_MATCHED = 0, 1
 
 
 def closest_mode(mode):
@@ -61,7 +62,7 @@ EXPORTS = (
     "vap_route_lookup", "vap_route_sample_count", "vap_route_forward_backward", "vap_route_motion_profile",
     "vap_grid_distances", "vap_route_limits", "vap_velocity_pass_limits", "vap_time_insert_waits", "vap_fit_ex",
     "vap_profile_routes", "vap_time_profile_routes", "vap_time_insert_events", "vap_limit_rows_dtype",
-    "vap_closest_points", "vap_route_closest", "vap_footprint_clearance",
+    "vap_closest_points", "vap_route_closest", "vap_footprint_clearance", "vap_footprint_conflicts",
 )
 
 
@@ -168,6 +169,8 @@ def lib():
     L.vap_route_closest.argtypes = [vp, C.c_int, C.c_int, dp, dp]
     L.vap_footprint_clearance.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_int, dp, dp, C.c_int, ip, dp,
                                           C.c_int, dp, C.c_double] + [vp] * 6
+    side = [C.c_int, C.c_long, vp, vp, C.c_int, C.c_int, dp]
+    L.vap_footprint_conflicts.argtypes = [vp, C.c_int, C.c_int, C.c_double] + side + side + [vp] * 8
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("vap_version", "vap_device_count"):

@@ -447,5 +447,17 @@ class BatchedTrajectoryGenerator:
             raise ValueError(f"rows must be on {self.device}")
         return fp.clearance(rows, counts, footprint, scene, margin=margin, per_row=per_row, out=out, ctx=self.ctx, cull=cull)
 
+    def footprint_conflicts(self, tp, footprint, others, others_footprint=None, **kw):
+        """Robot-to-robot clearance of the rows of ``tp`` (footprint ``footprint``) against the rows of ``others``
+        (``others_footprint``, default the same) — both dicts as ``time_profile`` / ``insert_waits`` return them, on the
+        same time step (vap_footprint_conflicts on this generator's context and torch's current stream; see
+        footprint.conflicts for margin, shift_rows, pairing, pairs, out, cull and the returned dict)."""
+        from . import footprint as fp
+        for d in (tp, others):
+            if d["rows"].device != self.device:
+                raise ValueError(f"rows must be on {self.device}")
+        return fp.conflicts(tp["rows"], tp["counts"], footprint, others["rows"], others["counts"], others_footprint,
+                            ctx=self.ctx, **kw)
+
     def timing(self):
         return self.ctx.last_timing()

@@ -20,17 +20,15 @@
 #include <cstdint>
 #include <cstring>
 
-#include "vap_internal.h"
+#include "vap_footprint.h"
 
 namespace vap {
 
 constexpr int kFootThreads = 256;
 constexpr int kFootWaves = kFootThreads / 64;
-constexpr int kFootMaxVerts = 16;        // footprint and each polygon
 constexpr int kFootMaxPolys = 256;
 constexpr int kFootMaxPolyVerts = 4096;  // all polygons together
 constexpr int kFootMaxCircles = 256;
-constexpr double kCullSlack = 1e-9;      // ft, per ft of coordinate magnitude (rounding of the bound and of the exact tests)
 
 // Packed scene (fp64):
 //   foot  [n_foot][8]  body vertex x, y; outward unit normal of the edge to the next vertex nx, ny; that edge ex, ey;
@@ -48,16 +46,6 @@ struct FootScene {
     double slack;                         // kCullSlack * (1 + scene coordinate scale)
     int has_field, n_foot, n_poly, n_circle, cull;
 };
-
-// squared distance from p to the segment a -> a + e (il2 = 1 / |e|^2)
-__device__ __forceinline__ double seg_dist2(double px, double py, double ax, double ay, double ex, double ey, double il2)
-{
-    const double wx = px - ax, wy = py - ay;
-    double t = (wx * ex + wy * ey) * il2;
-    t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
-    const double dx = wx - t * ex, dy = wy - t * ey;
-    return dx * dx + dy * dy;
-}
 
 // the footprint's vertex i at the row's pose
 __device__ __forceinline__ void foot_vertex(const FootScene &s, int i, double x, double y, double c, double sn, double &wx,

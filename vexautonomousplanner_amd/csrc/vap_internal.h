@@ -66,6 +66,8 @@ struct vap_ctx {
     void *scene_host = nullptr;
     size_t scene_host_cap = 0;
     hipEvent_t scene_ev = nullptr;
+    // vap_footprint_conflicts: packed poses and per-64-row bounding circles of either side, per-tile partial results
+    VapBuffer conf_pack_a, conf_pack_o, conf_blk_a, conf_blk_o, conf_part;
 
     int ensure(VapBuffer &b, size_t bytes)
     {

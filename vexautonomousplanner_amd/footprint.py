@@ -1,4 +1,5 @@
-"""Robot-footprint clearance of time-domain rows (vap_footprint_clearance, include/vap.h).
+"""Robot-footprint clearance of time-domain rows (vap_footprint_clearance, include/vap.h), and robot-to-robot clearance
+between two batches of them (vap_footprint_conflicts, ``conflicts`` below).
 
 Which candidate trajectories are drivable: does the robot's body stay on the field and off the field elements at every
 row?  The reference only previews the footprint (gui/path.py:764-809 PathWidget.draw_rect: the robot rectangle rotated to
@@ -213,6 +214,139 @@ def clearance(rows, counts, footprint, scene, margin=0.0, per_row=False, out=Non
         for k in list(res):
             res[k] = res[k][0]
     return res
+
+
+def _side(rows, counts, dev, device, what):
+    """One side's rows and counts as contiguous device tensors: (rows (B, cap, 8), counts (B, k), single, device)."""
+    if isinstance(rows, torch.Tensor):
+        if rows.device.type != "cuda" or rows.dtype != torch.float64:
+            raise ValueError(f"{what}: rows must be an fp64 tensor on a HIP device (or a host array)")
+        if dev is not None and rows.device != dev:
+            raise ValueError(f"{what}: rows are on {rows.device}, the other side on {dev}")
+        dev = rows.device
+    else:
+        dev = dev if dev is not None else torch.device("cuda", device)
+        rows = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.float64), device=dev)
+    single = rows.dim() == 2
+    if single:
+        rows = rows.unsqueeze(0)
+    if rows.dim() != 3 or rows.shape[2] != 8:
+        raise ValueError(f"{what}: rows must be (B, capacity, 8) or (n, 8), got {tuple(rows.shape)}")
+    rows = rows.contiguous()
+    B = int(rows.shape[0])
+    if counts is None:
+        if not single:
+            raise ValueError(f"{what}: counts is needed for a batch of rows")
+        counts = torch.full((1, 1), int(rows.shape[1]), dtype=torch.int32, device=dev)
+    elif isinstance(counts, torch.Tensor):
+        counts = counts.to(device=dev, dtype=torch.int32)
+    else:
+        counts = torch.as_tensor(np.asarray(counts, dtype=np.int32), device=dev)
+    if counts.dim() < 2:
+        counts = counts.reshape(B, 1)
+    if counts.dim() != 2 or counts.shape[0] != B:
+        raise ValueError(f"{what}: counts must be ({B}, k) or ({B},), got {tuple(counts.shape)}")
+    return rows, counts.contiguous(), single, dev
+
+
+def _ccw_polygon(vertices, what):
+    """convex_polygon, but a clockwise outline raises like the C-ABI does instead of being reversed: with two robots in a
+    call, a silently mirrored vertex order is more likely a mistake than a convention."""
+    v = np.array(vertices, dtype=np.float64)
+    if v.ndim == 2 and v.shape[1] == 2 and len(v) >= 3 and np.isfinite(v).all():
+        if float(np.sum(v[:, 0] * np.roll(v[:, 1], -1) - np.roll(v[:, 0], -1) * v[:, 1])) < 0:
+            raise ValueError(f"{what}: vertices must be counter-clockwise")
+    return convex_polygon(v, what)
+
+
+PAIRINGS = {"all": _lib.CONFLICT_ALL_PAIRS, "matched": _lib.CONFLICT_MATCHED}
+
+
+def conflicts(rows_a, counts_a, footprint_a, rows_o, counts_o, footprint_o=None, margin=0.0, shift_rows=0, pairing="all",
+              pairs=False, out=None, device=0, ctx=None, cull=True):
+    """Robot-to-robot clearance between two batches of time-domain rows (vap_footprint_conflicts): which of side A's
+    candidates get along with the routines of side O ("others", e.g. the alliance partner)?
+
+      rows_a, counts_a   side A as in ``clearance``: (Ba, cap_a, 8) device tensor or host array with (Ba, k) / (Ba,)
+                         counts, or a single (n, 8) trajectory with counts None
+      footprint_a        (n, 2) body-frame polygon of side A's robot, feet
+      rows_o, counts_o   side O, the same conventions; its capacity and count stride may differ.  BOTH SIDES MUST BE ON THE
+                         SAME TIME STEP (the dt of time_profile / insert_waits): row r of both is the same instant.  The two
+                         sides may be the same tensors (all pairs inside one batch; ignore the diagonal)
+      footprint_o        side O's robot; None = the same as side A
+      margin             pairs with a clearance < margin somewhere conflict (n_conflicts, first_row, compatible)
+      shift_rows         side O starts that many rows later (any sign); a robot that has not started or has finished stays
+                         parked at its first / last pose
+      pairing            "all": every (a, o), P = Bo; "matched": Ba == Bo, pairs (i, i), P = 1
+      pairs              also return pair_clearance, pair_row, pair_first_row, each (Ba, P)
+      out, ctx, cull     as in ``clearance``
+    Returns a dict of (Ba,) tensors: min_clearance (over the route's pairs and rows), min_other (the smallest o there),
+    min_row, min_time (min_row x the rows' time step, read from column 0: the time since side A's start), first_row (the earliest row any pair
+    goes below margin, or -1), first_time, n_conflicts, compatible (n_conflicts == 0).  A route without a valid pair
+    (no rows on either side) gets NaN / -1 / 0 (compatible).  A single side-A trajectory gives 0-d tensors ((P,) for the
+    pair outputs).  Work runs on torch's current stream and is not synchronised."""
+    foot_a = _ccw_polygon(footprint_a, "footprint_a")
+    foot_o = foot_a if footprint_o is None else _ccw_polygon(footprint_o, "footprint_o")
+    if not isinstance(pairing, str) or pairing not in PAIRINGS:
+        raise ValueError(f"pairing must be 'all' or 'matched' (got {pairing!r})")
+    shift_rows = int(shift_rows)
+    given = [r.device for r in (rows_a, rows_o) if isinstance(r, torch.Tensor)]
+    rows_a, counts_a, single, dev = _side(rows_a, counts_a, given[0] if given else None, device, "side A")
+    rows_o, counts_o, _, _ = _side(rows_o, counts_o, dev, device, "side O")
+    Ba, cap_a, Bo, cap_o = int(rows_a.shape[0]), int(rows_a.shape[1]), int(rows_o.shape[0]), int(rows_o.shape[1])
+    if pairing == "matched" and Ba != Bo:
+        raise ValueError(f"matched pairing needs as many routes on both sides (got {Ba} and {Bo})")
+    P = 1 if pairing == "matched" else Bo
+    res = {} if out is None else out
+    shapes = {"min_clearance": ((Ba,), torch.float64), "min_other": ((Ba,), torch.int32), "min_row": ((Ba,), torch.int32),
+              "n_conflicts": ((Ba,), torch.int32), "first_row": ((Ba,), torch.int32)}
+    if pairs:
+        shapes.update(pair_clearance=((Ba, P), torch.float64), pair_row=((Ba, P), torch.int32),
+                      pair_first_row=((Ba, P), torch.int32))
+    for k, (shp, dt) in shapes.items():
+        t = res.get(k)
+        if t is None or tuple(t.shape) != shp or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            res[k] = torch.empty(shp, dtype=dt, device=dev)
+    if Bo == 0:                                   # nothing to meet: the C-ABI call is a no-op
+        res["min_clearance"].fill_(float("nan"))
+        for k in ("min_other", "min_row", "first_row"):
+            res[k].fill_(-1)
+        res["n_conflicts"].zero_()
+    if ctx is None:
+        ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    ctx.set_option(_lib.OPT_FOOTPRINT_CULL, 1 if cull else 0)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    pp = lambda k: ptr(res[k]) if pairs else None
+    _lib.check(ctx._L.vap_footprint_conflicts(
+        ctx.handle, PAIRINGS[pairing], shift_rows, float(margin),
+        Ba, cap_a, ptr(rows_a), ptr(counts_a), int(counts_a.shape[1]), len(foot_a), _dptr(foot_a),
+        Bo, cap_o, ptr(rows_o), ptr(counts_o), int(counts_o.shape[1]), len(foot_o), _dptr(foot_o),
+        pp("pair_clearance"), pp("pair_row"), pp("pair_first_row"), ptr(res["min_clearance"]), ptr(res["min_other"]),
+        ptr(res["min_row"]), ptr(res["n_conflicts"]), ptr(res["first_row"])), "vap_footprint_conflicts")
+    res["compatible"] = res["n_conflicts"] == 0
+    dt = _time_step((rows_a, counts_a), (rows_o, counts_o))
+    for k, idx in (("min_time", res["min_row"]), ("first_time", res["first_row"])):
+        t = idx.to(torch.float64) * dt
+        res[k] = torch.where(idx >= 0, t, torch.full_like(t, float("nan")))
+    if single:
+        for k in list(res):
+            res[k] = res[k][0]
+    return res
+
+
+def _time_step(*sides):
+    """The rows' time step as a 0-d device tensor, without a host round trip: column 0 of rows 1 and 0 of a route with
+    at least two rows (the largest such difference over both sides; they are all dt); NaN when no route has two rows."""
+    best = None
+    for rows, counts in sides:
+        if rows.shape[0] == 0 or rows.shape[1] < 2:
+            continue
+        d = torch.where(counts[:, 0] >= 2, rows[:, 1, 0] - rows[:, 0, 0], torch.full_like(rows[:, 0, 0], float("-inf"))).max()
+        best = d if best is None else torch.maximum(best, d)
+    if best is None:
+        return torch.tensor(float("nan"), dtype=torch.float64, device=sides[0][0].device)
+    return torch.where(torch.isinf(best), torch.full_like(best, float("nan")), best)
 
 
 def _time_at(rows, idx):
