@@ -556,6 +556,71 @@ int vap_footprint_conflicts(vap_ctx *ctx, int pairing, int shift_rows, double ma
                             double *d_pair_clearance, int *d_pair_row, int *d_pair_first_row,
                             double *d_min_clearance, int *d_min_other, int *d_min_row, int *d_n_conflicts, int *d_first_row);
 
+/* ---- closed-loop tracking rollouts of time-domain rows -----------------------------------------------------------
+ * How far does the robot stray from a route when it DRIVES it?  The two clearance calls judge the nominal rows; the robot
+ * feeds those rows (t, x, y, heading, v, omega: the columns trajectory_io.py writes into routes.h) to a path follower.
+ * This call rolls a differential-drive robot with a RAMSETE follower along every route of a batch, K times per route under
+ * K perturbation records, and returns the tracking error and, on request, the EXECUTED rows in the time-profile layout, so
+ * that both clearance calls accept them unchanged.  fp64 throughout.
+ *
+ *   rows      d_rows [B][capacity][8], d_counts with counts_stride as vap_footprint_clearance (n = the count clamped to
+ *             [0, capacity]); columns 2, 4, 5, 6 and 7 are read.
+ *   reference at row r: (x_r, y_r) = columns 6, 7; phi_r = -column 4; v_r = column 2; omega_r = -column 5 (the body rate:
+ *             MPG:576 writes angular_vel = -v * curvature beside the negated heading).  For the settle rows r >= n the
+ *             reference is row n - 1's pose with v_r = omega_r = 0.
+ *   follower  vap_follower: track_width T (ft), RAMSETE gains b and zeta, the wheel speed limit (ft/s), the tolerance the
+ *             route summary counts against (ft), n_substeps integration steps per row, settle_rows extra rows at the end.
+ *   perturb   d_perturb [B][K][8], or [K][8] for every route with shared_perturb != 0; a record is {dx, dy, dphi,
+ *             gain_left, gain_right, track_scale, tau, reserved}: a start offset, a gain on each wheel's actual speed, a
+ *             factor on the effective track width, and the time constant (s) of a first-order lag between commanded and
+ *             actual wheel speed.  The undisturbed record is {0, 0, 0, 1, 1, 1, 0, 0}.
+ *   state     x, y, phi (unwrapped) and the actual wheel speeds w_L, w_R.  Start: (x_0 + dx, y_0 + dy, phi_0 + dphi),
+ *             w_L = v_0 - omega_0 T / 2, w_R = v_0 + omega_0 T / 2.
+ *   step      r = 0 .. n + settle_rows - 1, in this order:
+ *             1. errors: (e_x, e_y) = R(-phi) (p_r - p); e_phi = wrap(phi_r - phi), wrap(a) = ((a + pi) mod 2 pi) - pi
+ *                with the floored mod (MPG:560-562); e_pos = hypot(e_x, e_y).
+ *             2. statistics: the maximum e_pos and the first row that strictly exceeds the running maximum; the maxima
+ *                of |e_y| and |e_phi|.
+ *             3. executed row r (if requested): time = r * time_step; position = the distance travelled so far (the sum
+ *                of |d| below); velocity v = (g_L w_L + g_R w_R) / 2, the actual body speed; acceleration = (v - v of
+ *                the previous row) / time_step, 0 at row 0; heading = -wrap(phi); angular velocity = -omega, omega =
+ *                (g_R w_R - g_L w_L) / (T track_scale); x; y.
+ *             4. control (RAMSETE): k = 2 zeta sqrt(omega_r^2 + b v_r^2); v_c = v_r cos e_phi + k e_x;
+ *                omega_c = omega_r + k e_phi + b v_r sinc(e_phi) e_y; c_L = v_c - omega_c T / 2, c_R = v_c + omega_c T / 2.
+ *             5. saturation: m = max(|c_L|, |c_R|); if m > wheel_speed_max both are scaled by wheel_speed_max / m (the
+ *                ratio c_L : c_R, hence the curvature, is kept) and the row counts as saturated.
+ *             6. n_substeps substeps of h = time_step / n_substeps: w += (c - w) a for each wheel, a = 1 - exp(-h / tau)
+ *                (a = 1 for tau = 0); v and omega as in 3; the exact arc: u = omega h / 2, d = v h sinc(u),
+ *                p += d (cos(phi + u), sin(phi + u)), phi += omega h.  sinc(x) = 1 - x^2 / 6 for |x| < 1e-4, else sin x / x.
+ *             After the last step: the final position error |p_(n-1) - p| and heading error |wrap(phi_(n-1) - phi)|.
+ *   outputs   any pointer may be NULL.
+ *             per rollout: d_stats [B][K][6] = {max e_pos, max |e_y|, max |e_phi|, final position error, final heading
+ *             error, 0}; d_stat_rows [B][K][2] = {row of max e_pos, saturated rows}.
+ *             per route [B]: d_worst (the largest max e_pos over k; the smallest k on a tie), d_worst_rollout and
+ *             d_worst_row (that k and its row), d_mean (the mean of max e_pos, summed in ascending k), d_n_exceeding
+ *             (rollouts whose max e_pos is above f->tolerance).
+ *             executed rows: d_exec_rows [B * K][cap_exec][8], rollout (b, k) at b * K + k, rows 0 .. n + settle_rows - 1
+ *             (the rest is left as it was); d_exec_counts [B * K][2] = {n + settle_rows, 0}, so counts_stride = 2 works in
+ *             both clearance calls.  cap_exec < capacity + settle_rows: VAP_ERR_INVALID.
+ *   edges     a route with n = 0: NaN / -1 / 0 in every output of its rollouts and of the route, executed count 0.  A
+ *             rollout whose record has a non-finite entry, a gain <= 0, track_scale <= 0 or tau < 0 is invalid: NaN / -1,
+ *             no executed rows (count 0), no part in the route's summary (a route without a valid rollout: NaN, NaN, -1,
+ *             -1, 0).
+ *   alignment d_rows, d_perturb, d_stats and d_exec_rows must be 16-byte aligned (they are read and written two doubles
+ *             at a time); hipMalloc's and torch's allocations are.  A misaligned one: VAP_ERR_INVALID.
+ * VAP_ERR_INVALID: a non-positive (or non-finite) track_width, b, zeta, wheel_speed_max or time_step; n_substeps outside
+ * 1..16; settle_rows outside 0..10000; K outside 1..4096; a null rows, counts or perturbation pointer with B > 0.  The
+ * arguments are checked before the context is touched.  B = 0 is a no-op.  Works on the context's stream and does not
+ * synchronise.  Two calls on the same inputs give the same bits: every reduction has a fixed order, no float atomics. */
+typedef struct {
+    double track_width, b, zeta, wheel_speed_max, tolerance;
+    int n_substeps, settle_rows;
+} vap_follower;
+int vap_tracking_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride,
+                          double time_step, const vap_follower *f, int K, int shared_perturb, const double *d_perturb,
+                          double *d_stats, int *d_stat_rows, double *d_worst, double *d_mean, int *d_worst_rollout,
+                          int *d_worst_row, int *d_n_exceeding, long cap_exec, double *d_exec_rows, int *d_exec_counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,7 @@ EXPORTS = (
     "vap_grid_distances", "vap_route_limits", "vap_velocity_pass_limits", "vap_time_insert_waits", "vap_fit_ex",
     "vap_profile_routes", "vap_time_profile_routes", "vap_time_insert_events", "vap_limit_rows_dtype",
     "vap_closest_points", "vap_route_closest", "vap_footprint_clearance", "vap_footprint_conflicts",
+    "vap_tracking_rollouts",
 )
 
 
@@ -70,6 +71,12 @@ class Constraints(C.Structure):
     """vap_constraints == motion_profile_generator.Constraints field order (MPG:14-21)."""
     _fields_ = [("max_vel", C.c_double), ("max_acc", C.c_double), ("max_dec", C.c_double),
                 ("friction_coef", C.c_double), ("max_jerk", C.c_double), ("track_width", C.c_double)]
+
+
+class FollowerStruct(C.Structure):
+    """vap_follower (include/vap.h)."""
+    _fields_ = [("track_width", C.c_double), ("b", C.c_double), ("zeta", C.c_double), ("wheel_speed_max", C.c_double),
+                ("tolerance", C.c_double), ("n_substeps", C.c_int), ("settle_rows", C.c_int)]
 
 
 ip = C.POINTER(C.c_int)
@@ -171,6 +178,8 @@ def lib():
                                           C.c_int, dp, C.c_double] + [vp] * 6
     side = [C.c_int, C.c_long, vp, vp, C.c_int, C.c_int, dp]
     L.vap_footprint_conflicts.argtypes = [vp, C.c_int, C.c_int, C.c_double] + side + side + [vp] * 8
+    L.vap_tracking_rollouts.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_double, C.POINTER(FollowerStruct), C.c_int,
+                                        C.c_int, vp] + [vp] * 7 + [C.c_long, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("vap_version", "vap_device_count"):

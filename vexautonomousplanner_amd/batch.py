@@ -459,5 +459,14 @@ class BatchedTrajectoryGenerator:
         return fp.conflicts(tp["rows"], tp["counts"], footprint, others["rows"], others["counts"], others_footprint,
                             ctx=self.ctx, **kw)
 
+    def tracking_rollouts(self, tp, follower, perturbations, **kw):
+        """Closed-loop tracking rollouts along the rows of ``tp`` — the dict ``time_profile`` or ``insert_waits``
+        returned — under ``perturbations`` (vap_tracking_rollouts on this generator's context and torch's current stream;
+        see tracking.rollouts for time_step, executed, out and the returned dict).  ``follower``: a tracking.Follower."""
+        from . import tracking
+        if tp["rows"].device != self.device:
+            raise ValueError(f"rows must be on {self.device}")
+        return tracking.rollouts(tp["rows"], tp["counts"], follower, perturbations, ctx=self.ctx, **kw)
+
     def timing(self):
         return self.ctx.last_timing()

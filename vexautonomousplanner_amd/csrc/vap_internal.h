@@ -68,6 +68,8 @@ struct vap_ctx {
     hipEvent_t scene_ev = nullptr;
     // vap_footprint_conflicts: packed poses and per-64-row bounding circles of either side, per-tile partial results
     VapBuffer conf_pack_a, conf_pack_o, conf_blk_a, conf_blk_o, conf_part;
+    // vap_tracking_rollouts with more than 256 rollouts per route: per-rollout (max e_pos, row) for the reduce kernel
+    VapBuffer track_part;
 
     int ensure(VapBuffer &b, size_t bytes)
     {

@@ -1,0 +1,419 @@
+// vap_tracking.hip — closed-loop tracking rollouts of time-domain rows (vap_tracking_rollouts).
+//
+// The clearance calls judge the nominal rows vap_time_profile writes; the robot drives what a path follower makes of
+// them.  This file rolls a differential-drive robot with a RAMSETE follower along every route of a batch, K times per
+// route under K perturbation records, and reports how far it strays (and, on request, the executed rows in the
+// time-profile layout).  Definitions: include/vap.h.
+//
+// One kernel, a lane per rollout:
+//   layout   K <= 256: a workgroup takes R = 256 / K whole routes (thread = route-in-group * K + k; the last
+//            256 - R * K threads idle); K > 256: a route takes ceil(K / 256) workgroups.  A workgroup's lanes therefore
+//            never straddle a route boundary other than at a multiple of K.
+//   staging  every rollout of a route reads the same five columns {v, heading, angular_vel, x, y} of the same row at
+//            the same step, so the workgroup stages its routes' rows in LDS, 40 B per row, in tiles of kTrackRows / R rows
+//            (at most 64): the next tile's loads are issued before the current tile is marched and land in the other LDS
+//            buffer after it, one barrier per tile.  The settle rows (r >= n) are made by the loader (the last pose,
+//            v = omega = 0), so the march never looks at counts.  Staged as [row][column][route]: lanes of one route
+//            read one address (a broadcast), lanes of different routes consecutive ones.
+//   march    the header's steps 1-6 per row in fp64; the per-rollout constants (gains, T * track_scale,
+//            a = 1 - exp(-h / tau)) are computed once before the loop.  Executed rows go out as four 16-byte stores per
+//            lane and step.
+//   summary  K <= 256: the first lane of each route walks its K rollouts in LDS in ascending k (a fixed order: the
+//            worst keeps the smallest k on a tie, the mean is one running sum).  K > 256: the rollouts' (max e_pos,
+//            row) go to context scratch and k_tracking_reduce walks them the same way, a lane per route.  No float
+//            atomics anywhere, so two calls give the same bits.
+#include <climits>
+#include <cmath>
+#include <cstdint>
+
+#include "vap_internal.h"
+
+namespace vap {
+
+constexpr int kTrackThreads = 256;
+constexpr int kTrackRows = 512;        // staged rows per LDS buffer, over all routes of the workgroup
+constexpr int kTrackTileMax = 64;      // rows of one route per tile, at most
+constexpr double kPi = 3.14159265358979323846;
+
+struct TrackArgs {
+    const double *rows;       // [B][cap][8]
+    const int *counts;
+    long cap;
+    int stride, B, K, shared;
+    const double *perturb;    // [B][K][8] or [K][8]
+    double T, b, two_zeta, wmax, tol, dt, h;
+    int nsub, settle;
+    double *stats;            // [B][K][6]
+    int *stat_rows;           // [B][K][2]
+    double *worst, *mean;     // [B]
+    int *worst_rollout, *worst_row, *n_exceeding;
+    long cap_exec;
+    double *exec_rows;        // [B*K][cap_exec][8]
+    int *exec_counts;         // [B*K][2]
+    double *part_e;           // K > 256: [B][K] max e_pos (row < 0: takes no part)
+    int *part_row;
+    int R, tile, wpr;         // routes per workgroup, rows per tile, workgroups per route
+};
+
+// ((a + pi) mod 2 pi) - pi with the floored mod (MPG:560-562); fmod is exact
+__device__ __forceinline__ double track_wrap(double a)
+{
+    double m = fmod(a + kPi, 2.0 * kPi);
+    if (m < 0.0) m += 2.0 * kPi;
+    return m - kPi;
+}
+
+__device__ __forceinline__ double track_sinc(double x, double sin_x)
+{
+    return fabs(x) < 1e-4 ? 1.0 - x * x / 6.0 : sin_x / x;
+}
+
+// a route's rollouts in ascending k: worst (a strictly larger error replaces: the smallest k stays), running sum, count
+// above the tolerance
+struct TrackSummary {
+    double worst = -INFINITY, sum = 0.0;
+    int k = -1, row = -1, cnt = 0, nex = 0;
+    __device__ void take(double e, int r, int kk, double tol)
+    {
+        if (r < 0) return;
+        if (e > worst) { worst = e; k = kk; row = r; }
+        sum += e;
+        cnt++;
+        nex += e > tol ? 1 : 0;
+    }
+    __device__ void store(const TrackArgs &g, int b) const
+    {
+        if (g.worst) g.worst[b] = cnt ? worst : NAN;
+        if (g.mean) g.mean[b] = cnt ? sum / (double)cnt : NAN;
+        if (g.worst_rollout) g.worst_rollout[b] = k;
+        if (g.worst_row) g.worst_row[b] = row;
+        if (g.n_exceeding) g.n_exceeding[b] = nex;
+    }
+};
+
+template <bool EXEC>
+__global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g)
+{
+    __shared__ __attribute__((aligned(16))) double stage[2][kTrackRows * 5];
+    __shared__ int s_n[kTrackThreads];
+    __shared__ int s_total;
+    const int tid = threadIdx.x;
+    const int R = g.R, tile = g.tile;
+    // which rollout this lane walks
+    const int b0 = g.wpr > 1 ? (int)(blockIdx.x / g.wpr) : (int)blockIdx.x * R;
+    const int lr = g.wpr > 1 ? 0 : tid / g.K;                                  // route within the workgroup
+    const int k = g.wpr > 1 ? (int)(blockIdx.x % g.wpr) * kTrackThreads + tid : tid % g.K;
+    const int b = b0 + lr;
+    const bool inside = lr < R && b < g.B && k < g.K;
+    if (tid == 0) s_total = 0;
+    if (tid < R) {
+        int n = 0;
+        if (b0 + tid < g.B) {
+            const long c = g.counts[(size_t)(b0 + tid) * g.stride];
+            n = (int)(c < 0 ? 0 : (c > g.cap ? g.cap : c));
+        }
+        s_n[tid] = n;
+    }
+    __syncthreads();
+    if (tid < R && s_n[tid] > 0) atomicMax(&s_total, s_n[tid] + g.settle);
+    __syncthreads();
+    const int wg_total = s_total;                     // steps of the longest route of the workgroup
+    const int n = lr < R ? s_n[lr] : 0;
+    const size_t gi = (size_t)b * g.K + k;            // flattened (b, k)
+
+    // the rollout's constants and start state
+    double gl = 1.0, gr = 1.0, tts = 1.0, a = 1.0;
+    double x = 0.0, y = 0.0, phi = 0.0, wl = 0.0, wr = 0.0;
+    bool valid = false;
+    if (inside && n > 0) {
+        const double *p = g.perturb + (g.shared ? (size_t)k : gi) * 8;
+        const double2 p01 = *(const double2 *)p, p23 = *(const double2 *)(p + 2), p45 = *(const double2 *)(p + 4),
+                      p67 = *(const double2 *)(p + 6);
+        const double tau = p67.x;
+        valid = isfinite(p01.x) && isfinite(p01.y) && isfinite(p23.x) && isfinite(p23.y) && isfinite(p45.x) &&
+                isfinite(p45.y) && isfinite(p67.x) && isfinite(p67.y) && p23.y > 0.0 && p45.x > 0.0 && p45.y > 0.0 && tau >= 0.0;
+        if (valid) {
+            const double *row0 = g.rows + (size_t)b * (size_t)g.cap * 8;
+            const double v0 = row0[2], w0 = -row0[5];
+            x = row0[6] + p01.x;
+            y = row0[7] + p01.y;
+            phi = -row0[4] + p23.x;
+            wl = v0 - w0 * g.T / 2.0;
+            wr = v0 + w0 * g.T / 2.0;
+            gl = p23.y;
+            gr = p45.x;
+            tts = g.T * p45.y;
+            a = tau == 0.0 ? 1.0 : 1.0 - exp(-g.h / tau);
+        }
+    }
+    const int my_total = valid ? n + g.settle : 0;
+    double maxe = -INFINITY, maxey = -INFINITY, maxeph = -INFINITY, dist = 0.0, vprev = 0.0;
+    int mrow = -1, nsat = 0;
+    double *erow = EXEC && valid ? g.exec_rows + gi * (size_t)g.cap_exec * 8 : nullptr;
+
+    // the loader: item j < R * tile is row j % tile of route j / tile of the tile (consecutive threads on consecutive
+    // rows of a route); at most two items per thread
+    const int items = R * tile;
+    double lv[2], lh[2], lw[2], lx[2], ly[2];
+    auto load = [&](int ti) {
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const int j = tid + i * kTrackThreads;
+            lv[i] = lh[i] = lw[i] = lx[i] = ly[i] = 0.0;
+            if (j < items) {
+                const int route = j / tile, r = ti * tile + j % tile, nr = s_n[route];
+                if (nr > 0 && r < nr + g.settle) {
+                    const int src = r < nr ? r : nr - 1;
+                    const double *q = g.rows + ((size_t)(b0 + route) * (size_t)g.cap + (size_t)src) * 8;
+                    const double2 hw = *(const double2 *)(q + 4), xy = *(const double2 *)(q + 6);
+                    lv[i] = r < nr ? q[2] : 0.0;
+                    lh[i] = hw.x;
+                    lw[i] = r < nr ? hw.y : 0.0;
+                    lx[i] = xy.x;
+                    ly[i] = xy.y;
+                }
+            }
+        }
+    };
+    auto store = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const int j = tid + i * kTrackThreads;
+            if (j < items) {
+                double *d = stage[buf] + (size_t)(j % tile) * 5 * R + j / tile;
+                d[0] = lv[i];
+                d[R] = lh[i];
+                d[2 * R] = lw[i];
+                d[3 * R] = lx[i];
+                d[4 * R] = ly[i];
+            }
+        }
+    };
+
+    const int ntiles = (wg_total + tile - 1) / tile;
+    if (ntiles > 0) {
+        load(0);
+        store(0);
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int ti = 0; ti < ntiles; ti++) {
+        const bool more = ti + 1 < ntiles;
+        if (more) load(ti + 1);                        // in flight while this tile is marched
+        const double *cur = stage[ti & 1] + (lr < R ? lr : 0);
+        const int r0 = ti * tile;
+        const int rend = min(tile, wg_total - r0);
+#pragma unroll 1
+        for (int t = 0; t < rend; t++) {
+            const int r = r0 + t;
+            if (r >= my_total) continue;
+            const double *q = cur + (size_t)t * 5 * R;
+            const double vr = q[0], phr = -q[R], wref = -q[2 * R], xr = q[3 * R], yr = q[4 * R];
+            // 1. errors in the body frame
+            double sp, cp;
+            sincos(phi, &sp, &cp);
+            const double dx = xr - x, dy = yr - y;
+            const double ex = cp * dx + sp * dy, ey = cp * dy - sp * dx;
+            const double eph = track_wrap(phr - phi);
+            const double epos = hypot(ex, ey);
+            // 2. statistics
+            if (epos > maxe) { maxe = epos; mrow = r; }
+            if (fabs(ey) > maxey) maxey = fabs(ey);
+            if (fabs(eph) > maxeph) maxeph = fabs(eph);
+            // 3. the executed row
+            if (EXEC) {
+                const double v = (gl * wl + gr * wr) / 2.0;
+                const double om = (gr * wr - gl * wl) / tts;
+                double2 *o = (double2 *)(erow + (size_t)r * 8);
+                o[0] = make_double2((double)r * g.dt, dist);
+                o[1] = make_double2(v, r > 0 ? (v - vprev) / g.dt : 0.0);
+                o[2] = make_double2(-track_wrap(phi), -om);
+                o[3] = make_double2(x, y);
+                vprev = v;
+            }
+            // 4. RAMSETE
+            double se, ce;
+            sincos(eph, &se, &ce);
+            const double kk = g.two_zeta * sqrt(wref * wref + g.b * vr * vr);
+            const double vc = vr * ce + kk * ex;
+            const double wc = wref + kk * eph + g.b * vr * track_sinc(eph, se) * ey;
+            double cl = vc - wc * g.T / 2.0, cr = vc + wc * g.T / 2.0;
+            // 5. saturation, keeping c_L : c_R
+            const double mx = fmax(fabs(cl), fabs(cr));
+            if (mx > g.wmax) {
+                const double scale = g.wmax / mx;
+                cl *= scale;
+                cr *= scale;
+                nsat++;
+            }
+            // 6. substeps: first-order wheel lag, then the exact arc
+#pragma unroll 1
+            for (int s = 0; s < g.nsub; s++) {
+                wl += (cl - wl) * a;
+                wr += (cr - wr) * a;
+                const double v = (gl * wl + gr * wr) / 2.0;
+                const double om = (gr * wr - gl * wl) / tts;
+                const double u = om * g.h / 2.0;
+                double sa, ca;
+                sincos(phi + u, &sa, &ca);
+                const double d = v * g.h * track_sinc(u, sin(u));
+                x += d * ca;
+                y += d * sa;
+                phi += om * g.h;
+                dist += fabs(d);
+            }
+        }
+        if (more) store((ti + 1) & 1);
+        __syncthreads();
+    }
+
+    // 7. final errors against row n - 1, and the rollout's outputs
+    const bool have = mrow >= 0;
+    if (inside) {
+        double fpos = NAN, fphi = NAN;
+        if (have) {
+            const double *ql = g.rows + ((size_t)b * (size_t)g.cap + (size_t)(n - 1)) * 8;
+            fpos = hypot(ql[6] - x, ql[7] - y);
+            fphi = fabs(track_wrap(-ql[4] - phi));
+        }
+        if (g.stats) {
+            double2 *o = (double2 *)(g.stats + gi * 6);
+            o[0] = make_double2(have ? maxe : NAN, have ? maxey : NAN);
+            o[1] = make_double2(have ? maxeph : NAN, fpos);
+            o[2] = make_double2(fphi, have ? 0.0 : NAN);
+        }
+        if (g.stat_rows) {
+            g.stat_rows[gi * 2] = mrow;
+            g.stat_rows[gi * 2 + 1] = have ? nsat : -1;
+        }
+        if (g.exec_counts) {
+            g.exec_counts[gi * 2] = my_total;
+            g.exec_counts[gi * 2 + 1] = 0;
+        }
+        if (g.part_e) {
+            g.part_e[gi] = maxe;
+            g.part_row[gi] = mrow;
+        }
+    }
+    if (g.wpr > 1) return;                              // the route's summary: k_tracking_reduce
+    // the route's summary inside the workgroup: the stage buffers are free (the last barrier is behind every thread)
+    double *s_e = stage[0];
+    int *s_r = s_n;
+    __syncthreads();                                    // s_n was read above
+    s_e[tid] = maxe;
+    s_r[tid] = inside ? mrow : -1;
+    __syncthreads();
+    if (inside && k == 0) {
+        TrackSummary sum;
+#pragma unroll 1
+        for (int kk = 0; kk < g.K; kk++) sum.take(s_e[tid + kk], s_r[tid + kk], kk, g.tol);
+        sum.store(g, b);
+    }
+}
+
+// K > 256: per route, its rollouts' partials in ascending k
+__global__ __launch_bounds__(64) void k_tracking_reduce(TrackArgs g)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= g.B) return;
+    TrackSummary sum;
+#pragma unroll 1
+    for (int kk = 0; kk < g.K; kk++) {
+        const size_t p = (size_t)b * g.K + kk;
+        sum.take(g.part_e[p], g.part_row[p], kk, g.tol);
+    }
+    sum.store(g, b);
+}
+
+}  // namespace vap
+
+extern "C" {
+
+int vap_tracking_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride,
+                          double time_step, const vap_follower *f, int K, int shared_perturb, const double *d_perturb,
+                          double *d_stats, int *d_stat_rows, double *d_worst, double *d_mean, int *d_worst_rollout,
+                          int *d_worst_row, int *d_n_exceeding, long cap_exec, double *d_exec_rows, int *d_exec_counts)
+{
+    using namespace vap;
+    // host validation first: it needs no device
+    if (!f) return vap_fail(VAP_ERR_INVALID, "null follower");
+    if (!(f->track_width > 0.0) || !(f->b > 0.0) || !(f->zeta > 0.0) || !(f->wheel_speed_max > 0.0) ||
+        !std::isfinite(f->track_width) || !std::isfinite(f->b) || !std::isfinite(f->zeta) || !std::isfinite(f->wheel_speed_max))
+        return vap_fail(VAP_ERR_INVALID, "follower: track_width, b, zeta and wheel_speed_max must be positive and finite (got %g, %g, %g, %g)",
+                        f->track_width, f->b, f->zeta, f->wheel_speed_max);
+    if (std::isnan(f->tolerance)) return vap_fail(VAP_ERR_INVALID, "follower: tolerance is NaN");
+    if (!(time_step > 0.0) || !std::isfinite(time_step)) return vap_fail(VAP_ERR_INVALID, "time_step must be positive and finite (got %g)", time_step);
+    if (f->n_substeps < 1 || f->n_substeps > 16) return vap_fail(VAP_ERR_INVALID, "follower: n_substeps %d outside 1..16", f->n_substeps);
+    if (f->settle_rows < 0 || f->settle_rows > 10000) return vap_fail(VAP_ERR_INVALID, "follower: settle_rows %d outside 0..10000", f->settle_rows);
+    if (K < 1 || K > 4096) return vap_fail(VAP_ERR_INVALID, "K = %d rollouts per route outside 1..4096", K);
+    if (B < 0 || capacity < 0) return vap_fail(VAP_ERR_INVALID, "bad shape B=%d capacity=%ld", B, capacity);
+    if (counts_stride < 1) return vap_fail(VAP_ERR_INVALID, "counts_stride must be >= 1 (got %d)", counts_stride);
+    if (B > 0 && (!d_counts || (capacity > 0 && !d_rows))) return vap_fail(VAP_ERR_INVALID, "null rows / counts");
+    if (B > 0 && !d_perturb) return vap_fail(VAP_ERR_INVALID, "null perturbation records");
+    if (capacity + f->settle_rows > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "capacity %ld + settle rows above %d", capacity, INT_MAX);
+    if (d_exec_rows && cap_exec < capacity + f->settle_rows)
+        return vap_fail(VAP_ERR_INVALID, "cap_exec %ld below capacity + settle_rows = %ld", cap_exec, capacity + f->settle_rows);
+    if ((((uintptr_t)d_rows | (uintptr_t)d_perturb | (uintptr_t)d_stats | (uintptr_t)d_exec_rows) & 15) != 0)
+        return vap_fail(VAP_ERR_INVALID, "rows, perturbation records, stats and executed rows must be 16-byte aligned");
+    VAP_TRY(vap_set_device(ctx));
+    if (B == 0) return VAP_OK;
+
+    TrackArgs g{};
+    g.rows = d_rows;
+    g.counts = d_counts;
+    g.cap = capacity;
+    g.stride = counts_stride;
+    g.B = B;
+    g.K = K;
+    g.shared = shared_perturb != 0;
+    g.perturb = d_perturb;
+    g.T = f->track_width;
+    g.b = f->b;
+    g.two_zeta = 2.0 * f->zeta;
+    g.wmax = f->wheel_speed_max;
+    g.tol = f->tolerance;
+    g.dt = time_step;
+    g.h = time_step / (double)f->n_substeps;
+    g.nsub = f->n_substeps;
+    g.settle = f->settle_rows;
+    g.stats = d_stats;
+    g.stat_rows = d_stat_rows;
+    g.worst = d_worst;
+    g.mean = d_mean;
+    g.worst_rollout = d_worst_rollout;
+    g.worst_row = d_worst_row;
+    g.n_exceeding = d_n_exceeding;
+    g.cap_exec = cap_exec;
+    g.exec_rows = d_exec_rows;
+    g.exec_counts = d_exec_counts;
+    const bool summary = d_worst || d_mean || d_worst_rollout || d_worst_row || d_n_exceeding;
+    long grid;
+    if (K <= kTrackThreads) {
+        g.R = kTrackThreads / K;
+        g.wpr = 1;
+        grid = ((long)B + g.R - 1) / g.R;
+    } else {
+        g.R = 1;
+        g.wpr = (K + kTrackThreads - 1) / kTrackThreads;
+        grid = (long)B * g.wpr;
+        if (summary) {
+            const size_t np = (size_t)B * (size_t)K;
+            VAP_TRY(ctx->ensure(ctx->track_part, np * (sizeof(double) + sizeof(int))));
+            g.part_e = (double *)ctx->track_part.ptr;
+            g.part_row = (int *)(g.part_e + np);
+        }
+    }
+    if (grid > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "%d routes x %d rollouts: too many workgroups for one launch", B, K);
+    g.tile = kTrackRows / g.R < kTrackTileMax ? kTrackRows / g.R : kTrackTileMax;
+
+    if (d_exec_rows)
+        hipLaunchKernelGGL(k_tracking_rollouts<true>, dim3((unsigned)grid), dim3(kTrackThreads), 0, ctx->stream, g);
+    else
+        hipLaunchKernelGGL(k_tracking_rollouts<false>, dim3((unsigned)grid), dim3(kTrackThreads), 0, ctx->stream, g);
+    if (g.wpr > 1 && summary)
+        hipLaunchKernelGGL(k_tracking_reduce, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, g);
+    HIP_TRY(hipGetLastError());
+    return VAP_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,183 @@
+"""Closed-loop tracking rollouts of time-domain rows (vap_tracking_rollouts, include/vap.h).
+
+The clearance checks of ``footprint`` judge the nominal rows ``time_profile`` / ``insert_waits`` write.  The robot does
+not drive those rows: it feeds them to a path follower.  This module rolls a differential-drive robot with a RAMSETE
+follower along every route of a batch, K times per route under K perturbation records (a start offset, a gain per wheel,
+a track-width factor, a drive lag), on the device, and returns how far it strays — the margin the clearance calls need —
+and, with ``executed=True``, the executed rows in the time-profile layout, which ``footprint.clearance`` and
+``footprint.conflicts`` accept unchanged.
+
+The model, step by step, is the header's: reference pose (x, y) = columns 6, 7, phi = -heading, v = column 2,
+omega = -angular velocity; errors in the body frame; RAMSETE; wheel-speed saturation that keeps the curvature; a
+first-order wheel lag and the exact arc per substep.  Units: feet, seconds, radians.
+"""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_ROLLOUTS = 4096
+NOMINAL = (0.0, 0.0, 0.0, 1.0, 1.0, 1.0, 0.0, 0.0)      # dx, dy, dphi, gain_left, gain_right, track_scale, tau, reserved
+
+
+@dataclass
+class Follower:
+    """vap_follower: the robot's track width (ft), the RAMSETE gains b (1/ft^2) and zeta, the wheel speed limit (ft/s),
+    the position error (ft) above which a rollout counts in ``n_exceeding``, the integration substeps per row and the
+    rows the robot is given to settle on the last pose."""
+    track_width: float = 1.0
+    b: float = 2.0
+    zeta: float = 0.7
+    wheel_speed_max: float = 6.0
+    tolerance: float = 0.25
+    n_substeps: int = 2
+    settle_rows: int = 50
+
+    def validate(self):
+        for name in ("track_width", "b", "zeta", "wheel_speed_max"):
+            v = float(getattr(self, name))
+            if not (v > 0 and np.isfinite(v)):
+                raise ValueError(f"Follower.{name} must be positive and finite (got {v!r})")
+        if np.isnan(float(self.tolerance)):
+            raise ValueError("Follower.tolerance is NaN")
+        if int(self.n_substeps) != self.n_substeps or not 1 <= int(self.n_substeps) <= 16:
+            raise ValueError(f"Follower.n_substeps must be 1..16 (got {self.n_substeps!r})")
+        if int(self.settle_rows) != self.settle_rows or not 0 <= int(self.settle_rows) <= 10000:
+            raise ValueError(f"Follower.settle_rows must be 0..10000 (got {self.settle_rows!r})")
+        return self
+
+    def as_struct(self):
+        return _lib.FollowerStruct(float(self.track_width), float(self.b), float(self.zeta), float(self.wheel_speed_max),
+                                   float(self.tolerance), int(self.n_substeps), int(self.settle_rows))
+
+
+def sample_perturbations(B, K, pos_sigma=0.1, heading_sigma=0.05, gain_sigma=0.03, track_sigma=0.05, tau=0.05, seed=0,
+                         nominal_first=True):
+    """(B, K, 8) fp64 perturbation records drawn on the host with ``np.random.default_rng(seed)``: dx, dy ~ N(0,
+    pos_sigma) ft, dphi ~ N(0, heading_sigma) rad, the wheel gains ~ 1 + N(0, gain_sigma), track_scale ~ 1 + N(0,
+    track_sigma) (the three clipped to >= 0.5), the drive lag ``tau`` seconds for every record.  With ``nominal_first``
+    rollout k = 0 of every route is the undisturbed record {0, 0, 0, 1, 1, 1, 0, 0}.  The same arguments give the same
+    array."""
+    B, K = int(B), int(K)
+    if B < 0 or not 1 <= K <= MAX_ROLLOUTS:
+        raise ValueError(f"B must be >= 0 and K in 1..{MAX_ROLLOUTS} (got {B}, {K})")
+    for name, v in (("pos_sigma", pos_sigma), ("heading_sigma", heading_sigma), ("gain_sigma", gain_sigma),
+                    ("track_sigma", track_sigma), ("tau", tau)):
+        if not (float(v) >= 0 and np.isfinite(float(v))):
+            raise ValueError(f"{name} must be >= 0 and finite (got {v!r})")
+    rng = np.random.default_rng(seed)
+    z = rng.standard_normal((B, K, 6))
+    p = np.zeros((B, K, 8), dtype=np.float64)
+    p[..., 0:2] = z[..., 0:2] * float(pos_sigma)
+    p[..., 2] = z[..., 2] * float(heading_sigma)
+    p[..., 3:5] = np.maximum(1.0 + z[..., 3:5] * float(gain_sigma), 0.5)
+    p[..., 5] = np.maximum(1.0 + z[..., 5] * float(track_sigma), 0.5)
+    p[..., 6] = float(tau)
+    if nominal_first:
+        p[:, 0] = NOMINAL
+    return p
+
+
+STAT_COLUMNS = ("max_error", "max_cross_track", "max_heading_error", "final_error", "final_heading_error")
+
+
+def rollouts(rows, counts, follower, perturbations, time_step=0.01, executed=False, out=None, device=0, ctx=None):
+    """Tracking rollouts of a batch of time-domain rows (vap_tracking_rollouts).
+
+      rows           (B, capacity, 8) fp64 rows of time_profile / insert_waits — a device tensor (used in place) or a
+                     host array (uploaded once); (n, 8) for a single trajectory
+      counts         (B, k) int counts of that call (column 0 = rows), or (B,); None for a single trajectory
+      follower       a Follower
+      perturbations  (B, K, 8) records per route, or (K, 8) shared by every route (``sample_perturbations``); a device
+                     tensor or a host array
+      time_step      the rows' time step in seconds (time_profile's dt)
+      executed       also return the executed rows: ``rows`` (B * K, capacity + settle_rows, 8) and ``counts``
+                     (B * K, 2), rollout (b, k) at b * K + k — the dict can be passed to footprint.clearance /
+                     footprint.conflicts (and the generator's footprint_clearance) as it is.  Rows past a rollout's
+                     count are not written
+      out            optional dict that keeps the call's buffers (stats, stat_rows, the per-route outputs, rows, counts, in
+                     their batch shapes) between calls: a missing or mis-shaped entry is allocated into it, nothing else
+                     in it is touched, and a later call with the same shapes allocates nothing
+    Returns a dict of tensors: stats (B, K, 6) and its columns as views max_error, max_cross_track, max_heading_error,
+    final_error, final_heading_error (B, K); stat_rows (B, K, 2) with views max_row and saturated_rows; per route (B,)
+    worst, mean, worst_rollout, worst_row, n_exceeding.  A route without rows and an invalid record give NaN / -1 / 0.
+    A single trajectory gives (K, ...) and 0-d tensors.  Work runs on torch's current stream and is not synchronised."""
+    if not isinstance(follower, Follower):
+        raise TypeError("follower must be a tracking.Follower")
+    follower.validate()
+    time_step = float(time_step)
+    if not (time_step > 0 and np.isfinite(time_step)):
+        raise ValueError(f"time_step must be positive and finite (got {time_step!r})")
+    if isinstance(rows, torch.Tensor):
+        dev = rows.device
+        if dev.type != "cuda" or rows.dtype != torch.float64:
+            raise ValueError("rows must be an fp64 tensor on a HIP device (or a host array)")
+    else:
+        dev = torch.device("cuda", device)
+        rows = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.float64), device=dev)
+    single = rows.dim() == 2
+    if single:
+        rows = rows.unsqueeze(0)
+    if rows.dim() != 3 or rows.shape[2] != 8:
+        raise ValueError(f"rows must be (B, capacity, 8) or (n, 8), got {tuple(rows.shape)}")
+    rows = rows.contiguous()
+    B, cap = int(rows.shape[0]), int(rows.shape[1])
+    if counts is None:
+        if not single:
+            raise ValueError("counts is needed for a batch of rows")
+        counts = torch.full((1, 1), cap, dtype=torch.int32, device=dev)
+    elif isinstance(counts, torch.Tensor):
+        counts = counts.to(device=dev, dtype=torch.int32)
+    else:
+        counts = torch.as_tensor(np.asarray(counts, dtype=np.int32), device=dev)
+    if counts.dim() < 2:
+        counts = counts.reshape(B, 1)
+    if counts.dim() != 2 or counts.shape[0] != B:
+        raise ValueError(f"counts must be ({B}, k) or ({B},), got {tuple(counts.shape)}")
+    counts = counts.contiguous()
+    if isinstance(perturbations, torch.Tensor):
+        pert = perturbations.to(device=dev, dtype=torch.float64)
+    else:
+        pert = torch.as_tensor(np.ascontiguousarray(perturbations, dtype=np.float64), device=dev)
+    shared = pert.dim() == 2
+    if pert.dim() not in (2, 3) or pert.shape[-1] != 8 or (not shared and pert.shape[0] != B):
+        raise ValueError(f"perturbations must be ({B}, K, 8) or (K, 8), got {tuple(pert.shape)}")
+    pert = pert.contiguous()
+    K = int(pert.shape[-2])
+    if not 1 <= K <= MAX_ROLLOUTS:
+        raise ValueError(f"K = {K} rollouts per route (1..{MAX_ROLLOUTS})")
+    cap_exec = cap + int(follower.settle_rows)
+    bufs = {} if out is None else out      # the call's buffers; the returned dict is built apart from it
+    shapes = {"stats": ((B, K, 6), torch.float64), "stat_rows": ((B, K, 2), torch.int32), "worst": ((B,), torch.float64),
+              "mean": ((B,), torch.float64), "worst_rollout": ((B,), torch.int32), "worst_row": ((B,), torch.int32),
+              "n_exceeding": ((B,), torch.int32)}
+    if executed:
+        shapes["rows"] = ((B * K, cap_exec, 8), torch.float64)
+        shapes["counts"] = ((B * K, 2), torch.int32)
+    for k, (shp, dt) in shapes.items():
+        t = bufs.get(k)
+        if t is None or tuple(t.shape) != shp or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            bufs[k] = torch.empty(shp, dtype=dt, device=dev)
+    res = {k: bufs[k] for k in shapes}
+    if ctx is None:
+        ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    fs = follower.as_struct()
+    _lib.check(ctx._L.vap_tracking_rollouts(
+        ctx.handle, B, cap, ptr(rows), ptr(counts), int(counts.shape[1]), time_step, C.byref(fs), K, int(shared), ptr(pert),
+        ptr(res["stats"]), ptr(res["stat_rows"]), ptr(res["worst"]), ptr(res["mean"]), ptr(res["worst_rollout"]),
+        ptr(res["worst_row"]), ptr(res["n_exceeding"]), cap_exec, ptr(res.get("rows") if executed else None),
+        ptr(res.get("counts") if executed else None)), "vap_tracking_rollouts")
+    for i, name in enumerate(STAT_COLUMNS):
+        res[name] = res["stats"][..., i]
+    res["max_row"] = res["stat_rows"][..., 0]
+    res["saturated_rows"] = res["stat_rows"][..., 1]
+    if single:
+        for k in list(res):
+            if k not in ("rows", "counts"):
+                res[k] = res[k][0]
+    return res
