@@ -621,6 +621,67 @@ int vap_tracking_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_ro
                           double *d_stats, int *d_stat_rows, double *d_worst, double *d_mean, int *d_worst_rollout,
                           int *d_worst_row, int *d_n_exceeding, long cap_exec, double *d_exec_rows, int *d_exec_counts);
 
+/* ---- cross-entropy route search over batches of candidate trajectories --------------------------------------------
+ * The calls above judge candidate routes; these two make the candidates and act on the verdicts, so that a search
+ *   sample -> vap_profile_batch -> vap_time_profile -> vap_footprint_clearance [-> conflicts, rollouts] -> update
+ * runs on the device with no result read on the host.  R routes ("problems") are refined at a time, N candidates each;
+ * candidate (r, n) is route r * N + n of the batch B = R * N the evaluation calls see.  Plain-node paths only.
+ *
+ * vap_search_sample writes d_waypoints [R * N][W][2] in dt (the input of vap_profile_batch) from d_mean and d_sigma
+ * [R][W][2] fp64:
+ *   candidate 0   the best route so far, d_best_waypoints [R][W][2] in dt, where d_best_cost[r] is finite (both pointers
+ *                 non-NULL); otherwise the mean rounded to dt.
+ *   candidate n   coordinate = mean + sigma * z in fp64 (a product, a sum), rounded once to dt; where sigma == 0 the
+ *                 coordinate is the mean itself (pinned).  (z_x, z_y) of waypoint w come from one Philox4x32-10 block with
+ *                 counter (n, w, iteration, first_problem + r) and key (seed & 0xffffffff, seed >> 32): u1 = (x0 + 0.5) *
+ *                 2^-32, u2 = (x1 + 0.5) * 2^-32, rho = sqrt(-2 ln u1), z_x = rho cos(2 pi u2), z_y = rho sin(2 pi u2), with
+ *                 2 pi = 6.283185307179586; x2 and x3 are unused.  A candidate depends on (seed, iteration, first_problem
+ *                 + r, n, w) only, not on R, N or the launch.
+ * VAP_ERR_INVALID: N outside 1..4096, W < 2, a null mean, sigma or output, a misaligned pointer (mean, sigma: 16 bytes;
+ * waypoints: a pair of dt); VAP_ERR_UNSUPPORTED: W above 2048 or R * N above INT_MAX.
+ *
+ * vap_search_update scores the N candidates of each problem, ranks them, refits mean and sigma to the elites and keeps
+ * the best route so far.  One workgroup per problem; every sum has a fixed order and there are no float atomics, so two
+ * calls on the same inputs give the same bits.
+ *   terms      per candidate [B], any pointer may be NULL: d_counts with counts_stride (the count c of vap_time_profile;
+ *              duration = c * time_step), d_meta [B][4] (length = meta[b][1]), d_flags, d_clearance (the route's minimum of
+ *              vap_footprint_clearance), d_conflict_clearance (of vap_footprint_conflicts), d_tracking_worst (d_worst of
+ *              vap_tracking_rollouts).
+ *   cost       violation = max(0, clearance_margin - clearance) + max(0, conflict_margin - conflict) + max(0, tracking_worst
+ *              - tracking_tolerance) over the terms given, summed in this order from 0;
+ *              cost = w_time * duration + w_length * length; if violation > 0: cost = cost + (infeasible_base +
+ *              w_violation * violation).  cost = +inf if flags != 0, c <= 0, the length or one of the three terms is NaN
+ *              (the violation is then NaN) or the sum is NaN.  So a feasible candidate beats every infeasible one, and
+ *              among infeasible ones the smaller violation wins.
+ *   rank       d_order [R][N]: the problem's candidate indices by (cost, index) ascending; d_cost, d_violation [B];
+ *              d_n_feasible [R]: candidates with a finite cost and violation == 0.
+ *   refit      (d_mean != NULL; d_sigma then too) the elites are the first min(E, finite-cost candidates) of the order.
+ *              Per coordinate j with sigma > 0: m = (sum of the elites' values in rank order, as stored in dt and widened
+ *              to fp64) / count; var = (sum of (value - m)^2 in rank order) / count; mean = (1 - alpha) * mean + alpha * m;
+ *              sigma = min(max(sqrt((1 - alpha) * (sigma * sigma) + alpha * var), sigma_min), sigma_max).  A coordinate
+ *              with sigma == 0 is pinned: its mean and sigma keep their bits.  Without a finite-cost candidate nothing
+ *              changes.  With d_mean == NULL the call only scores and ranks.
+ *   best       (d_best_cost != NULL, in/out [R], +inf before the first call) if the first candidate of the order has a
+ *              finite cost strictly below d_best_cost[r]: d_best_cost[r] = it, d_best_waypoints [R][W][2] (dt) = its
+ *              waypoints, d_best_terms [R][4] = {duration, length, violation, candidate index}.  d_history
+ *              [R][history_stride] receives d_best_cost[r] after this step at column iteration.
+ * VAP_ERR_INVALID: N, W as above; E outside 1..N, alpha outside [0, 1], sigma_min < 0 or above sigma_max (with d_mean); a
+ * negative or non-finite weight, a non-finite margin or tolerance; counts without a positive time_step; best waypoints,
+ * terms or history without d_best_cost; iteration >= history_stride.  R = 0 is a no-op.  Both calls work on the context's
+ * stream and do not synchronise. */
+typedef struct {
+    double w_time, w_length, w_violation, infeasible_base, clearance_margin, conflict_margin, tracking_tolerance;
+} vap_search_weights;
+int vap_search_sample(vap_ctx *ctx, int dt, int R, int N, int W, const double *d_mean, const double *d_sigma,
+                      const void *d_best_waypoints, const double *d_best_cost, uint64_t seed, uint32_t iteration,
+                      uint32_t first_problem, void *d_waypoints);
+int vap_search_update(vap_ctx *ctx, int dt, int R, int N, int W, const void *d_waypoints, const int *d_counts, int counts_stride,
+                      double time_step, const double *d_meta, const uint32_t *d_flags, const double *d_clearance,
+                      const double *d_conflict_clearance, const double *d_tracking_worst, const vap_search_weights *weights,
+                      int E, double alpha, double sigma_min, double sigma_max, double *d_mean, double *d_sigma, double *d_cost,
+                      double *d_violation, int *d_order, int *d_n_feasible, double *d_best_cost, void *d_best_waypoints,
+                      double *d_best_terms, double *d_history, int history_stride, uint32_t iteration);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,7 +63,7 @@ EXPORTS = (
     "vap_grid_distances", "vap_route_limits", "vap_velocity_pass_limits", "vap_time_insert_waits", "vap_fit_ex",
     "vap_profile_routes", "vap_time_profile_routes", "vap_time_insert_events", "vap_limit_rows_dtype",
     "vap_closest_points", "vap_route_closest", "vap_footprint_clearance", "vap_footprint_conflicts",
-    "vap_tracking_rollouts",
+    "vap_tracking_rollouts", "vap_search_sample", "vap_search_update",
 )
 
 
@@ -77,6 +77,12 @@ class FollowerStruct(C.Structure):
     """vap_follower (include/vap.h)."""
     _fields_ = [("track_width", C.c_double), ("b", C.c_double), ("zeta", C.c_double), ("wheel_speed_max", C.c_double),
                 ("tolerance", C.c_double), ("n_substeps", C.c_int), ("settle_rows", C.c_int)]
+
+
+class SearchWeights(C.Structure):
+    """vap_search_weights (include/vap.h)."""
+    _fields_ = [("w_time", C.c_double), ("w_length", C.c_double), ("w_violation", C.c_double), ("infeasible_base", C.c_double),
+                ("clearance_margin", C.c_double), ("conflict_margin", C.c_double), ("tracking_tolerance", C.c_double)]
 
 
 ip = C.POINTER(C.c_int)
@@ -180,6 +186,9 @@ def lib():
     L.vap_footprint_conflicts.argtypes = [vp, C.c_int, C.c_int, C.c_double] + side + side + [vp] * 8
     L.vap_tracking_rollouts.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_double, C.POINTER(FollowerStruct), C.c_int,
                                         C.c_int, vp] + [vp] * 7 + [C.c_long, vp, vp]
+    L.vap_search_sample.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]
+    L.vap_search_update.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double] + [vp] * 5 + \
+        [C.POINTER(SearchWeights), C.c_int, C.c_double, C.c_double, C.c_double] + [vp] * 10 + [C.c_int, C.c_uint32]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("vap_version", "vap_device_count"):

@@ -468,5 +468,14 @@ class BatchedTrajectoryGenerator:
             raise ValueError(f"rows must be on {self.device}")
         return tracking.rollouts(tp["rows"], tp["counts"], follower, perturbations, ctx=self.ctx, **kw)
 
+    def refine(self, seeds, sigma0, footprint, scene, **kw):
+        """Cross-entropy search for faster routes that still clear ``scene`` (and a partner's routines, and a follower's
+        tracking error), starting from ``seeds``: sample, profile, time_profile, clearance checks and the refit run on this
+        generator's context and torch's current stream with no host synchronisation (vap_search_sample /
+        vap_search_update; see search.refine for sigma0, the keyword arguments, SearchConfig and the returned dict).
+        Plain-node paths only."""
+        from . import search
+        return search.refine(self, seeds, sigma0, footprint, scene, **kw)
+
     def timing(self):
         return self.ctx.last_timing()
