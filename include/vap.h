@@ -682,6 +682,78 @@ int vap_search_update(vap_ctx *ctx, int dt, int R, int N, int W, const void *d_w
                       double *d_violation, int *d_order, int *d_n_feasible, double *d_best_cost, void *d_best_waypoints,
                       double *d_best_terms, double *d_history, int history_stride, uint32_t iteration);
 
+/* ---- seed routes through a scene, on a grid ----------------------------------------------------------------------------
+ * vap_search_* refine a route that is already roughly right; these two calls find one.  The robot is a disc of radius
+ * `radius` (feet); the scene is vap_footprint_clearance's (h_field, polygons, circles: the same validation, limits and
+ * status codes), and a field box is required (h_field == NULL: VAP_ERR_INVALID).  Everything below is decided by integer
+ * comparisons or by comparisons of single IEEE additions, so the outputs do not depend on scheduling: two calls give the
+ * same bits, and a heap Dijkstra doing the same additions gives the same distance field bit for bit.  No FMA anywhere.
+ *
+ *   grid      nx = ceil((xmax - xmin) / cell), ny = ceil((ymax - ymin) / cell); cell (i, j), index j * nx + i, has its centre
+ *             at (xmin + (i + 0.5) * cell, ymin + (j + 0.5) * cell); a point lies in cell i = clamp(floor((x - xmin) / cell),
+ *             0, nx - 1), j likewise.  The last column or row may reach past the box when the quotient is no integer.
+ *   clearance of a cell centre p, the minimum of
+ *             wall     min(p.x - xmin, xmax - p.x, p.y - ymin, ymax - p.y);
+ *             polygon  with edges a -> b, e = b - a, |e| = sqrt(e.x e.x + e.y e.y): s = ((p - a) x e) / |e|, the outward
+ *                      signed distance to the edge's line.  If the largest s is > 0: the smallest point-to-segment
+ *                      distance, sqrt of the smallest dx dx + dy dy with (dx, dy) = (p - a) - t e, t = ((p - a) . e) *
+ *                      (1 / (e.x e.x + e.y e.y)) clamped to [0, 1]; else the largest s (<= 0, inside);
+ *             circle   sqrt(dx dx + dy dy) - r;
+ *             minus radius.  A cell is FREE iff clearance >= margin.
+ *   distance  per problem, from the goal's cell, over the eight moves (di, dj) in this order: (1,0) (0,1) (-1,0) (0,-1)
+ *             (1,1) (-1,1) (-1,-1) (1,-1); an axis move costs w = cell, a diagonal one w = cell * 1.4142135623730951.  A
+ *             move between two free cells is allowed; a diagonal one also needs the two axis cells it passes between to
+ *             be free (no corner is cut).  d[goal cell] = 0, d[v] = min over allowed moves v -> u of fl(d[u] + w): the
+ *             unique fixed point.  Cells that are not free, or not reached, have +inf.
+ *   snapping  if the start's or the goal's own cell is not free, the free cell nearest to the point is used: smallest
+ *             dx dx + dy dy from the point to the cell centre, the lowest index on a tie (a robot parked against a wall is
+ *             the usual start, and a disc of the circumscribed radius does not fit there).  VAP_PLAN_SNAPPED_START /
+ *             VAP_PLAN_SNAPPED_GOAL say so.
+ *   trace     from the (snapped) start cell, step to the allowed neighbour with the smallest fl(d[u] + w), the first in the
+ *             move order on a tie (strict <), until d = 0.
+ *   pull      over the traced cells c_0 .. c_(n-1): anchor a = 0; take the largest b > a with c_b visible from c_a, or
+ *             a + 1 if none beyond it is; emit c_b; a = b.  c_b is visible from c_a = (i0, j0) when, with (dx, dy) the index
+ *             difference, every cell (i, j) of the two cells' bounding box with 2 |(i - i0) dy - (j - j0) dx| <= |dx| + |dy|
+ *             is free (the supercover of the segment between the centres; integers only).
+ *   vertices  the start, the centres of the emitted cells but the last, the goal: c_0's centre is replaced by the exact
+ *             start and the goal cell's by the exact goal; [start, goal] when both share a cell.  Visibility holds between
+ *             centres, so the first and last segment may be off by up to half a cell (more after snapping): these are
+ *             SEEDS for the search, not checked routes.
+ *   waypoints l_m = sqrt(dx dx + dy dy) of segment m, c_0 = 0, c_(m+1) = c_m + l_m in order, L = the last c.  Waypoint k =
+ *             1 .. W-2 lies at arc s = (k * L) / (W - 1) on the first segment m with c_(m+1) >= s and l_m > 0, at a + ((s -
+ *             c_m) / l_m) * (b - a) (the goal if there is none: L = 0).  Waypoints 0 and W-1 are the start's and the goal's
+ *             own bits.  fp64.
+ *   failures  a non-finite start or goal (VAP_FLAG_DEGENERATE), no free cell at all (VAP_PLAN_NO_FREE), a start whose d is
+ *             +inf (VAP_PLAN_UNREACHABLE): NaN waypoints and vertices, length +inf, n_vertices 0 (and, for the first two, a
+ *             distance field of +inf; the unreachable start's field is the goal's own).  The relaxation stops
+ *             after a sweep that changes nothing and after nx * ny sweeps at the latest, the trace after nx * ny cells; a
+ *             shortest path has fewer edges, so valid input never gets there (VAP_FLAG_NOCONVERGE if it does).
+ *
+ * vap_plan_grid writes d_clearance [ny][nx] fp64 and d_free [ny][nx] bytes (1 = free); either may be NULL, and with both
+ * NULL the call only checks its arguments and reports nx, ny (host ints, either may be NULL) without a context.
+ * vap_plan_seeds plans R problems, d_starts / d_goals [R][2] fp64 on the device, one workgroup per problem at a time with
+ * the distance field in LDS: d_waypoints [R][W][2]; optional (NULL to skip) d_length [R], d_flags [R], d_n_vertices [R]
+ * (all vertices, also beyond max_vertices), d_vertices [R][max_vertices][2] (the first max_vertices, NaN behind the last;
+ * more vertices than that set VAP_PLAN_VERTICES_TRUNCATED, only when this output is asked for; the waypoints always use
+ * every vertex), d_distance [R][ny][nx].
+ * VAP_ERR_INVALID: cell <= 0, radius < 0, a non-finite cell, radius or margin, no field box, a bad scene, W < 2, R < 0, a
+ * null start, goal or waypoint pointer with R > 0, max_vertices < 2 with d_vertices.  VAP_ERR_UNSUPPORTED: nx * ny above
+ * 16384, W above 2048, the scene's limits, a device whose LDS cannot hold the grid.  The arguments are checked before the
+ * context is touched.  R = 0 is a no-op.  Both work on the context's stream and do not synchronise; the scene is host
+ * memory, uploaded once per call. */
+#define VAP_PLAN_SNAPPED_START 16u
+#define VAP_PLAN_SNAPPED_GOAL 32u
+#define VAP_PLAN_NO_FREE 64u
+#define VAP_PLAN_UNREACHABLE 128u
+#define VAP_PLAN_VERTICES_TRUNCATED 256u
+int vap_plan_grid(vap_ctx *ctx, const double *h_field, int n_poly, const int *h_poly_start, const double *h_poly_xy, int n_circle,
+                  const double *h_circles, double cell, double radius, double margin, double *d_clearance, uint8_t *d_free,
+                  int *nx_out, int *ny_out);
+int vap_plan_seeds(vap_ctx *ctx, int R, int W, const double *d_starts, const double *d_goals, const double *h_field, int n_poly,
+                   const int *h_poly_start, const double *h_poly_xy, int n_circle, const double *h_circles, double cell,
+                   double radius, double margin, int max_vertices, double *d_waypoints, double *d_length, uint32_t *d_flags,
+                   int *d_n_vertices, double *d_vertices, double *d_distance);
+
 #ifdef __cplusplus
 }
 #endif

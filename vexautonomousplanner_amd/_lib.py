@@ -23,6 +23,7 @@ FLAG_DEGENERATE = 1
 FLAG_TRUNCATED = 2
 FLAG_NOCONVERGE = 4
 FLAG_BAD_ROUTE = 8
+PLAN_SNAPPED_START, PLAN_SNAPPED_GOAL, PLAN_NO_FREE, PLAN_UNREACHABLE, PLAN_VERTICES_TRUNCATED = 16, 32, 64, 128, 256
 T_FIT, T_LUT, T_SAMPLE, T_VELOCITY, T_TOTAL, T_COUNT = 0, 1, 2, 3, 4, 8
 OPT_VELOCITY_KERNEL = 0
 OPT_TIME_DOMAIN_RESIDUAL = 3
@@ -63,7 +64,7 @@ EXPORTS = (
     "vap_grid_distances", "vap_route_limits", "vap_velocity_pass_limits", "vap_time_insert_waits", "vap_fit_ex",
     "vap_profile_routes", "vap_time_profile_routes", "vap_time_insert_events", "vap_limit_rows_dtype",
     "vap_closest_points", "vap_route_closest", "vap_footprint_clearance", "vap_footprint_conflicts",
-    "vap_tracking_rollouts", "vap_search_sample", "vap_search_update",
+    "vap_tracking_rollouts", "vap_search_sample", "vap_search_update", "vap_plan_grid", "vap_plan_seeds",
 )
 
 
@@ -189,6 +190,9 @@ def lib():
     L.vap_search_sample.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]
     L.vap_search_update.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double] + [vp] * 5 + \
         [C.POINTER(SearchWeights), C.c_int, C.c_double, C.c_double, C.c_double] + [vp] * 10 + [C.c_int, C.c_uint32]
+    scene = [dp, C.c_int, ip, dp, C.c_int, dp, C.c_double, C.c_double, C.c_double]   # field .. circles, cell, radius, margin
+    L.vap_plan_grid.argtypes = [vp] + scene + [vp, vp, ip, ip]
+    L.vap_plan_seeds.argtypes = [vp, C.c_int, C.c_int, vp, vp] + scene + [C.c_int] + [vp] * 6
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("vap_version", "vap_device_count"):

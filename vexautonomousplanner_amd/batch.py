@@ -477,5 +477,12 @@ class BatchedTrajectoryGenerator:
         from . import search
         return search.refine(self, seeds, sigma0, footprint, scene, **kw)
 
+    def plan_seeds(self, starts, goals, scene, waypoints, radius, **kw):
+        """Seed routes round ``scene``'s obstacles for a disc of ``radius`` feet, one per (start, goal) pair, on this
+        generator's device and context (vap_plan_seeds; see plan.seeds for the keyword arguments and the returned dict).
+        ``plan_seeds(...)["waypoints"]`` is what ``refine`` takes as ``seeds``."""
+        from . import plan
+        return plan.seeds(starts, goals, scene, waypoints, radius, device=self.device.index, ctx=self.ctx, **kw)
+
     def timing(self):
         return self.ctx.last_timing()

@@ -254,7 +254,7 @@ int vap_ctx_destroy(vap_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     VapBuffer *bufs[] = {&ctx->sptab, &ctx->nspl, &ctx->k64, &ctx->dth64, &ctx->ufwd, &ctx->vhi, &ctx->vres, &ctx->lstate, &ctx->lcount, &ctx->seg, &ctx->power, &ctx->lut, &ctx->slopes, &ctx->aux, &ctx->runs, &ctx->meta, &ctx->dth, &ctx->flags, &ctx->small_in,
                       &ctx->small_out, &ctx->small_seg, &ctx->small_lut, &ctx->scene, &ctx->conf_pack_a, &ctx->conf_pack_o,
-                      &ctx->conf_blk_a, &ctx->conf_blk_o, &ctx->conf_part, &ctx->track_part};
+                      &ctx->conf_blk_a, &ctx->conf_blk_o, &ctx->conf_part, &ctx->track_part, &ctx->plan_free, &ctx->plan_path};
     for (VapBuffer *b : bufs)
         if (b->ptr) (void)hipFree(b->ptr);
     for (VapBuffer &b : ctx->io)

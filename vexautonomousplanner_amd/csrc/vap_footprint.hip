@@ -26,9 +26,6 @@ namespace vap {
 
 constexpr int kFootThreads = 256;
 constexpr int kFootWaves = kFootThreads / 64;
-constexpr int kFootMaxPolys = 256;
-constexpr int kFootMaxPolyVerts = 4096;  // all polygons together
-constexpr int kFootMaxCircles = 256;
 
 // Packed scene (fp64):
 //   foot  [n_foot][8]  body vertex x, y; outward unit normal of the edge to the next vertex nx, ny; that edge ex, ey;
@@ -321,30 +318,15 @@ void bound_polygon(const double *v, int n, double &cx, double &cy, double &r)
     for (int i = 0; i < n; i++) r = std::fmax(r, std::hypot(v[2 * i] - cx, v[2 * i + 1] - cy));
 }
 
-}  // namespace vap
-
-extern "C" {
-
-int vap_footprint_clearance(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride,
-                            int n_foot, const double *h_footprint, const double *h_field, int n_poly, const int *h_poly_start,
-                            const double *h_poly_xy, int n_circle, const double *h_circles, double margin,
-                            double *d_row_clearance, double *d_min_clearance, int *d_min_row, int *d_min_element,
-                            int *d_first_row, int *d_n_below)
+// The field box, polygons and circles of a scene (include/vap.h, vap_footprint_clearance): limits and geometry.  scale: the
+// largest coordinate magnitude; nv: the polygons' vertices together.  Host only, no device call.
+int check_scene(const double *h_field, int n_poly, const int *h_poly_start, const double *h_poly_xy, int n_circle,
+                const double *h_circles, double &scale, int &nv)
 {
-    using namespace vap;
-    VAP_TRY(vap_set_device(ctx));
-    if (B < 0 || capacity < 0) return vap_fail(VAP_ERR_INVALID, "bad shape B=%d capacity=%ld", B, capacity);
-    if (capacity > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "capacity %ld above %d rows", capacity, INT_MAX);
-    if (counts_stride < 1) return vap_fail(VAP_ERR_INVALID, "counts_stride must be >= 1 (got %d)", counts_stride);
-    if (B > 0 && (!d_counts || (capacity > 0 && !d_rows))) return vap_fail(VAP_ERR_INVALID, "null rows / counts");
-    if (!std::isfinite(margin)) return vap_fail(VAP_ERR_INVALID, "margin must be finite");
-    // the scene
-    if (!h_footprint) return vap_fail(VAP_ERR_INVALID, "null footprint");
-    VAP_TRY(check_convex(h_footprint, n_foot, "footprint", 0));
     if (n_poly < 0 || n_circle < 0) return vap_fail(VAP_ERR_INVALID, "negative element count");
     if (n_poly > kFootMaxPolys) return vap_fail(VAP_ERR_UNSUPPORTED, "%d polygons (at most %d)", n_poly, kFootMaxPolys);
     if (n_circle > kFootMaxCircles) return vap_fail(VAP_ERR_UNSUPPORTED, "%d circles (at most %d)", n_circle, kFootMaxCircles);
-    double scale = 0.0;
+    scale = 0.0;
     if (h_field) {
         for (int i = 0; i < 4; i++) {
             if (!std::isfinite(h_field[i])) return vap_fail(VAP_ERR_INVALID, "non-finite field box");
@@ -353,7 +335,7 @@ int vap_footprint_clearance(vap_ctx *ctx, int B, long capacity, const double *d_
         if (!(h_field[0] < h_field[2]) || !(h_field[1] < h_field[3]))
             return vap_fail(VAP_ERR_INVALID, "empty field box (%g, %g, %g, %g)", h_field[0], h_field[1], h_field[2], h_field[3]);
     }
-    int nv = 0;
+    nv = 0;
     if (n_poly > 0) {
         if (!h_poly_start || !h_poly_xy) return vap_fail(VAP_ERR_INVALID, "null polygon arrays");
         if (h_poly_start[0] != 0) return vap_fail(VAP_ERR_INVALID, "poly_start[0] must be 0");
@@ -378,12 +360,13 @@ int vap_footprint_clearance(vap_ctx *ctx, int B, long capacity, const double *d_
             scale = std::fmax(scale, std::fabs(ck[0]) + std::fabs(ck[1]) + ck[2]);
         }
     }
-    if (B == 0) return VAP_OK;
+    return VAP_OK;
+}
 
-    // pack: foot [n_foot][8] | poly [n_poly][4] | pv [nv][8] | circ [n_circle][4]
-    const size_t o_poly = (size_t)n_foot * 8, o_pv = o_poly + (size_t)n_poly * 4, o_circ = o_pv + (size_t)nv * 8;
-    const size_t n_dbl = o_circ + (size_t)n_circle * 4;
-    const size_t bytes = n_dbl * sizeof(double);
+// The pinned host block of the packed scene, at least `bytes` long and free of the previous upload, and room for it on
+// the device (ctx->scene).
+int scene_stage(vap_ctx *ctx, size_t bytes, double **h)
+{
     if (!ctx->scene_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->scene_ev, hipEventDisableTiming));
     else HIP_TRY(hipEventSynchronize(ctx->scene_ev));      // the previous upload has left the host block
     if (bytes > ctx->scene_host_cap) {
@@ -394,8 +377,50 @@ int vap_footprint_clearance(vap_ctx *ctx, int B, long capacity, const double *d_
         ctx->scene_host_cap = bytes;
     }
     VAP_TRY(ctx->ensure(ctx->scene, bytes));
-    double *h = (double *)ctx->scene_host;
-    std::memset(h, 0, bytes);
+    *h = (double *)ctx->scene_host;
+    std::memset(*h, 0, bytes);
+    return VAP_OK;
+}
+
+// Upload the staged block on the context's stream.
+int scene_upload(vap_ctx *ctx, size_t bytes)
+{
+    HIP_TRY(hipMemcpyAsync(ctx->scene.ptr, ctx->scene_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->scene_ev, ctx->stream));
+    return VAP_OK;
+}
+
+}  // namespace vap
+
+extern "C" {
+
+int vap_footprint_clearance(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride,
+                            int n_foot, const double *h_footprint, const double *h_field, int n_poly, const int *h_poly_start,
+                            const double *h_poly_xy, int n_circle, const double *h_circles, double margin,
+                            double *d_row_clearance, double *d_min_clearance, int *d_min_row, int *d_min_element,
+                            int *d_first_row, int *d_n_below)
+{
+    using namespace vap;
+    VAP_TRY(vap_set_device(ctx));
+    if (B < 0 || capacity < 0) return vap_fail(VAP_ERR_INVALID, "bad shape B=%d capacity=%ld", B, capacity);
+    if (capacity > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "capacity %ld above %d rows", capacity, INT_MAX);
+    if (counts_stride < 1) return vap_fail(VAP_ERR_INVALID, "counts_stride must be >= 1 (got %d)", counts_stride);
+    if (B > 0 && (!d_counts || (capacity > 0 && !d_rows))) return vap_fail(VAP_ERR_INVALID, "null rows / counts");
+    if (!std::isfinite(margin)) return vap_fail(VAP_ERR_INVALID, "margin must be finite");
+    // the scene
+    if (!h_footprint) return vap_fail(VAP_ERR_INVALID, "null footprint");
+    VAP_TRY(check_convex(h_footprint, n_foot, "footprint", 0));
+    double scale = 0.0;
+    int nv = 0;
+    VAP_TRY(check_scene(h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, scale, nv));
+    if (B == 0) return VAP_OK;
+
+    // pack: foot [n_foot][8] | poly [n_poly][4] | pv [nv][8] | circ [n_circle][4]
+    const size_t o_poly = (size_t)n_foot * 8, o_pv = o_poly + (size_t)n_poly * 4, o_circ = o_pv + (size_t)nv * 8;
+    const size_t n_dbl = o_circ + (size_t)n_circle * 4;
+    const size_t bytes = n_dbl * sizeof(double);
+    double *h = nullptr;
+    VAP_TRY(scene_stage(ctx, bytes, &h));
     FootScene s;
     pack_polygon(h_footprint, n_foot, h);
     bound_polygon(h_footprint, n_foot, s.fcx, s.fcy, s.fR);
@@ -408,8 +433,7 @@ int vap_footprint_clearance(vap_ctx *ctx, int B, long capacity, const double *d_
     }
     for (int k = 0; k < n_circle; k++)
         for (int j = 0; j < 3; j++) h[o_circ + (size_t)k * 4 + j] = h_circles[3 * (size_t)k + j];
-    HIP_TRY(hipMemcpyAsync(ctx->scene.ptr, h, bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->scene_ev, ctx->stream));
+    VAP_TRY(scene_upload(ctx, bytes));
 
     const double *d = (const double *)ctx->scene.ptr;
     s.foot = d;

@@ -70,6 +70,8 @@ struct vap_ctx {
     VapBuffer conf_pack_a, conf_pack_o, conf_blk_a, conf_blk_o, conf_part;
     // vap_tracking_rollouts with more than 256 rollouts per route: per-rollout (max e_pos, row) for the reduce kernel
     VapBuffer track_part;
+    // vap_plan_seeds: the grid's free mask, and the traced cell lists (one per resident workgroup)
+    VapBuffer plan_free, plan_path;
 
     int ensure(VapBuffer &b, size_t bytes)
     {

@@ -1,0 +1,568 @@
+// vap_plan.hip — seed routes through a scene on a grid (vap_plan_grid, vap_plan_seeds).
+//
+// The route search refines a route that is already roughly right; this file finds one.  The robot is a disc of radius
+// rho on a grid over the field box; a cell is free when the disc at its centre clears the walls, polygons and circles by
+// the margin; an 8-connected shortest-path field from the goal's cell, a steepest-descent trace from the start's, a
+// line-of-sight pull of the traced cells and an equal-arc resample give W waypoints per (start, goal) pair.  Every
+// decision is an integer comparison or a comparison of single IEEE additions, so the result does not depend on the order
+// of the work.  Definitions: include/vap.h.
+//
+//   k_plan_clearance  a thread per cell.  The polygons pass through LDS 32 at a time (their packed edge rows, 32 KB), the
+//                     circles in one piece (8 KB); a thread walks them at wave-uniform LDS addresses (broadcast reads).
+//   k_plan_seeds      persistent workgroups of 1024 threads, each taking problems r = block, block + grid, ...  LDS holds
+//                     the whole distance field (8 B a cell, 128 KB at the 16384-cell limit), the free mask as bits (2 KB)
+//                     and, per cell, the byte of its allowed moves (16 KB) — both built once per workgroup, since every
+//                     problem shares the scene: 146 KB of gfx950's 160 KB, one workgroup per CU at the limit.
+//                       relax   Jacobi sweeps: a read phase (each thread keeps the new values of its <= 16 cells in
+//                               registers), a barrier, a write phase, and __syncthreads_or of "changed" as the second
+//                               barrier.  Neighbours are at constant offsets; the move byte has done the bounds, the
+//                               free test and the no-corner-cutting rule once.
+//                       snap    a workgroup argmin over (distance^2, cell index): wave shuffles, then 16 partials in LDS.
+//                       trace   one lane; the cell list goes to a global workspace (the LDS has no room for a worst-case
+//                               list), one list per resident workgroup.
+//                       pull    candidates b = n-1, n-2, ... one per lane, 1024 at a time; a lane runs the integer
+//                               supercover test along the major axis (at most four cells per step can satisfy it); the
+//                               largest visible b is an integer atomicMax in LDS.  The pulled list overwrites the front of
+//                               the traced one.
+//                       resample  segment lengths a thread each, their running sum on one lane (a fixed order), then a
+//                               thread per waypoint.  The sums live where the distance field was.
+//                     No float atomics: two calls give the same bits.
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+
+#include "vap_footprint.h"
+#include "vap_kernels.h"
+
+namespace vap {
+
+constexpr int kPlanMaxCells = 16384;
+constexpr int kPlanThreads = 1024;
+constexpr int kPlanWaves = kPlanThreads / 64;
+constexpr int kPlanCellsPerThread = kPlanMaxCells / kPlanThreads;   // 16
+constexpr int kPlanMaxBlocks = 1024;                                // x 32 KB of cell list at the limit
+constexpr int kPlanGridThreads = 256;
+constexpr int kPlanChunkPolys = 32;                                 // polygons in LDS at a time
+constexpr size_t kPlanStaticLds = 512;                              // bound on k_plan_seeds' static LDS
+constexpr double kPlanSqrt2 = 1.4142135623730951;
+
+struct PlanGrid {
+    double xmin, ymin, xmax, ymax, cell;
+    int nx, ny;
+};
+
+// Packed scene (fp64), the layouts of vap_footprint.hip:
+//   poly  [n_poly][4]   -, -, -, first vertex * 32 + vertex count (as a double)
+//   pv    [nv][8]       vertex x, y; -, -; the edge to the next vertex ex, ey; 1 / |e|^2; |e| = sqrt(ex ex + ey ey)
+//   circ  [n_circle][4] cx, cy, r, 0
+struct PlanScene {
+    const double *poly, *pv, *circ;
+    int n_poly, n_circle;
+};
+
+__device__ __forceinline__ double plan_centre(double lo, int i, double cell) { return lo + ((double)i + 0.5) * cell; }
+
+// the cell of a finite coordinate, clamped to the grid
+__device__ __forceinline__ int plan_cell_of(double x, double lo, double cell, int n)
+{
+    double f = floor((x - lo) / cell);
+    f = f < 0.0 ? 0.0 : (f > (double)(n - 1) ? (double)(n - 1) : f);
+    return (int)f;
+}
+
+__global__ __launch_bounds__(kPlanGridThreads) void k_plan_clearance(PlanGrid g, PlanScene s, double radius, double margin,
+                                                                     double *__restrict__ clearance, uint8_t *__restrict__ free_mask)
+{
+    __shared__ double s_pv[kPlanChunkPolys * kFootMaxVerts * 8];
+    __shared__ double s_circ[kFootMaxCircles * 4];
+    __shared__ int s_code[kPlanChunkPolys];
+    const int tid = threadIdx.x;
+    const int idx = blockIdx.x * kPlanGridThreads + tid;
+    const bool live = idx < g.nx * g.ny;
+    const int j = live ? idx / g.nx : 0, i = live ? idx - j * g.nx : 0;
+    const double px = plan_centre(g.xmin, i, g.cell), py = plan_centre(g.ymin, j, g.cell);
+    double best = fmin(fmin(px - g.xmin, g.xmax - px), fmin(py - g.ymin, g.ymax - py));
+#pragma unroll 1
+    for (int k0 = 0; k0 < s.n_poly; k0 += kPlanChunkPolys) {
+        const int k1 = min(k0 + kPlanChunkPolys, s.n_poly);
+        const int v0 = (int)s.poly[(size_t)k0 * 4 + 3] >> 5;
+        const int last = (int)s.poly[(size_t)(k1 - 1) * 4 + 3];
+        const int nrow = (last >> 5) + (last & 31) - v0;             // <= 32 x 16
+        __syncthreads();
+        for (int t = tid; t < nrow * 8; t += kPlanGridThreads) s_pv[t] = s.pv[(size_t)v0 * 8 + t];
+        for (int t = tid; t < k1 - k0; t += kPlanGridThreads) s_code[t] = (int)s.poly[(size_t)(k0 + t) * 4 + 3];
+        __syncthreads();
+        if (!live) continue;
+#pragma unroll 1
+        for (int k = 0; k < k1 - k0; k++) {
+            const int code = s_code[k], m = code & 31;
+            const double *row = s_pv + (size_t)((code >> 5) - v0) * 8;
+            double smax = -INFINITY, d2 = INFINITY;
+#pragma unroll 1
+            for (int e = 0; e < m; e++, row += 8) {
+                const double wx = px - row[0], wy = py - row[1];
+                smax = fmax(smax, (wx * row[5] - wy * row[4]) / row[7]);
+                d2 = fmin(d2, seg_dist2(px, py, row[0], row[1], row[4], row[5], row[6]));
+            }
+            best = fmin(best, smax > 0.0 ? sqrt(d2) : smax);
+        }
+    }
+    __syncthreads();
+    for (int t = tid; t < s.n_circle * 4; t += kPlanGridThreads) s_circ[t] = s.circ[t];
+    __syncthreads();
+    if (!live) return;
+#pragma unroll 1
+    for (int k = 0; k < s.n_circle; k++) {
+        const double dx = px - s_circ[k * 4 + 0], dy = py - s_circ[k * 4 + 1];
+        best = fmin(best, sqrt(dx * dx + dy * dy) - s_circ[k * 4 + 2]);
+    }
+    const double c = best - radius;
+    if (clearance) clearance[idx] = c;
+    if (free_mask) free_mask[idx] = c >= margin ? 1 : 0;
+}
+
+struct SeedArgs {
+    PlanGrid g;
+    int R, W, max_vertices;
+    const double *starts, *goals;
+    const uint8_t *free_mask;
+    uint16_t *path_ws;          // [gridDim.x][nx * ny]
+    double *wp, *length;
+    uint32_t *flags;
+    int *n_vertices;
+    double *vertices, *distance;
+};
+
+__device__ __forceinline__ bool plan_free(const uint32_t *fb, int idx) { return (fb[idx >> 5] >> (idx & 31)) & 1u; }
+
+__device__ __forceinline__ int plan_floordiv(int a, int b)
+{
+    int q = a / b;
+    if (a % b != 0 && ((a < 0) != (b < 0))) q--;
+    return q;
+}
+
+// Every cell (i, j) of the bounding box of the two cells with 2 |(i - i0) dy - (j - j0) dx| <= |dx| + |dy| is free.  With
+// |dy| <= |dx| the bound is at most |dx|, so j - j0 lies within 1 of (i - i0) dy / dx: the four cells floor(.) - 1 ..
+// floor(.) + 2 of each column hold every cell the condition can pick (and likewise along y).
+__device__ bool plan_visible(const uint32_t *fb, int nx, int c0, int c1)
+{
+    const int j0 = c0 / nx, i0 = c0 - j0 * nx, j1 = c1 / nx, i1 = c1 - j1 * nx;
+    const int dx = i1 - i0, dy = j1 - j0, lim = abs(dx) + abs(dy);
+    const int ilo = min(i0, i1), ihi = max(i0, i1), jlo = min(j0, j1), jhi = max(j0, j1);
+    if (abs(dx) >= abs(dy)) {
+        if (dx == 0) return true;                                    // the same cell
+        for (int i = ilo; i <= ihi; i++) {
+            const int q = plan_floordiv((i - i0) * dy, dx);
+            for (int j = max(j0 + q - 1, jlo); j <= min(j0 + q + 2, jhi); j++)
+                if (2 * abs((i - i0) * dy - (j - j0) * dx) <= lim && !plan_free(fb, j * nx + i)) return false;
+        }
+    } else {
+        for (int j = jlo; j <= jhi; j++) {
+            const int q = plan_floordiv((j - j0) * dx, dy);
+            for (int i = max(i0 + q - 1, ilo); i <= min(i0 + q + 2, ihi); i++)
+                if (2 * abs((i - i0) * dy - (j - j0) * dx) <= lim && !plan_free(fb, j * nx + i)) return false;
+        }
+    }
+    return true;
+}
+
+// The free cell nearest to (px, py) by dx dx + dy dy to its centre, the lowest index on a tie; the whole workgroup calls it.
+__device__ int plan_nearest_free(const PlanGrid &g, const uint32_t *fb, double px, double py, double *s_key, int *s_idx)
+{
+    const int tid = threadIdx.x, ncell = g.nx * g.ny;
+    double best = INFINITY;
+    int bi = INT_MAX;
+    for (int idx = tid; idx < ncell; idx += kPlanThreads) {          // ascending per thread: the first minimum stays
+        if (!plan_free(fb, idx)) continue;
+        const int j = idx / g.nx, i = idx - j * g.nx;
+        const double dx = plan_centre(g.xmin, i, g.cell) - px, dy = plan_centre(g.ymin, j, g.cell) - py;
+        const double d2 = dx * dx + dy * dy;
+        if (d2 < best) { best = d2; bi = idx; }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double ob = __shfl_xor(best, off);
+        const int oi = __shfl_xor(bi, off);
+        if (ob < best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    if ((tid & 63) == 0) {
+        s_key[tid >> 6] = best;
+        s_idx[tid >> 6] = bi;
+    }
+    __syncthreads();
+    best = s_key[0];
+    bi = s_idx[0];
+    for (int w = 1; w < kPlanWaves; w++)
+        if (s_key[w] < best || (s_key[w] == best && s_idx[w] < bi)) { best = s_key[w]; bi = s_idx[w]; }
+    __syncthreads();                                                 // the partials may be rewritten
+    return bi;
+}
+
+__global__ __launch_bounds__(kPlanThreads) void k_plan_seeds(SeedArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char plan_lds[];
+    __shared__ double s_key[kPlanWaves];
+    __shared__ int s_idx[kPlanWaves];
+    __shared__ int s_n, s_best, s_fail;
+    const PlanGrid g = a.g;
+    const int tid = threadIdx.x, nx = g.nx, ny = g.ny, ncell = nx * ny, nwords = (ncell + 31) / 32;
+    double *d = reinterpret_cast<double *>(plan_lds);
+    uint32_t *fb = reinterpret_cast<uint32_t *>(d + (ncell < 2 ? 2 : ncell));   // the sums c_0, c_1 of a one-cell grid
+    uint8_t *mv = reinterpret_cast<uint8_t *>(fb + nwords);
+    // the eight moves in the header's order: offset in the grid and cost
+    const int off[8] = {1, nx, -1, -nx, nx + 1, nx - 1, -nx - 1, -nx + 1};
+    const double wa = g.cell, wd = g.cell * kPlanSqrt2;
+
+    // once per workgroup: the free bits, then each free cell's allowed moves
+    int any = 0;
+    for (int w = tid; w < nwords; w += kPlanThreads) {
+        uint32_t bits = 0;
+        for (int b = 0; b < 32; b++) {
+            const int idx = w * 32 + b;
+            if (idx < ncell && a.free_mask[idx]) bits |= 1u << b;
+        }
+        fb[w] = bits;
+        any |= bits != 0;
+    }
+    const bool any_free = __syncthreads_or(any);
+    for (int idx = tid; idx < ncell; idx += kPlanThreads) {
+        unsigned m = 0;
+        if (plan_free(fb, idx)) {
+            const int j = idx / nx, i = idx - j * nx;
+            const bool e = i + 1 < nx && plan_free(fb, idx + 1), n = j + 1 < ny && plan_free(fb, idx + nx);
+            const bool w = i > 0 && plan_free(fb, idx - 1), s = j > 0 && plan_free(fb, idx - nx);
+            m = (e ? 1u : 0u) | (n ? 2u : 0u) | (w ? 4u : 0u) | (s ? 8u : 0u);
+            if (e && n && plan_free(fb, idx + nx + 1)) m |= 16u;     // a diagonal needs both axis cells beside it
+            if (w && n && plan_free(fb, idx + nx - 1)) m |= 32u;
+            if (w && s && plan_free(fb, idx - nx - 1)) m |= 64u;
+            if (e && s && plan_free(fb, idx - nx + 1)) m |= 128u;
+        }
+        mv[idx] = (uint8_t)m;
+    }
+    __syncthreads();
+
+    uint16_t *path = a.path_ws + (size_t)blockIdx.x * (size_t)ncell;
+#pragma unroll 1
+    for (int r = blockIdx.x; r < a.R; r += gridDim.x) {
+        const double sx = a.starts[(size_t)r * 2], sy = a.starts[(size_t)r * 2 + 1];
+        const double gx = a.goals[(size_t)r * 2], gy = a.goals[(size_t)r * 2 + 1];
+        uint32_t flags = 0;
+        bool ok = true;
+        int sc = 0, gc = 0, nvtx = 0;
+        if (!(isfinite(sx) && isfinite(sy) && isfinite(gx) && isfinite(gy))) {
+            flags |= VAP_FLAG_DEGENERATE;
+            ok = false;
+        } else if (!any_free) {
+            flags |= VAP_PLAN_NO_FREE;
+            ok = false;
+        }
+        if (!ok && a.distance)                                       // no field: +inf everywhere
+            for (int idx = tid; idx < ncell; idx += kPlanThreads) a.distance[(size_t)r * ncell + idx] = INFINITY;
+        if (ok) {                                                    // every condition below is the same in all threads
+            gc = plan_cell_of(gy, g.ymin, g.cell, ny) * nx + plan_cell_of(gx, g.xmin, g.cell, nx);
+            if (!plan_free(fb, gc)) {
+                gc = plan_nearest_free(g, fb, gx, gy, s_key, s_idx);
+                flags |= VAP_PLAN_SNAPPED_GOAL;
+            }
+            sc = plan_cell_of(sy, g.ymin, g.cell, ny) * nx + plan_cell_of(sx, g.xmin, g.cell, nx);
+            if (!plan_free(fb, sc)) {
+                sc = plan_nearest_free(g, fb, sx, sy, s_key, s_idx);
+                flags |= VAP_PLAN_SNAPPED_START;
+            }
+            // the distance field: d[goal] = 0, d[v] = min over allowed moves v -> u of fl(d[u] + w)
+            for (int idx = tid; idx < ncell; idx += kPlanThreads) d[idx] = idx == gc ? 0.0 : INFINITY;
+            __syncthreads();
+            bool converged = false;
+#pragma unroll 1
+            for (int sweep = 0; sweep < ncell && !converged; sweep++) {
+                double nv[kPlanCellsPerThread];
+#pragma unroll
+                for (int c = 0; c < kPlanCellsPerThread; c++) {
+                    const int idx = tid + c * kPlanThreads;
+                    nv[c] = INFINITY;
+                    if (idx < ncell) {
+                        const unsigned m = mv[idx];
+                        double best = INFINITY;
+                        if (m) {
+#pragma unroll
+                            for (int k = 0; k < 8; k++)
+                                if (m & (1u << k)) best = fmin(best, d[idx + off[k]] + (k < 4 ? wa : wd));
+                        }
+                        nv[c] = best;
+                    }
+                }
+                __syncthreads();                                     // every read of this sweep is done
+                int changed = 0;
+#pragma unroll
+                for (int c = 0; c < kPlanCellsPerThread; c++) {
+                    const int idx = tid + c * kPlanThreads;
+                    if (idx < ncell && nv[c] < d[idx]) {
+                        d[idx] = nv[c];
+                        changed = 1;
+                    }
+                }
+                converged = !__syncthreads_or(changed);
+            }
+            if (!converged) flags |= VAP_FLAG_NOCONVERGE;
+            if (a.distance)
+                for (int idx = tid; idx < ncell; idx += kPlanThreads) a.distance[(size_t)r * ncell + idx] = d[idx];
+            if (d[sc] == INFINITY) {
+                flags |= VAP_PLAN_UNREACHABLE;
+                ok = false;
+            }
+        }
+        if (ok) {
+            // trace: from the start's cell to the allowed neighbour with the smallest fl(d[u] + w), the first on a tie
+            if (tid == 0) {
+                int cur = sc, n = 0;
+                path[n++] = (uint16_t)cur;
+                while (d[cur] > 0.0 && n < ncell) {
+                    const unsigned m = mv[cur];
+                    double best = INFINITY;
+                    int bu = -1;
+#pragma unroll
+                    for (int k = 0; k < 8; k++) {
+                        if (!(m & (1u << k))) continue;
+                        const double c = d[cur + off[k]] + (k < 4 ? wa : wd);
+                        if (c < best) { best = c; bu = cur + off[k]; }
+                    }
+                    if (bu < 0) break;
+                    cur = bu;
+                    path[n++] = (uint16_t)cur;
+                }
+                s_n = n;
+                s_fail = d[cur] > 0.0;
+            }
+            __syncthreads();
+            const int n = s_n;
+            if (s_fail) {
+                flags |= VAP_FLAG_NOCONVERGE;
+                ok = false;
+            }
+            __syncthreads();
+            if (ok) {
+                // pull: from anchor a the largest b whose cell is visible from a's, else a + 1
+                int nv = 1, anchor = 0;
+                while (anchor < n - 1) {
+                    if (tid == 0) s_best = anchor + 1;
+                    __syncthreads();
+                    const int ca = path[anchor];
+                    int bb = anchor + 1;
+                    for (int base = n - 1; base > anchor + 1; base -= kPlanThreads) {
+                        const int b = base - tid;
+                        if (b > anchor + 1 && plan_visible(fb, nx, ca, path[b])) atomicMax(&s_best, b);
+                        __syncthreads();
+                        bb = s_best;
+                        __syncthreads();
+                        if (bb > anchor + 1) break;
+                    }
+                    if (tid == 0) path[nv] = path[bb];               // nv <= bb: the front of the list is done with
+                    nv++;
+                    anchor = bb;
+                }
+                __syncthreads();
+                nvtx = n == 1 ? 2 : nv;
+            }
+        }
+        // vertex m: the start, the centres of the pulled cells, the goal
+        auto vertex = [&](int m, double &x, double &y) {
+            if (m == 0) { x = sx; y = sy; return; }
+            if (m == nvtx - 1) { x = gx; y = gy; return; }
+            const int c = path[m], j = c / nx;
+            x = plan_centre(g.xmin, c - j * nx, g.cell);
+            y = plan_centre(g.ymin, j, g.cell);
+        };
+        double *cum = d;                                             // the field is done with: c_0 .. c_(nvtx-1)
+        if (ok) {
+            for (int m = tid; m < nvtx - 1; m += kPlanThreads) {
+                double x0, y0, x1, y1;
+                vertex(m, x0, y0);
+                vertex(m + 1, x1, y1);
+                const double dx = x1 - x0, dy = y1 - y0;
+                cum[m + 1] = sqrt(dx * dx + dy * dy);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                cum[0] = 0.0;
+                for (int m = 1; m < nvtx; m++) cum[m] = cum[m - 1] + cum[m];
+            }
+            __syncthreads();
+        }
+        const double L = ok ? cum[nvtx - 1] : INFINITY;
+        double *wp = a.wp + (size_t)r * a.W * 2;
+        for (int k = tid; k < a.W; k += kPlanThreads) {
+            double x = NAN, y = NAN;
+            if (ok) {
+                x = gx;
+                y = gy;
+                if (k == 0) {
+                    x = sx;
+                    y = sy;
+                } else if (k < a.W - 1) {
+                    const double s = ((double)k * L) / (double)(a.W - 1);
+                    for (int m = 0; m < nvtx - 1; m++) {
+                        if (!(cum[m + 1] >= s)) continue;
+                        double x0, y0, x1, y1;
+                        vertex(m, x0, y0);
+                        vertex(m + 1, x1, y1);
+                        const double dx = x1 - x0, dy = y1 - y0, l = sqrt(dx * dx + dy * dy);
+                        if (!(l > 0.0)) continue;
+                        const double t = (s - cum[m]) / l;
+                        x = x0 + t * dx;
+                        y = y0 + t * dy;
+                        break;
+                    }
+                }
+            }
+            wp[2 * k] = x;
+            wp[2 * k + 1] = y;
+        }
+        if (a.vertices) {
+            double *vo = a.vertices + (size_t)r * a.max_vertices * 2;
+            for (int m = tid; m < a.max_vertices; m += kPlanThreads) {
+                double x = NAN, y = NAN;
+                if (ok && m < nvtx) vertex(m, x, y);
+                vo[2 * m] = x;
+                vo[2 * m + 1] = y;
+            }
+            if (ok && nvtx > a.max_vertices) flags |= VAP_PLAN_VERTICES_TRUNCATED;
+        }
+        if (tid == 0) {
+            if (a.length) a.length[r] = L;
+            if (a.flags) a.flags[r] = flags;
+            if (a.n_vertices) a.n_vertices[r] = ok ? nvtx : 0;
+        }
+        __syncthreads();                                             // the next problem rewrites the field and the list
+    }
+}
+
+// The arguments both calls share, checked on the host before anything touches the device; fills the grid.
+static int plan_check(const double *h_field, int n_poly, const int *h_poly_start, const double *h_poly_xy, int n_circle,
+                      const double *h_circles, double cell, double radius, double margin, PlanGrid &g, int &nv)
+{
+    if (!(cell > 0.0) || !std::isfinite(cell)) return vap_fail(VAP_ERR_INVALID, "cell must be positive and finite (got %g)", cell);
+    if (!(radius >= 0.0) || !std::isfinite(radius)) return vap_fail(VAP_ERR_INVALID, "radius must be >= 0 and finite (got %g)", radius);
+    if (!std::isfinite(margin)) return vap_fail(VAP_ERR_INVALID, "margin must be finite");
+    if (!h_field) return vap_fail(VAP_ERR_INVALID, "the planner needs a scene with a field box");
+    double scale = 0.0;
+    VAP_TRY(check_scene(h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, scale, nv));
+    const double fx = std::ceil((h_field[2] - h_field[0]) / cell), fy = std::ceil((h_field[3] - h_field[1]) / cell);
+    if (!(fx >= 1.0) || !(fy >= 1.0) || !std::isfinite(fx) || !std::isfinite(fy))
+        return vap_fail(VAP_ERR_INVALID, "the field box over cell %g gives no grid", cell);
+    if (fx * fy > (double)kPlanMaxCells)
+        return vap_fail(VAP_ERR_UNSUPPORTED, "a grid of %.0f x %.0f cells (at most %d cells)", fx, fy, kPlanMaxCells);
+    g.xmin = h_field[0];
+    g.ymin = h_field[1];
+    g.xmax = h_field[2];
+    g.ymax = h_field[3];
+    g.cell = cell;
+    g.nx = (int)fx;
+    g.ny = (int)fy;
+    return VAP_OK;
+}
+
+// Pack and upload the scene, then the clearance kernel over the grid.
+static int plan_launch_grid(vap_ctx *ctx, const PlanGrid &g, int nv, int n_poly, const int *h_poly_start, const double *h_poly_xy,
+                            int n_circle, const double *h_circles, double radius, double margin, double *d_clearance,
+                            uint8_t *d_free)
+{
+    // pack: poly [n_poly][4] | pv [nv][8] | circ [n_circle][4]
+    const size_t o_pv = (size_t)n_poly * 4, o_circ = o_pv + (size_t)nv * 8;
+    const size_t bytes = (o_circ + (size_t)n_circle * 4 + 1) * sizeof(double);
+    double *h = nullptr;
+    VAP_TRY(scene_stage(ctx, bytes, &h));
+    for (int k = 0; k < n_poly; k++) {
+        const int p0 = h_poly_start[k], m = h_poly_start[k + 1] - p0;
+        h[(size_t)k * 4 + 3] = (double)(p0 * 32 + m);
+        double *rows = h + o_pv + (size_t)p0 * 8;
+        pack_polygon(h_poly_xy + 2 * (size_t)p0, m, rows);
+        for (int e = 0; e < m; e++) rows[e * 8 + 7] = std::sqrt(rows[e * 8 + 4] * rows[e * 8 + 4] + rows[e * 8 + 5] * rows[e * 8 + 5]);
+    }
+    for (int k = 0; k < n_circle; k++)
+        for (int j = 0; j < 3; j++) h[o_circ + (size_t)k * 4 + j] = h_circles[3 * (size_t)k + j];
+    VAP_TRY(scene_upload(ctx, bytes));
+    const double *d = (const double *)ctx->scene.ptr;
+    PlanScene s{d, d + o_pv, d + o_circ, n_poly, n_circle};
+    const int ncell = g.nx * g.ny;
+    hipLaunchKernelGGL(k_plan_clearance, dim3((ncell + kPlanGridThreads - 1) / kPlanGridThreads), dim3(kPlanGridThreads), 0,
+                       ctx->stream, g, s, radius, margin, d_clearance, d_free);
+    HIP_TRY(hipGetLastError());
+    return VAP_OK;
+}
+
+}  // namespace vap
+
+extern "C" {
+
+int vap_plan_grid(vap_ctx *ctx, const double *h_field, int n_poly, const int *h_poly_start, const double *h_poly_xy, int n_circle,
+                  const double *h_circles, double cell, double radius, double margin, double *d_clearance, uint8_t *d_free,
+                  int *nx_out, int *ny_out)
+{
+    using namespace vap;
+    PlanGrid g{};
+    int nv = 0;
+    VAP_TRY(plan_check(h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, cell, radius, margin, g, nv));
+    if (nx_out) *nx_out = g.nx;
+    if (ny_out) *ny_out = g.ny;
+    if (!d_clearance && !d_free) return VAP_OK;                      // the shape only
+    VAP_TRY(vap_set_device(ctx));
+    return plan_launch_grid(ctx, g, nv, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, radius, margin, d_clearance, d_free);
+}
+
+int vap_plan_seeds(vap_ctx *ctx, int R, int W, const double *d_starts, const double *d_goals, const double *h_field, int n_poly,
+                   const int *h_poly_start, const double *h_poly_xy, int n_circle, const double *h_circles, double cell,
+                   double radius, double margin, int max_vertices, double *d_waypoints, double *d_length, uint32_t *d_flags,
+                   int *d_n_vertices, double *d_vertices, double *d_distance)
+{
+    using namespace vap;
+    if (R < 0) return vap_fail(VAP_ERR_INVALID, "bad shape R=%d", R);
+    if (W < 2) return vap_fail(VAP_ERR_INVALID, "W=%d: a route needs at least 2 waypoints", W);
+    if (W > kMaxWaypoints) return vap_fail(VAP_ERR_UNSUPPORTED, "W=%d exceeds %d", W, kMaxWaypoints);
+    if (d_vertices && max_vertices < 2) return vap_fail(VAP_ERR_INVALID, "max_vertices = %d: the vertex output needs at least 2", max_vertices);
+    if (R > 0 && (!d_starts || !d_goals || !d_waypoints)) return vap_fail(VAP_ERR_INVALID, "null starts / goals / waypoints");
+    PlanGrid g{};
+    int nv = 0;
+    VAP_TRY(plan_check(h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, cell, radius, margin, g, nv));
+    VAP_TRY(vap_set_device(ctx));
+    if (R == 0) return VAP_OK;
+
+    const size_t ncell = (size_t)g.nx * g.ny, nwords = (ncell + 31) / 32;
+    const size_t lds = (ncell < 2 ? 2 : ncell) * sizeof(double) + nwords * sizeof(uint32_t) + ((ncell + 15) & ~(size_t)15);
+    if (lds > 64 * 1024) {
+        // above the default limit the runtime has to grant the size; a device attribute that reports more than the default
+        // is the opt-in limit and is checked too
+        int lds_max = 0;
+        if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess) lds_max = 0;
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_plan_seeds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess || (lds_max > 64 * 1024 && lds + kPlanStaticLds > (size_t)lds_max))
+            return vap_fail(VAP_ERR_UNSUPPORTED, "a grid of %d x %d cells needs %zu bytes of LDS; the device gives a workgroup %d (%s)",
+                            g.nx, g.ny, lds + kPlanStaticLds, lds_max, hipGetErrorString(e));
+    }
+    const int blocks = R < kPlanMaxBlocks ? R : kPlanMaxBlocks;
+    VAP_TRY(ctx->ensure(ctx->plan_free, ncell));
+    VAP_TRY(ctx->ensure(ctx->plan_path, (size_t)blocks * ncell * sizeof(uint16_t)));
+    VAP_TRY(plan_launch_grid(ctx, g, nv, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, radius, margin, nullptr,
+                             (uint8_t *)ctx->plan_free.ptr));
+    SeedArgs a{};
+    a.g = g;
+    a.R = R;
+    a.W = W;
+    a.max_vertices = max_vertices;
+    a.starts = d_starts;
+    a.goals = d_goals;
+    a.free_mask = (const uint8_t *)ctx->plan_free.ptr;
+    a.path_ws = (uint16_t *)ctx->plan_path.ptr;
+    a.wp = d_waypoints;
+    a.length = d_length;
+    a.flags = d_flags;
+    a.n_vertices = d_n_vertices;
+    a.vertices = d_vertices;
+    a.distance = d_distance;
+    hipLaunchKernelGGL(k_plan_seeds, dim3((unsigned)blocks), dim3(kPlanThreads), lds, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    return VAP_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,175 @@
+"""Seed routes through a scene, planned on a grid on the device (vap_plan_grid, vap_plan_seeds, include/vap.h).
+
+``search.refine`` improves a route that is already roughly right: it draws candidates round a mean, coordinate by
+coordinate, and cannot get round an obstacle that is larger than its sigma.  This module gives it the route to start from.
+The robot is a disc of radius ``radius`` on a grid of ``cell``-sized squares over the scene's field box; a cell is free when
+the disc at its centre clears the walls, polygons and circles of the ``footprint.Scene`` by ``margin``; a shortest 8-connected
+path from the start's cell to the goal's is pulled taut by line of sight and resampled at equal arc into W waypoints.
+``seeds(...)["waypoints"]`` goes straight into ``refine(seeds=...)``.
+
+The disc stands in for the robot's footprint: ``circumscribed_radius`` is safe at every heading (and may not fit through a
+gap the robot can pass lengthways), ``inscribed_radius`` is necessary but not sufficient.  The seeds are not checked routes:
+the first and last segment join the exact start and goal to cell centres, so they may be off by half a cell, more when the
+start or goal had to be snapped to the nearest free cell (a robot parked against a wall).  ``refine`` does the checking.
+
+Units: feet, in the scene's frame.  At most 16384 cells (the distance field of a problem lives in one workgroup's LDS).
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .footprint import Scene, convex_polygon
+
+MAX_CELLS = 16384
+MAX_WAYPOINTS = 2048
+FLAGS = {"degenerate": _lib.FLAG_DEGENERATE, "noconverge": _lib.FLAG_NOCONVERGE, "snapped_start": _lib.PLAN_SNAPPED_START,
+         "snapped_goal": _lib.PLAN_SNAPPED_GOAL, "no_free": _lib.PLAN_NO_FREE, "unreachable": _lib.PLAN_UNREACHABLE,
+         "vertices_truncated": _lib.PLAN_VERTICES_TRUNCATED}
+
+
+def circumscribed_radius(footprint):
+    """The largest distance from the tracked point (the body origin) to a vertex of the footprint polygon, feet: a disc of
+    this radius contains the robot at every heading."""
+    v = convex_polygon(footprint, "footprint")
+    return float(np.sqrt((v * v).sum(axis=1)).max())
+
+
+def inscribed_radius(footprint):
+    """The smallest distance from the tracked point to an edge line of the footprint polygon, feet: the largest disc
+    round the tracked point inside the robot.  The tracked point must lie inside the footprint."""
+    v = convex_polygon(footprint, "footprint")
+    e = np.roll(v, -1, axis=0) - v
+    s = (v[:, 0] * e[:, 1] - v[:, 1] * e[:, 0]) / np.sqrt((e * e).sum(axis=1))   # inward distance of the origin per edge
+    if not (s > 0).all():
+        raise ValueError("the tracked point (the body origin) must lie inside the footprint")
+    return float(s.min())
+
+
+def grid_shape(scene, cell):
+    """(ny, nx) of the grid over ``scene``'s field box."""
+    ny, nx, _ = _check(scene, cell, 0.0, 0.0)
+    return ny, nx
+
+
+def _dptr(a):
+    return a.ctypes.data_as(_lib.dp) if a is not None and a.size else None
+
+
+def _check(scene, cell, radius, margin):
+    """Validate what both calls share; returns (ny, nx, the scene arguments of the C-ABI)."""
+    if not isinstance(scene, Scene):
+        raise TypeError("scene must be a footprint.Scene")
+    if scene.field is None:
+        raise ValueError("the planner needs a scene with a field box")
+    cell, radius, margin = float(cell), float(radius), float(margin)
+    if not (cell > 0 and np.isfinite(cell)):
+        raise ValueError(f"cell must be positive and finite (got {cell!r})")
+    if not (radius >= 0 and np.isfinite(radius)):
+        raise ValueError(f"radius must be >= 0 and finite (got {radius!r})")
+    if not np.isfinite(margin):
+        raise ValueError(f"margin must be finite (got {margin!r})")
+    f = scene.field
+    nx, ny = int(np.ceil((f[2] - f[0]) / cell)), int(np.ceil((f[3] - f[1]) / cell))
+    if nx * ny > MAX_CELLS:
+        raise ValueError(f"a grid of {nx} x {ny} cells: at most {MAX_CELLS} cells (use a larger cell)")
+    args = (_dptr(f), scene.n_polygons, scene.poly_start.ctypes.data_as(_lib.ip), _dptr(scene.poly_xy), scene.n_circles,
+            _dptr(scene.circles), cell, radius, margin)
+    return ny, nx, args
+
+
+def _context(dev, ctx):
+    if ctx is None:
+        ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    return ctx
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _buffers(out, shapes, dev):
+    res = {} if out is None else out
+    for k, (shp, dt) in shapes.items():
+        t = res.get(k)
+        if t is None or tuple(t.shape) != shp or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            res[k] = torch.empty(shp, dtype=dt, device=dev)
+    return res
+
+
+def clearance_grid(scene, cell, radius, margin=0.0, out=None, device=0, ctx=None):
+    """The planner's grid (vap_plan_grid): ``clearance`` (ny, nx) fp64, the disc's clearance at every cell centre, and
+    ``free`` (ny, nx) bool, clearance >= margin.  Row j, column i is the cell whose centre is (xmin + (i + 0.5) cell,
+    ymin + (j + 0.5) cell).  Device tensors on torch's current stream, not synchronised; ``out`` keeps the buffers."""
+    ny, nx, args = _check(scene, cell, radius, margin)
+    dev = torch.device("cuda", device)
+    res = _buffers(out, {"clearance": ((ny, nx), torch.float64), "free_u8": ((ny, nx), torch.uint8)}, dev)
+    ctx = _context(dev, ctx)
+    _lib.check(ctx._L.vap_plan_grid(ctx.handle, *args, _ptr(res["clearance"]), _ptr(res["free_u8"]), None, None), "vap_plan_grid")
+    res["free"] = res["free_u8"].view(torch.bool)
+    return res
+
+
+def _points(p, dev, what):
+    if isinstance(p, torch.Tensor):
+        t = p.to(device=dev, dtype=torch.float64)
+    else:
+        t = torch.as_tensor(np.ascontiguousarray(p, dtype=np.float64), device=dev)
+    single = t.dim() == 1
+    if single:
+        t = t.unsqueeze(0)
+    if t.dim() != 2 or t.shape[1] != 2:
+        raise ValueError(f"{what} must be (R, 2) or (2,), got {tuple(p.shape) if hasattr(p, 'shape') else p!r}")
+    return t.contiguous(), single
+
+
+def seeds(starts, goals, scene, waypoints, radius, cell=0.25, margin=0.0, max_vertices=64, vertices=False, distance=False,
+          out=None, device=0, ctx=None):
+    """Seed routes for R (start, goal) pairs (vap_plan_seeds).
+
+      starts, goals   (R, 2) or (2,) points in feet: device tensors (any float type, used as fp64) or host arrays
+      scene           a footprint.Scene with a field box
+      waypoints       W, the number of waypoints per route (2..2048); the first and last are the start and goal themselves
+      radius          the disc that stands in for the robot, feet (``circumscribed_radius(footprint)``)
+      cell, margin    the grid's cell size and the clearance a free cell needs, feet
+      vertices        also return the pulled path's vertices (R, max_vertices, 2), NaN behind the last
+      distance        also return every problem's distance field (R, ny, nx), +inf where blocked or unreached
+      out             optional dict of tensors of the shapes below to reuse
+    Returns a dict of device tensors: waypoints (R, W, 2) fp64, length (R,) (the polyline's, +inf on failure), flags (R,)
+    int32 (``plan.FLAGS``), n_vertices (R,) int32, feasible (R,) bool (a route was found), and the optional ones.  A failed
+    problem (no free cell, unreachable goal, non-finite point) has NaN waypoints.  A single pair gives (W, 2) and 0-d
+    tensors.  Work runs on torch's current stream and is not synchronised."""
+    W = int(waypoints)
+    if W != waypoints or W < 2:
+        raise ValueError(f"waypoints must be an integer >= 2 (got {waypoints!r})")
+    if W > MAX_WAYPOINTS:
+        raise ValueError(f"waypoints = {W}: at most {MAX_WAYPOINTS}")
+    max_vertices = int(max_vertices)
+    if vertices and max_vertices < 2:
+        raise ValueError(f"max_vertices must be >= 2 (got {max_vertices})")
+    ny, nx, args = _check(scene, cell, radius, margin)
+    given = [p.device for p in (starts, goals) if isinstance(p, torch.Tensor) and p.device.type == "cuda"]
+    dev = given[0] if given else torch.device("cuda", device)
+    starts, single = _points(starts, dev, "starts")
+    goals, _ = _points(goals, dev, "goals")
+    if starts.shape != goals.shape:
+        raise ValueError(f"starts and goals must have the same shape, got {tuple(starts.shape)} and {tuple(goals.shape)}")
+    R = int(starts.shape[0])
+    shapes = {"waypoints": ((R, W, 2), torch.float64), "length": ((R,), torch.float64), "flags": ((R,), torch.int32),
+              "n_vertices": ((R,), torch.int32)}
+    if vertices:
+        shapes["vertices"] = ((R, max_vertices, 2), torch.float64)
+    if distance:
+        shapes["distance"] = ((R, ny, nx), torch.float64)
+    res = _buffers(out, shapes, dev)
+    ctx = _context(dev, ctx)
+    _lib.check(ctx._L.vap_plan_seeds(
+        ctx.handle, R, W, _ptr(starts), _ptr(goals), *args, max_vertices, _ptr(res["waypoints"]), _ptr(res["length"]),
+        _ptr(res["flags"]), _ptr(res["n_vertices"]), _ptr(res["vertices"] if vertices else None),
+        _ptr(res["distance"] if distance else None)), "vap_plan_seeds")
+    res["feasible"] = res["n_vertices"] > 0
+    if single:
+        res = {k: v[0] for k, v in res.items()}
+    return res

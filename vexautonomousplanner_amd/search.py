@@ -262,6 +262,7 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
     waypoints').
 
       seeds          (R, W, 2) or (W, 2) waypoints in feet: the first mean, and candidate 0 of the first iteration
+                     (``plan.seeds(...)["waypoints"]`` gives seeds that already go round the scene's obstacles)
       sigma0         the first sigma in feet: a scalar, (W, 2) or (R, W, 2); the first and last waypoint are pinned unless
                      ``pin_ends=False``; ``pinned`` (W,) or (R, W) bool pins more
       footprint, scene   the robot's polygon and the footprint.Scene of ``footprint.clearance``; the margin is
