@@ -754,6 +754,66 @@ int vap_plan_seeds(vap_ctx *ctx, int R, int W, const double *d_starts, const dou
                    double radius, double margin, int max_vertices, double *d_waypoints, double *d_length, uint32_t *d_flags,
                    int *d_n_vertices, double *d_vertices, double *d_distance);
 
+/* ---- routes rasterised onto the planner's grid; seeds round a partner's routine -------------------------------------------
+ * vap_plan_seeds plans through the static scene and does not know that another robot drives there.  vap_plan_occupancy
+ * turns a batch of time-domain rows (a partner's routine, or my own candidates) into per-cell occupancy on vap_plan_grid's
+ * grid: which cell centres a disc of `radius` cannot stand on while the routes' footprints pass, and when.
+ * vap_plan_seeds_occupied plans with that occupancy blocked, per problem and within a time window.  The reference poses a
+ * footprint in one place only (gui/path.py:764-809 PathWidget.draw_rect) and never rasterises it.
+ *
+ *   rows      d_rows [B][capacity][8], d_counts, counts_stride: vap_footprint_clearance's (a count outside [0, capacity] is
+ *             clamped to it; columns 4, 6 and 7 are read).  n_b = the clamped count of route b.
+ *   footprint h_footprint [n_foot][2], body frame, convex, counter-clockwise, 3..16 vertices: vap_footprint_clearance's
+ *             validation.
+ *   grid      vap_plan_grid's, from h_field (required) and cell: nx, ny, the cell centres, nx * ny <= 16384.
+ *   pose      row r of a route: vertex v of the footprint at (x, y) + R(phi) v, phi = -heading, R(phi) = [[cos, -sin],
+ *             [sin, cos]], computed as x + (cos * v.x - sin * v.y), y + (sin * v.x + cos * v.y) in fp64, once per row.
+ *   clearance of cell centre p against that row: vap_plan_grid's polygon formula applied to the posed vertices (edges
+ *             a -> b between consecutive posed vertices, e = b - a, |e| = sqrt(e.x e.x + e.y e.y), s = ((p - a) x e) / |e|;
+ *             largest s > 0: sqrt of the smallest point-to-segment dx dx + dy dy, t = ((p - a) . e) * (1 / (e.x e.x +
+ *             e.y e.y)) clamped to [0, 1]; else the largest s), minus radius.  The row COVERS the cell iff clearance <
+ *             margin: a cell is covered exactly when vap_plan_grid with the posed footprint as a scene polygon would not
+ *             call it free on the polygon's account.  A row with a non-finite pose covers nothing and takes no part in
+ *             the minimum.  No FMA.
+ *   instants  row r stands at instant r + shift_rows (any sign).
+ *   outputs   per cell [ny][nx], over all B routes, any pointer may be NULL:
+ *             d_first  int32, the smallest covering instant; INT_MAX if never covered;
+ *             d_last   int32, the largest covering instant; INT_MIN if never covered;
+ *             d_count  int32, the number of covering (route, row) pairs;
+ *             d_min_clearance  fp64, the minimum of the clearance over every existing row of every route (covering or
+ *                      not); +inf without rows.
+ *   holds     hold_last != 0: a cell covered by row n_b - 1 of a route gets last = INT_MAX (the robot stays where its
+ *             routine ends, vap_footprint_conflicts' convention).  hold_first != 0: a cell covered by row 0 gets first =
+ *             INT_MIN (it stands there before it starts).  Holds do not change d_count.
+ *   B = 0, capacity = 0 or counts of 0 write the never-covered values.  With every output NULL the call only checks its
+ *   arguments and reports nx, ny (host ints, either may be NULL) without a context.
+ * VAP_ERR_INVALID: B < 0, capacity < 0, counts_stride < 1, a null row or count pointer with B > 0, a bad footprint, no field
+ * box, an empty or non-finite box, cell <= 0, radius < 0, a non-finite cell, radius or margin.  VAP_ERR_UNSUPPORTED: nx * ny
+ * above 16384; a capacity of INT_MAX rows or more; a shift_rows with which an instant could reach INT_MIN or INT_MAX (the
+ * hold values).  The arguments are checked before the context is touched.  Works on the context's stream and does not
+ * synchronise.  The outputs do not depend on scheduling: integer min, max and add and a minimum over the doubles' ordered
+ * bit patterns merge the routes, so two calls give the same bits, and B routes in one call give the elementwise min / max /
+ * sum / min of B calls.  VAP_OPT_FOOTPRINT_CULL governs culling here too (a box per 64 rows, a circle per row); outputs are
+ * bit for bit the same either way.  Discrete at the rows' dt: pass margin > 0 for a guard band.
+ *
+ * vap_plan_seeds_occupied is vap_plan_seeds with three more inputs: d_occ_first, d_occ_last [ny][nx] int32 (device; what
+ * vap_plan_occupancy wrote for the same field and cell) and d_windows [R][2] int32 = (t0, t1) per problem (device; NULL:
+ * every instant, (INT_MIN, INT_MAX)).  For problem r a cell is FREE iff it is free in the static scene and NOT
+ * (t0 < t1 and first < t1 and last >= t0): the window [t0, t1) meets [first, last].  [first, last] is the hull of the visits:
+ * a cell visited twice counts as blocked in between, which is conservative.  A window with t1 <= t0 is empty and blocks
+ * nothing.  Everything after the free mask (no free cell, distance, snapping, trace, pull, vertices, waypoints, flags,
+ * limits) is vap_plan_seeds' definition with this mask.  With both occupancy pointers NULL the call IS vap_plan_seeds, bit
+ * for bit (d_windows is ignored); exactly one of them NULL is VAP_ERR_INVALID. */
+int vap_plan_occupancy(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride, int n_foot,
+                       const double *h_footprint, const double *h_field, double cell, double radius, double margin, int shift_rows,
+                       int hold_first, int hold_last, int *d_first, int *d_last, int *d_count, double *d_min_clearance, int *nx_out,
+                       int *ny_out);
+int vap_plan_seeds_occupied(vap_ctx *ctx, int R, int W, const double *d_starts, const double *d_goals, const double *h_field,
+                            int n_poly, const int *h_poly_start, const double *h_poly_xy, int n_circle, const double *h_circles,
+                            double cell, double radius, double margin, int max_vertices, const int *d_occ_first,
+                            const int *d_occ_last, const int *d_windows, double *d_waypoints, double *d_length, uint32_t *d_flags,
+                            int *d_n_vertices, double *d_vertices, double *d_distance);
+
 #ifdef __cplusplus
 }
 #endif

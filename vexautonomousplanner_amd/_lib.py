@@ -65,6 +65,7 @@ EXPORTS = (
     "vap_profile_routes", "vap_time_profile_routes", "vap_time_insert_events", "vap_limit_rows_dtype",
     "vap_closest_points", "vap_route_closest", "vap_footprint_clearance", "vap_footprint_conflicts",
     "vap_tracking_rollouts", "vap_search_sample", "vap_search_update", "vap_plan_grid", "vap_plan_seeds",
+    "vap_plan_occupancy", "vap_plan_seeds_occupied",
 )
 
 
@@ -193,6 +194,9 @@ def lib():
     scene = [dp, C.c_int, ip, dp, C.c_int, dp, C.c_double, C.c_double, C.c_double]   # field .. circles, cell, radius, margin
     L.vap_plan_grid.argtypes = [vp] + scene + [vp, vp, ip, ip]
     L.vap_plan_seeds.argtypes = [vp, C.c_int, C.c_int, vp, vp] + scene + [C.c_int] + [vp] * 6
+    L.vap_plan_seeds_occupied.argtypes = [vp, C.c_int, C.c_int, vp, vp] + scene + [C.c_int] + [vp] * 3 + [vp] * 6
+    L.vap_plan_occupancy.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_int, dp, dp, C.c_double, C.c_double, C.c_double,
+                                     C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, ip, ip]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("vap_version", "vap_device_count"):

@@ -480,9 +480,20 @@ class BatchedTrajectoryGenerator:
     def plan_seeds(self, starts, goals, scene, waypoints, radius, **kw):
         """Seed routes round ``scene``'s obstacles for a disc of ``radius`` feet, one per (start, goal) pair, on this
         generator's device and context (vap_plan_seeds; see plan.seeds for the keyword arguments and the returned dict).
-        ``plan_seeds(...)["waypoints"]`` is what ``refine`` takes as ``seeds``."""
+        ``plan_seeds(...)["waypoints"]`` is what ``refine`` takes as ``seeds``.  ``occupancy=`` (what ``plan_occupancy``
+        returned) and ``windows=`` also keep the seeds off the cells a partner's routine occupies (vap_plan_seeds_occupied)."""
         from . import plan
         return plan.seeds(starts, goals, scene, waypoints, radius, device=self.device.index, ctx=self.ctx, **kw)
+
+    def plan_occupancy(self, tp, footprint, scene, cell, radius, **kw):
+        """The rows of ``tp`` — the dict ``time_profile``, ``insert_waits`` or ``tracking_rollouts`` returned — rasterised
+        onto the planner's grid over ``scene``'s field box: per cell the first and last instant and the number of rows at
+        which the posed ``footprint`` leaves a disc of ``radius`` less than ``margin`` (vap_plan_occupancy on this
+        generator's context; see plan.occupancy for the keyword arguments and the returned dict)."""
+        from . import plan
+        if tp["rows"].device != self.device:
+            raise ValueError(f"rows must be on {self.device}")
+        return plan.occupancy(tp, None, footprint, scene, cell, radius, device=self.device.index, ctx=self.ctx, **kw)
 
     def timing(self):
         return self.ctx.last_timing()

@@ -13,6 +13,10 @@
 //                     the whole distance field (8 B a cell, 128 KB at the 16384-cell limit), the free mask as bits (2 KB)
 //                     and, per cell, the byte of its allowed moves (16 KB) — both built once per workgroup, since every
 //                     problem shares the scene: 146 KB of gfx950's 160 KB, one workgroup per CU at the limit.
+//                     With an occupancy (vap_plan_seeds_occupied) the static bits stay where they are and a second
+//                     bitset (2 KB more: 148 KB) holds the problem's own mask, static bits minus the cells occupied in
+//                     the problem's window; it and the move bytes are rebuilt per problem, from LDS and 8 B a cell of
+//                     L2-resident occupancy.  Without one the kernel runs as before, on the static bits.
 //                       relax   Jacobi sweeps: a read phase (each thread keeps the new values of its <= 16 cells in
 //                               registers), a barrier, a write phase, and __syncthreads_or of "changed" as the second
 //                               barrier.  Neighbours are at constant offsets; the move byte has done the bounds, the
@@ -32,12 +36,11 @@
 #include <cstdint>
 #include <cstring>
 
-#include "vap_footprint.h"
 #include "vap_kernels.h"
+#include "vap_plan.h"
 
 namespace vap {
 
-constexpr int kPlanMaxCells = 16384;
 constexpr int kPlanThreads = 1024;
 constexpr int kPlanWaves = kPlanThreads / 64;
 constexpr int kPlanCellsPerThread = kPlanMaxCells / kPlanThreads;   // 16
@@ -47,11 +50,6 @@ constexpr int kPlanChunkPolys = 32;                                 // polygons 
 constexpr size_t kPlanStaticLds = 512;                              // bound on k_plan_seeds' static LDS
 constexpr double kPlanSqrt2 = 1.4142135623730951;
 
-struct PlanGrid {
-    double xmin, ymin, xmax, ymax, cell;
-    int nx, ny;
-};
-
 // Packed scene (fp64), the layouts of vap_footprint.hip:
 //   poly  [n_poly][4]   -, -, -, first vertex * 32 + vertex count (as a double)
 //   pv    [nv][8]       vertex x, y; -, -; the edge to the next vertex ex, ey; 1 / |e|^2; |e| = sqrt(ex ex + ey ey)
@@ -60,8 +58,6 @@ struct PlanScene {
     const double *poly, *pv, *circ;
     int n_poly, n_circle;
 };
-
-__device__ __forceinline__ double plan_centre(double lo, int i, double cell) { return lo + ((double)i + 0.5) * cell; }
 
 // the cell of a finite coordinate, clamped to the grid
 __device__ __forceinline__ int plan_cell_of(double x, double lo, double cell, int n)
@@ -132,6 +128,8 @@ struct SeedArgs {
     uint32_t *flags;
     int *n_vertices;
     double *vertices, *distance;
+    const int *occ_first, *occ_last;   // [ny][nx], both or neither
+    const int *windows;                // [R][2] (t0, t1), NULL: every instant
 };
 
 __device__ __forceinline__ bool plan_free(const uint32_t *fb, int idx) { return (fb[idx >> 5] >> (idx & 31)) & 1u; }
@@ -200,34 +198,10 @@ __device__ int plan_nearest_free(const PlanGrid &g, const uint32_t *fb, double p
     return bi;
 }
 
-__global__ __launch_bounds__(kPlanThreads) void k_plan_seeds(SeedArgs a)
+// Each cell's byte of allowed moves from the free bits; the whole workgroup calls it, and a barrier follows.
+__device__ __forceinline__ void plan_moves(const uint32_t *fb, uint8_t *mv, int nx, int ny)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char plan_lds[];
-    __shared__ double s_key[kPlanWaves];
-    __shared__ int s_idx[kPlanWaves];
-    __shared__ int s_n, s_best, s_fail;
-    const PlanGrid g = a.g;
-    const int tid = threadIdx.x, nx = g.nx, ny = g.ny, ncell = nx * ny, nwords = (ncell + 31) / 32;
-    double *d = reinterpret_cast<double *>(plan_lds);
-    uint32_t *fb = reinterpret_cast<uint32_t *>(d + (ncell < 2 ? 2 : ncell));   // the sums c_0, c_1 of a one-cell grid
-    uint8_t *mv = reinterpret_cast<uint8_t *>(fb + nwords);
-    // the eight moves in the header's order: offset in the grid and cost
-    const int off[8] = {1, nx, -1, -nx, nx + 1, nx - 1, -nx - 1, -nx + 1};
-    const double wa = g.cell, wd = g.cell * kPlanSqrt2;
-
-    // once per workgroup: the free bits, then each free cell's allowed moves
-    int any = 0;
-    for (int w = tid; w < nwords; w += kPlanThreads) {
-        uint32_t bits = 0;
-        for (int b = 0; b < 32; b++) {
-            const int idx = w * 32 + b;
-            if (idx < ncell && a.free_mask[idx]) bits |= 1u << b;
-        }
-        fb[w] = bits;
-        any |= bits != 0;
-    }
-    const bool any_free = __syncthreads_or(any);
-    for (int idx = tid; idx < ncell; idx += kPlanThreads) {
+    for (int idx = threadIdx.x; idx < nx * ny; idx += kPlanThreads) {
         unsigned m = 0;
         if (plan_free(fb, idx)) {
             const int j = idx / nx, i = idx - j * nx;
@@ -241,7 +215,41 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_seeds(SeedArgs a)
         }
         mv[idx] = (uint8_t)m;
     }
-    __syncthreads();
+}
+
+__global__ __launch_bounds__(kPlanThreads) void k_plan_seeds(SeedArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char plan_lds[];
+    __shared__ double s_key[kPlanWaves];
+    __shared__ int s_idx[kPlanWaves];
+    __shared__ int s_n, s_best, s_fail;
+    const PlanGrid g = a.g;
+    const int tid = threadIdx.x, nx = g.nx, ny = g.ny, ncell = nx * ny, nwords = (ncell + 31) / 32;
+    double *d = reinterpret_cast<double *>(plan_lds);
+    const bool occupied = a.occ_first != nullptr;
+    uint32_t *fbs = reinterpret_cast<uint32_t *>(d + (ncell < 2 ? 2 : ncell));  // the sums c_0, c_1 of a one-cell grid
+    uint32_t *fb = occupied ? fbs + nwords : fbs;                    // the problem's own mask
+    uint8_t *mv = reinterpret_cast<uint8_t *>(fb + nwords);
+    // the eight moves in the header's order: offset in the grid and cost
+    const int off[8] = {1, nx, -1, -nx, nx + 1, nx - 1, -nx - 1, -nx + 1};
+    const double wa = g.cell, wd = g.cell * kPlanSqrt2;
+
+    // once per workgroup: the static free bits; without an occupancy also each free cell's allowed moves
+    int any = 0;
+    for (int w = tid; w < nwords; w += kPlanThreads) {
+        uint32_t bits = 0;
+        for (int b = 0; b < 32; b++) {
+            const int idx = w * 32 + b;
+            if (idx < ncell && a.free_mask[idx]) bits |= 1u << b;
+        }
+        fbs[w] = bits;
+        any |= bits != 0;
+    }
+    bool any_free = __syncthreads_or(any);
+    if (!occupied) {
+        plan_moves(fb, mv, nx, ny);
+        __syncthreads();
+    }
 
     uint16_t *path = a.path_ws + (size_t)blockIdx.x * (size_t)ncell;
 #pragma unroll 1
@@ -251,6 +259,24 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_seeds(SeedArgs a)
         uint32_t flags = 0;
         bool ok = true;
         int sc = 0, gc = 0, nvtx = 0;
+        if (occupied) {                                              // the static bits minus the cells occupied in (t0, t1)
+            const int t0 = a.windows ? a.windows[(size_t)r * 2] : INT_MIN, t1 = a.windows ? a.windows[(size_t)r * 2 + 1] : INT_MAX;
+            int some = 0;
+            for (int w = tid; w < nwords; w += kPlanThreads) {
+                uint32_t bits = fbs[w];
+                if (t0 < t1) {
+                    for (uint32_t left = bits; left; left &= left - 1) {
+                        const int b = __ffs(left) - 1, idx = w * 32 + b;
+                        if (a.occ_first[idx] < t1 && a.occ_last[idx] >= t0) bits &= ~(1u << b);
+                    }
+                }
+                fb[w] = bits;
+                some |= bits != 0;
+            }
+            any_free = __syncthreads_or(some);
+            plan_moves(fb, mv, nx, ny);
+            __syncthreads();
+        }
         if (!(isfinite(sx) && isfinite(sy) && isfinite(gx) && isfinite(gy))) {
             flags |= VAP_FLAG_DEGENERATE;
             ok = false;
@@ -438,16 +464,8 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_seeds(SeedArgs a)
     }
 }
 
-// The arguments both calls share, checked on the host before anything touches the device; fills the grid.
-static int plan_check(const double *h_field, int n_poly, const int *h_poly_start, const double *h_poly_xy, int n_circle,
-                      const double *h_circles, double cell, double radius, double margin, PlanGrid &g, int &nv)
+int plan_grid_of(const double *h_field, double cell, PlanGrid &g)
 {
-    if (!(cell > 0.0) || !std::isfinite(cell)) return vap_fail(VAP_ERR_INVALID, "cell must be positive and finite (got %g)", cell);
-    if (!(radius >= 0.0) || !std::isfinite(radius)) return vap_fail(VAP_ERR_INVALID, "radius must be >= 0 and finite (got %g)", radius);
-    if (!std::isfinite(margin)) return vap_fail(VAP_ERR_INVALID, "margin must be finite");
-    if (!h_field) return vap_fail(VAP_ERR_INVALID, "the planner needs a scene with a field box");
-    double scale = 0.0;
-    VAP_TRY(check_scene(h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, scale, nv));
     const double fx = std::ceil((h_field[2] - h_field[0]) / cell), fy = std::ceil((h_field[3] - h_field[1]) / cell);
     if (!(fx >= 1.0) || !(fy >= 1.0) || !std::isfinite(fx) || !std::isfinite(fy))
         return vap_fail(VAP_ERR_INVALID, "the field box over cell %g gives no grid", cell);
@@ -461,6 +479,19 @@ static int plan_check(const double *h_field, int n_poly, const int *h_poly_start
     g.nx = (int)fx;
     g.ny = (int)fy;
     return VAP_OK;
+}
+
+// The arguments both calls share, checked on the host before anything touches the device; fills the grid.
+static int plan_check(const double *h_field, int n_poly, const int *h_poly_start, const double *h_poly_xy, int n_circle,
+                      const double *h_circles, double cell, double radius, double margin, PlanGrid &g, int &nv)
+{
+    if (!(cell > 0.0) || !std::isfinite(cell)) return vap_fail(VAP_ERR_INVALID, "cell must be positive and finite (got %g)", cell);
+    if (!(radius >= 0.0) || !std::isfinite(radius)) return vap_fail(VAP_ERR_INVALID, "radius must be >= 0 and finite (got %g)", radius);
+    if (!std::isfinite(margin)) return vap_fail(VAP_ERR_INVALID, "margin must be finite");
+    if (!h_field) return vap_fail(VAP_ERR_INVALID, "the planner needs a scene with a field box");
+    double scale = 0.0;
+    VAP_TRY(check_scene(h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, scale, nv));
+    return plan_grid_of(h_field, cell, g);
 }
 
 // Pack and upload the scene, then the clearance kernel over the grid.
@@ -516,7 +547,20 @@ int vap_plan_seeds(vap_ctx *ctx, int R, int W, const double *d_starts, const dou
                    double radius, double margin, int max_vertices, double *d_waypoints, double *d_length, uint32_t *d_flags,
                    int *d_n_vertices, double *d_vertices, double *d_distance)
 {
+    return vap_plan_seeds_occupied(ctx, R, W, d_starts, d_goals, h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, cell,
+                                   radius, margin, max_vertices, nullptr, nullptr, nullptr, d_waypoints, d_length, d_flags,
+                                   d_n_vertices, d_vertices, d_distance);
+}
+
+int vap_plan_seeds_occupied(vap_ctx *ctx, int R, int W, const double *d_starts, const double *d_goals, const double *h_field,
+                            int n_poly, const int *h_poly_start, const double *h_poly_xy, int n_circle, const double *h_circles,
+                            double cell, double radius, double margin, int max_vertices, const int *d_occ_first,
+                            const int *d_occ_last, const int *d_windows, double *d_waypoints, double *d_length, uint32_t *d_flags,
+                            int *d_n_vertices, double *d_vertices, double *d_distance)
+{
     using namespace vap;
+    if ((d_occ_first == nullptr) != (d_occ_last == nullptr))
+        return vap_fail(VAP_ERR_INVALID, "the occupancy needs both its first and its last instants (or neither)");
     if (R < 0) return vap_fail(VAP_ERR_INVALID, "bad shape R=%d", R);
     if (W < 2) return vap_fail(VAP_ERR_INVALID, "W=%d: a route needs at least 2 waypoints", W);
     if (W > kMaxWaypoints) return vap_fail(VAP_ERR_UNSUPPORTED, "W=%d exceeds %d", W, kMaxWaypoints);
@@ -529,7 +573,8 @@ int vap_plan_seeds(vap_ctx *ctx, int R, int W, const double *d_starts, const dou
     if (R == 0) return VAP_OK;
 
     const size_t ncell = (size_t)g.nx * g.ny, nwords = (ncell + 31) / 32;
-    const size_t lds = (ncell < 2 ? 2 : ncell) * sizeof(double) + nwords * sizeof(uint32_t) + ((ncell + 15) & ~(size_t)15);
+    const size_t lds = (ncell < 2 ? 2 : ncell) * sizeof(double) + (d_occ_first ? 2 : 1) * nwords * sizeof(uint32_t) +
+                       ((ncell + 15) & ~(size_t)15);
     if (lds > 64 * 1024) {
         // above the default limit the runtime has to grant the size; a device attribute that reports more than the default
         // is the opt-in limit and is checked too
@@ -560,6 +605,9 @@ int vap_plan_seeds(vap_ctx *ctx, int R, int W, const double *d_starts, const dou
     a.n_vertices = d_n_vertices;
     a.vertices = d_vertices;
     a.distance = d_distance;
+    a.occ_first = d_occ_first;
+    a.occ_last = d_occ_last;
+    a.windows = d_occ_first ? d_windows : nullptr;
     hipLaunchKernelGGL(k_plan_seeds, dim3((unsigned)blocks), dim3(kPlanThreads), lds, ctx->stream, a);
     HIP_TRY(hipGetLastError());
     return VAP_OK;

@@ -1,4 +1,5 @@
-"""Seed routes through a scene, planned on a grid on the device (vap_plan_grid, vap_plan_seeds, include/vap.h).
+"""Seed routes through a scene, planned on a grid on the device (vap_plan_grid, vap_plan_seeds, vap_plan_occupancy,
+vap_plan_seeds_occupied, include/vap.h).
 
 ``search.refine`` improves a route that is already roughly right: it draws candidates round a mean, coordinate by
 coordinate, and cannot get round an obstacle that is larger than its sigma.  This module gives it the route to start from.
@@ -12,6 +13,10 @@ gap the robot can pass lengthways), ``inscribed_radius`` is necessary but not su
 the first and last segment join the exact start and goal to cell centres, so they may be off by half a cell, more when the
 start or goal had to be snapped to the nearest free cell (a robot parked against a wall).  ``refine`` does the checking.
 
+A partner's routine is no part of the scene: ``occupancy`` rasterises its time-domain rows onto the same grid (per cell the
+first and last instant at which its footprint leaves the disc less than ``margin``), and ``seeds(occupancy=..., windows=...)``
+keeps each problem off the cells occupied within its window of instants.
+
 Units: feet, in the scene's frame.  At most 16384 cells (the distance field of a problem lives in one workgroup's LDS).
 """
 import ctypes as C
@@ -20,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .footprint import Scene, convex_polygon
+from .footprint import Scene, _ccw_polygon, _side, convex_polygon
 
 MAX_CELLS = 16384
 MAX_WAYPOINTS = 2048
@@ -125,9 +130,54 @@ def _points(p, dev, what):
     return t.contiguous(), single
 
 
+INT_MIN, INT_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def occupancy(rows, counts, footprint, scene, cell, radius, margin=0.0, shift_rows=0, hold_first=False, hold_last=True,
+              min_clearance=False, out=None, device=0, ctx=None, cull=True):
+    """Time-domain rows rasterised onto the planner's grid (vap_plan_occupancy).
+
+      rows, counts   the dict ``time_profile`` / ``insert_waits`` / ``tracking.rollouts(executed=True)`` returned (then
+                     ``counts`` is None), or (B, capacity, 8) fp64 rows with their (B, k) or (B,) counts as
+                     ``footprint.clearance`` takes them; (n, 8) rows with counts None for a single trajectory
+      footprint      (n, 2) body-frame polygon of the robot that drives the rows, counter-clockwise, feet
+      scene, cell    the grid: ``scene``'s field box over ``cell``-sized squares, as ``clearance_grid`` lays it out
+      radius, margin the disc that will be planned (mine) and the clearance it wants: a row covers a cell when the disc at
+                     the cell's centre clears the posed footprint by less than ``margin``
+      shift_rows     row r stands at instant r + shift_rows
+      hold_first     the robot stands at its first pose before instant shift_rows: first = INT_MIN where row 0 covers
+      hold_last      it stays at its last pose: last = INT_MAX where the last row covers
+      min_clearance  also return the smallest clearance of every cell over all rows (+inf without rows)
+      out            optional dict of tensors of the shapes below to reuse; cull: VAP_OPT_FOOTPRINT_CULL (the same bits)
+    Returns a dict of (ny, nx) device tensors: first, last (int32; INT_MAX / INT_MIN where never covered), count (int32,
+    covering rows), blocked (bool: covered at some instant), and min_clearance (fp64) if asked.  All B routes go into the
+    one grid.  Work runs on torch's current stream and is not synchronised."""
+    if isinstance(rows, dict):
+        if counts is not None:
+            raise ValueError("counts comes with the dict of rows")
+        rows, counts = rows["rows"], rows["counts"]
+    ny, nx, _ = _check(scene, cell, radius, margin)
+    foot = _ccw_polygon(footprint, "footprint")
+    rows, counts, _, dev = _side(rows, counts, None, device, "occupancy")
+    shift_rows = int(shift_rows)
+    shapes = {"first": ((ny, nx), torch.int32), "last": ((ny, nx), torch.int32), "count": ((ny, nx), torch.int32)}
+    if min_clearance:
+        shapes["min_clearance"] = ((ny, nx), torch.float64)
+    res = _buffers(out, shapes, dev)
+    ctx = _context(dev, ctx)
+    ctx.set_option(_lib.OPT_FOOTPRINT_CULL, 1 if cull else 0)
+    _lib.check(ctx._L.vap_plan_occupancy(
+        ctx.handle, int(rows.shape[0]), int(rows.shape[1]), _ptr(rows), _ptr(counts), int(counts.shape[1]), len(foot), _dptr(foot),
+        _dptr(scene.field), float(cell), float(radius), float(margin), shift_rows, int(bool(hold_first)), int(bool(hold_last)),
+        _ptr(res["first"]), _ptr(res["last"]), _ptr(res["count"]), _ptr(res["min_clearance"] if min_clearance else None), None,
+        None), "vap_plan_occupancy")
+    res["blocked"] = res["first"] <= res["last"]
+    return res
+
+
 def seeds(starts, goals, scene, waypoints, radius, cell=0.25, margin=0.0, max_vertices=64, vertices=False, distance=False,
-          out=None, device=0, ctx=None):
-    """Seed routes for R (start, goal) pairs (vap_plan_seeds).
+          out=None, device=0, ctx=None, occupancy=None, windows=None):
+    """Seed routes for R (start, goal) pairs (vap_plan_seeds; with an occupancy vap_plan_seeds_occupied).
 
       starts, goals   (R, 2) or (2,) points in feet: device tensors (any float type, used as fp64) or host arrays
       scene           a footprint.Scene with a field box
@@ -137,6 +187,10 @@ def seeds(starts, goals, scene, waypoints, radius, cell=0.25, margin=0.0, max_ve
       vertices        also return the pulled path's vertices (R, max_vertices, 2), NaN behind the last
       distance        also return every problem's distance field (R, ny, nx), +inf where blocked or unreached
       out             optional dict of tensors of the shapes below to reuse
+      occupancy       what ``occupancy(...)`` returned for the same scene and cell (or a (first, last) pair of (ny, nx)
+                      int32 device tensors): the cells a partner occupies, and when, are not free
+      windows         (R, 2) or (2,) integers (t0, t1): problem r keeps off the cells occupied at some instant of
+                      [t0, t1); None: at any instant.  Needs ``occupancy``
     Returns a dict of device tensors: waypoints (R, W, 2) fp64, length (R,) (the polyline's, +inf on failure), flags (R,)
     int32 (``plan.FLAGS``), n_vertices (R,) int32, feasible (R,) bool (a route was found), and the optional ones.  A failed
     problem (no free cell, unreachable goal, non-finite point) has NaN waypoints.  A single pair gives (W, 2) and 0-d
@@ -164,11 +218,32 @@ def seeds(starts, goals, scene, waypoints, radius, cell=0.25, margin=0.0, max_ve
     if distance:
         shapes["distance"] = ((R, ny, nx), torch.float64)
     res = _buffers(out, shapes, dev)
-    ctx = _context(dev, ctx)
-    _lib.check(ctx._L.vap_plan_seeds(
-        ctx.handle, R, W, _ptr(starts), _ptr(goals), *args, max_vertices, _ptr(res["waypoints"]), _ptr(res["length"]),
-        _ptr(res["flags"]), _ptr(res["n_vertices"]), _ptr(res["vertices"] if vertices else None),
-        _ptr(res["distance"] if distance else None)), "vap_plan_seeds")
+    outs = (_ptr(res["waypoints"]), _ptr(res["length"]), _ptr(res["flags"]), _ptr(res["n_vertices"]),
+            _ptr(res["vertices"] if vertices else None), _ptr(res["distance"] if distance else None))
+    if occupancy is None:
+        if windows is not None:
+            raise ValueError("windows needs an occupancy")
+        ctx = _context(dev, ctx)
+        _lib.check(ctx._L.vap_plan_seeds(ctx.handle, R, W, _ptr(starts), _ptr(goals), *args, max_vertices, *outs), "vap_plan_seeds")
+    else:
+        first, last = (occupancy["first"], occupancy["last"]) if isinstance(occupancy, dict) else occupancy
+        for t in (first, last):
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.int32 or tuple(t.shape) != (ny, nx):
+                raise ValueError(f"occupancy must be ({ny}, {nx}) int32 tensors on {dev} (plan.occupancy with the same scene and cell)")
+        first, last = first.contiguous(), last.contiguous()
+        if windows is not None:
+            if isinstance(windows, torch.Tensor):
+                windows = windows.to(device=dev, dtype=torch.int32)
+            else:
+                windows = torch.as_tensor(np.ascontiguousarray(windows, dtype=np.int32), device=dev)
+            if windows.dim() == 1:
+                windows = windows.unsqueeze(0).expand(R, 2)
+            if tuple(windows.shape) != (R, 2):
+                raise ValueError(f"windows must be ({R}, 2) or (2,), got {tuple(windows.shape)}")
+            windows = windows.contiguous()
+        ctx = _context(dev, ctx)
+        _lib.check(ctx._L.vap_plan_seeds_occupied(ctx.handle, R, W, _ptr(starts), _ptr(goals), *args, max_vertices, _ptr(first),
+                                                  _ptr(last), _ptr(windows), *outs), "vap_plan_seeds_occupied")
     res["feasible"] = res["n_vertices"] > 0
     if single:
         res = {k: v[0] for k, v in res.items()}
