@@ -814,6 +814,57 @@ int vap_plan_seeds_occupied(vap_ctx *ctx, int R, int W, const double *d_starts, 
                             const int *d_occ_last, const int *d_windows, double *d_waypoints, double *d_length, uint32_t *d_flags,
                             int *d_n_vertices, double *d_vertices, double *d_distance);
 
+/* ---- a routine's travel matrix and its visiting order -----------------------------------------------------------------------
+ * A routine is a start and a handful of sites, not one (start, goal) pair.  vap_plan_travel plans every ordered pair of P
+ * points of a problem at the price of P distance fields; vap_plan_order finds the cheapest order to visit the sites in from
+ * any cost matrix (the travel matrix, or what the caller made of it on the device: seconds, dwell times, forbidden legs).
+ * The reference keeps a routine as a hand-ordered list of nodes (gui/path.py) and has neither.
+ *
+ * vap_plan_travel: d_points [R][P][2] fp64 on the device, 2 <= P <= 16; the scene, cell, radius and margin of vap_plan_seeds;
+ * d_occ_first, d_occ_last, d_windows [R][2] of vap_plan_seeds_occupied (both occupancy pointers NULL: the static scene;
+ * problem r's one window holds for all its pairs).  For a != b, entry (r, a, b) of every output IS what vap_plan_seeds (or,
+ * with an occupancy, vap_plan_seeds_occupied) gives for start = point a, goal = point b of problem r, bit for bit: its
+ * snapping, trace, pull, vertices, waypoints, flags and failures (vap_plan_seeds without its vertex output: max_vertices is
+ * accepted and cuts nothing, VAP_PLAN_VERTICES_TRUNCATED is never set).  The diagonal (r, b, b) has travel 0, flags 0,
+ * n_vertices 0 and every waypoint equal to point b's own bits, whatever they are.  The matrix is NOT symmetric: the trace
+ * breaks ties by move order, so (a, b) and (b, a) may take different cells; nothing is mirrored.  The field of goal b is
+ * relaxed once and serves every start, which is all that distinguishes this call from P (P - 1) problems of vap_plan_seeds.
+ *   d_travel      [R][P][P] fp64, the pulled polyline's length (vap_plan_seeds' d_length), +inf on failure; required
+ *   d_flags       [R][P][P] uint32, d_n_vertices [R][P][P] int32, d_waypoints [R][P][P][W][2] fp64: each may be NULL; W is
+ *                 read only with d_waypoints
+ * VAP_ERR_INVALID: vap_plan_seeds' scene, cell, radius and margin errors, exactly one occupancy pointer NULL, P < 2, R < 0, a
+ * null point or travel pointer with R > 0, W < 2 with d_waypoints.  VAP_ERR_UNSUPPORTED: P > 16, nx * ny above 16384, W above
+ * 2048 with d_waypoints, R * P above INT_MAX, a device whose LDS cannot hold the grid.  The arguments are checked before the
+ * context is touched.  R = 0 is a no-op.  Works on the context's stream and does not synchronise; two calls give the same bits.
+ *
+ * vap_plan_order: d_cost [R][P][P] fp64 on the device, c[a][b] the cost of going from point a to point b; point 0 is where
+ * the routine starts, points 1 .. M = P - 1 are the sites, 1 <= M <= 10; the diagonal and column 0 are not read.  An entry
+ * that is NaN or -inf counts as +inf (a forbidden leg).
+ *   end       -1: the routine may end at any site; 1 .. M: it ends at that site.
+ *   before    d_before [R][P] uint32 or NULL: bit j - 1 of before[k] says site j must have been visited before site k.
+ *             Entry 0 and bits >= M are ignored.
+ *   f         over site sets S (bit j - 1 = site j): f[{j}][j] = c[0][j] if before[j] = 0, else +inf.  For j in S, |S| > 1:
+ *             if before[j] is a subset of S \ {j}, f[S][j] = the minimum over i in S \ {j}, taken in increasing i under a
+ *             strict <, of fl(f[S \ {j}][i] + c[i][j]), and the parent of (S, j) is the i that won; otherwise +inf.
+ *   last      with F the full set: `end` if given, else the j with the smallest f[F][j], the lowest j on a tie.
+ *   outputs   d_total [R] = f[F][last]; d_order [R][M] int32, the sites in visiting order, from `last` back along the
+ *             parents; d_flags [R] uint32, optional.  A total of +inf (every leg forbidden, a precedence cycle, an `end`
+ *             that something must follow) is infeasible: order all -1, total +inf, VAP_ORDER_INFEASIBLE.
+ * fl(x + c) is monotone in x, so the total is the smallest left-to-right sum c[0][o1] + c[o1][o2] + ... over all admissible
+ * permutations, bit for bit; only the choice among equal totals rests on the two tie rules.  One workgroup per problem at a
+ * time with f in LDS (2^M * M * 8 bytes).  VAP_ERR_INVALID: P < 2, R < 0, end outside {-1, 1 .. M}, a null cost, order or
+ * total pointer with R > 0.  VAP_ERR_UNSUPPORTED: P > 11.  The arguments are checked before the context is touched.  R = 0 is a
+ * no-op.  Works on the context's stream and does not synchronise; no atomics: two calls give the same bits. */
+#define VAP_ORDER_INFEASIBLE 512u
+#define VAP_PLAN_TRAVEL_MAX_POINTS 16
+#define VAP_PLAN_ORDER_MAX_SITES 10
+int vap_plan_travel(vap_ctx *ctx, int R, int P, int W, const double *d_points, const double *h_field, int n_poly,
+                    const int *h_poly_start, const double *h_poly_xy, int n_circle, const double *h_circles, double cell,
+                    double radius, double margin, int max_vertices, const int *d_occ_first, const int *d_occ_last,
+                    const int *d_windows, double *d_travel, uint32_t *d_flags, int *d_n_vertices, double *d_waypoints);
+int vap_plan_order(vap_ctx *ctx, int R, int P, const double *d_cost, int end, const uint32_t *d_before, int *d_order, double *d_total,
+                   uint32_t *d_flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,8 @@ FLAG_TRUNCATED = 2
 FLAG_NOCONVERGE = 4
 FLAG_BAD_ROUTE = 8
 PLAN_SNAPPED_START, PLAN_SNAPPED_GOAL, PLAN_NO_FREE, PLAN_UNREACHABLE, PLAN_VERTICES_TRUNCATED = 16, 32, 64, 128, 256
+ORDER_INFEASIBLE = 512
+PLAN_TRAVEL_MAX_POINTS, PLAN_ORDER_MAX_SITES = 16, 10
 T_FIT, T_LUT, T_SAMPLE, T_VELOCITY, T_TOTAL, T_COUNT = 0, 1, 2, 3, 4, 8
 OPT_VELOCITY_KERNEL = 0
 OPT_TIME_DOMAIN_RESIDUAL = 3
@@ -65,7 +67,7 @@ EXPORTS = (
     "vap_profile_routes", "vap_time_profile_routes", "vap_time_insert_events", "vap_limit_rows_dtype",
     "vap_closest_points", "vap_route_closest", "vap_footprint_clearance", "vap_footprint_conflicts",
     "vap_tracking_rollouts", "vap_search_sample", "vap_search_update", "vap_plan_grid", "vap_plan_seeds",
-    "vap_plan_occupancy", "vap_plan_seeds_occupied",
+    "vap_plan_occupancy", "vap_plan_seeds_occupied", "vap_plan_travel", "vap_plan_order",
 )
 
 
@@ -197,6 +199,8 @@ def lib():
     L.vap_plan_seeds_occupied.argtypes = [vp, C.c_int, C.c_int, vp, vp] + scene + [C.c_int] + [vp] * 3 + [vp] * 6
     L.vap_plan_occupancy.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_int, dp, dp, C.c_double, C.c_double, C.c_double,
                                      C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, ip, ip]
+    L.vap_plan_travel.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp] + scene + [C.c_int] + [vp] * 3 + [vp] * 4
+    L.vap_plan_order.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("vap_version", "vap_device_count"):

@@ -485,6 +485,14 @@ class BatchedTrajectoryGenerator:
         from . import plan
         return plan.seeds(starts, goals, scene, waypoints, radius, device=self.device.index, ctx=self.ctx, **kw)
 
+    def plan_routine(self, points, scene, waypoints, radius, **kw):
+        """The cheapest order to visit the sites ``points[1:]`` in from ``points[0]`` through ``scene``, and the seed route of
+        every leg in that order, on this generator's device and context (vap_plan_travel, vap_plan_order; see plan.routine
+        for the keyword arguments and the returned dict).  ``plan_routine(...)["legs"].reshape(-1, W, 2)`` is what ``refine``
+        takes as ``seeds``."""
+        from . import plan
+        return plan.routine(points, scene, waypoints, radius, device=self.device.index, ctx=self.ctx, **kw)
+
     def plan_occupancy(self, tp, footprint, scene, cell, radius, **kw):
         """The rows of ``tp`` — the dict ``time_profile``, ``insert_waits`` or ``tracking_rollouts`` returned — rasterised
         onto the planner's grid over ``scene``'s field box: per cell the first and last instant and the number of rows at

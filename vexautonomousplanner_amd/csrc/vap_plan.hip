@@ -1,4 +1,4 @@
-// vap_plan.hip — seed routes through a scene on a grid (vap_plan_grid, vap_plan_seeds).
+// vap_plan.hip — seed routes through a scene on a grid (vap_plan_grid, vap_plan_seeds, vap_plan_travel).
 //
 // The route search refines a route that is already roughly right; this file finds one.  The robot is a disc of radius
 // rho on a grid over the field box; a cell is free when the disc at its centre clears the walls, polygons and circles by
@@ -31,6 +31,11 @@
 //                       resample  segment lengths a thread each, their running sum on one lane (a fixed order), then a
 //                               thread per waypoint.  The sums live where the distance field was.
 //                     No float atomics: two calls give the same bits.
+//   k_plan_travel     all ordered pairs of a problem's P points: the same workgroups over the R x P (problem, goal) items.
+//                     An item relaxes its goal's field once and keeps it in LDS while every start is snapped, traced,
+//                     pulled and resampled against it — the stages above, shared as __device__ functions — so the sums
+//                     live in the workgroup's global workspace, in front of its cell list.  The mask and the moves are
+//                     rebuilt only when the workgroup's next item belongs to another problem (and only with an occupancy).
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -217,6 +222,200 @@ __device__ __forceinline__ void plan_moves(const uint32_t *fb, uint8_t *mv, int 
     }
 }
 
+// The stages of one problem, shared by k_plan_seeds and k_plan_travel.  `off` holds the eight moves in the header's order as
+// offsets in the grid; an axis move costs wa, a diagonal one wd.
+
+// The problem's own mask: the static bits minus the cells occupied in [t0, t1).  The whole workgroup calls it; returns
+// whether a cell is free at all (a barrier).
+__device__ __forceinline__ bool plan_window_mask(const uint32_t *fbs, uint32_t *fb, int nwords, const int *occ_first,
+                                                 const int *occ_last, int t0, int t1)
+{
+    int some = 0;
+    for (int w = threadIdx.x; w < nwords; w += kPlanThreads) {
+        uint32_t bits = fbs[w];
+        if (t0 < t1) {
+            for (uint32_t left = bits; left; left &= left - 1) {
+                const int b = __ffs(left) - 1, idx = w * 32 + b;
+                if (occ_first[idx] < t1 && occ_last[idx] >= t0) bits &= ~(1u << b);
+            }
+        }
+        fb[w] = bits;
+        some |= bits != 0;
+    }
+    return __syncthreads_or(some);
+}
+
+// relax: d[gc] = 0, d[v] = min over allowed moves v -> u of fl(d[u] + w), by Jacobi sweeps.  The whole workgroup calls it;
+// returns whether a sweep changed nothing within ncell sweeps.
+__device__ __forceinline__ bool plan_relax(double *d, const uint8_t *mv, const int (&off)[8], double wa, double wd, int ncell, int gc)
+{
+    const int tid = threadIdx.x;
+    for (int idx = tid; idx < ncell; idx += kPlanThreads) d[idx] = idx == gc ? 0.0 : INFINITY;
+    __syncthreads();
+    bool converged = false;
+#pragma unroll 1
+    for (int sweep = 0; sweep < ncell && !converged; sweep++) {
+        double nv[kPlanCellsPerThread];
+#pragma unroll
+        for (int c = 0; c < kPlanCellsPerThread; c++) {
+            const int idx = tid + c * kPlanThreads;
+            nv[c] = INFINITY;
+            if (idx < ncell) {
+                const unsigned m = mv[idx];
+                double best = INFINITY;
+                if (m) {
+#pragma unroll
+                    for (int k = 0; k < 8; k++)
+                        if (m & (1u << k)) best = fmin(best, d[idx + off[k]] + (k < 4 ? wa : wd));
+                }
+                nv[c] = best;
+            }
+        }
+        __syncthreads();                                             // every read of this sweep is done
+        int changed = 0;
+#pragma unroll
+        for (int c = 0; c < kPlanCellsPerThread; c++) {
+            const int idx = tid + c * kPlanThreads;
+            if (idx < ncell && nv[c] < d[idx]) {
+                d[idx] = nv[c];
+                changed = 1;
+            }
+        }
+        converged = !__syncthreads_or(changed);
+    }
+    return converged;
+}
+
+// trace: from cell sc to the allowed neighbour with the smallest fl(d[u] + w), the first on a tie, until d = 0.  One lane
+// calls it; returns the number of cells written to path, `fail` when the walk ended above d = 0.
+__device__ __forceinline__ int plan_trace(const double *d, const uint8_t *mv, const int (&off)[8], double wa, double wd, int ncell,
+                                          int sc, uint16_t *path, int &fail)
+{
+    int cur = sc, n = 0;
+    path[n++] = (uint16_t)cur;
+    while (d[cur] > 0.0 && n < ncell) {
+        const unsigned m = mv[cur];
+        double best = INFINITY;
+        int bu = -1;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            if (!(m & (1u << k))) continue;
+            const double c = d[cur + off[k]] + (k < 4 ? wa : wd);
+            if (c < best) { best = c; bu = cur + off[k]; }
+        }
+        if (bu < 0) break;
+        cur = bu;
+        path[n++] = (uint16_t)cur;
+    }
+    fail = d[cur] > 0.0;
+    return n;
+}
+
+// pull: from anchor a the largest b whose cell is visible from a's, else a + 1.  The whole workgroup calls it; the pulled
+// list overwrites the front of the traced one.  Returns the number of pulled cells.
+__device__ __forceinline__ int plan_pull(const uint32_t *fb, int nx, uint16_t *path, int n, int *s_best)
+{
+    const int tid = threadIdx.x;
+    int nv = 1, anchor = 0;
+    while (anchor < n - 1) {
+        if (tid == 0) *s_best = anchor + 1;
+        __syncthreads();
+        const int ca = path[anchor];
+        int bb = anchor + 1;
+        for (int base = n - 1; base > anchor + 1; base -= kPlanThreads) {
+            const int b = base - tid;
+            if (b > anchor + 1 && plan_visible(fb, nx, ca, path[b])) atomicMax(s_best, b);
+            __syncthreads();
+            bb = *s_best;
+            __syncthreads();
+            if (bb > anchor + 1) break;
+        }
+        if (tid == 0) path[nv] = path[bb];                           // nv <= bb: the front of the list is done with
+        nv++;
+        anchor = bb;
+    }
+    __syncthreads();
+    return nv;
+}
+
+// A route's ends and its pulled cells.  Vertex m: the start, the centres of the pulled cells, the goal.
+struct PlanRoute {
+    double sx, sy, gx, gy;
+    const uint16_t *path;
+    int nvtx;
+};
+
+__device__ __forceinline__ void plan_vertex(const PlanGrid &g, const PlanRoute &rt, int m, double &x, double &y)
+{
+    if (m == 0) { x = rt.sx; y = rt.sy; return; }
+    if (m == rt.nvtx - 1) { x = rt.gx; y = rt.gy; return; }
+    const int c = rt.path[m], j = c / g.nx;
+    x = plan_centre(g.xmin, c - j * g.nx, g.cell);
+    y = plan_centre(g.ymin, j, g.cell);
+}
+
+// lengths: the segment lengths a thread each, their running sum c_0 .. c_(nvtx-1) on one lane (a fixed order).  The whole
+// workgroup calls it.
+__device__ __forceinline__ void plan_lengths(const PlanGrid &g, const PlanRoute &rt, double *cum)
+{
+    const int tid = threadIdx.x;
+    for (int m = tid; m < rt.nvtx - 1; m += kPlanThreads) {
+        double x0, y0, x1, y1;
+        plan_vertex(g, rt, m, x0, y0);
+        plan_vertex(g, rt, m + 1, x1, y1);
+        const double dx = x1 - x0, dy = y1 - y0;
+        cum[m + 1] = sqrt(dx * dx + dy * dy);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        cum[0] = 0.0;
+        for (int m = 1; m < rt.nvtx; m++) cum[m] = cum[m - 1] + cum[m];
+    }
+    __syncthreads();
+}
+
+// resample: waypoint k of W at arc (k L) / (W - 1); 0 and W - 1 are the ends' own bits.  A thread per waypoint.
+__device__ __forceinline__ void plan_waypoint(const PlanGrid &g, const PlanRoute &rt, const double *cum, double L, int k, int W,
+                                              double &x, double &y)
+{
+    x = rt.gx;
+    y = rt.gy;
+    if (k == 0) {
+        x = rt.sx;
+        y = rt.sy;
+    } else if (k < W - 1) {
+        const double s = ((double)k * L) / (double)(W - 1);
+        for (int m = 0; m < rt.nvtx - 1; m++) {
+            if (!(cum[m + 1] >= s)) continue;
+            double x0, y0, x1, y1;
+            plan_vertex(g, rt, m, x0, y0);
+            plan_vertex(g, rt, m + 1, x1, y1);
+            const double dx = x1 - x0, dy = y1 - y0, l = sqrt(dx * dx + dy * dy);
+            if (!(l > 0.0)) continue;
+            const double t = (s - cum[m]) / l;
+            x = x0 + t * dx;
+            y = y0 + t * dy;
+            break;
+        }
+    }
+}
+
+// The static free bits from the byte mask; the whole workgroup calls it; returns whether a cell is free at all (a barrier).
+__device__ __forceinline__ bool plan_static_bits(const uint8_t *free_mask, uint32_t *fbs, int ncell, int nwords)
+{
+    int any = 0;
+    for (int w = threadIdx.x; w < nwords; w += kPlanThreads) {
+        uint32_t bits = 0;
+        for (int b = 0; b < 32; b++) {
+            const int idx = w * 32 + b;
+            if (idx < ncell && free_mask[idx]) bits |= 1u << b;
+        }
+        fbs[w] = bits;
+        any |= bits != 0;
+    }
+    return __syncthreads_or(any);
+}
+
 __global__ __launch_bounds__(kPlanThreads) void k_plan_seeds(SeedArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char plan_lds[];
@@ -235,17 +434,7 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_seeds(SeedArgs a)
     const double wa = g.cell, wd = g.cell * kPlanSqrt2;
 
     // once per workgroup: the static free bits; without an occupancy also each free cell's allowed moves
-    int any = 0;
-    for (int w = tid; w < nwords; w += kPlanThreads) {
-        uint32_t bits = 0;
-        for (int b = 0; b < 32; b++) {
-            const int idx = w * 32 + b;
-            if (idx < ncell && a.free_mask[idx]) bits |= 1u << b;
-        }
-        fbs[w] = bits;
-        any |= bits != 0;
-    }
-    bool any_free = __syncthreads_or(any);
+    bool any_free = plan_static_bits(a.free_mask, fbs, ncell, nwords);
     if (!occupied) {
         plan_moves(fb, mv, nx, ny);
         __syncthreads();
@@ -254,30 +443,17 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_seeds(SeedArgs a)
     uint16_t *path = a.path_ws + (size_t)blockIdx.x * (size_t)ncell;
 #pragma unroll 1
     for (int r = blockIdx.x; r < a.R; r += gridDim.x) {
-        const double sx = a.starts[(size_t)r * 2], sy = a.starts[(size_t)r * 2 + 1];
-        const double gx = a.goals[(size_t)r * 2], gy = a.goals[(size_t)r * 2 + 1];
+        PlanRoute rt{a.starts[(size_t)r * 2], a.starts[(size_t)r * 2 + 1], a.goals[(size_t)r * 2], a.goals[(size_t)r * 2 + 1], path, 0};
         uint32_t flags = 0;
         bool ok = true;
-        int sc = 0, gc = 0, nvtx = 0;
+        int sc = 0, gc = 0;
         if (occupied) {                                              // the static bits minus the cells occupied in (t0, t1)
             const int t0 = a.windows ? a.windows[(size_t)r * 2] : INT_MIN, t1 = a.windows ? a.windows[(size_t)r * 2 + 1] : INT_MAX;
-            int some = 0;
-            for (int w = tid; w < nwords; w += kPlanThreads) {
-                uint32_t bits = fbs[w];
-                if (t0 < t1) {
-                    for (uint32_t left = bits; left; left &= left - 1) {
-                        const int b = __ffs(left) - 1, idx = w * 32 + b;
-                        if (a.occ_first[idx] < t1 && a.occ_last[idx] >= t0) bits &= ~(1u << b);
-                    }
-                }
-                fb[w] = bits;
-                some |= bits != 0;
-            }
-            any_free = __syncthreads_or(some);
+            any_free = plan_window_mask(fbs, fb, nwords, a.occ_first, a.occ_last, t0, t1);
             plan_moves(fb, mv, nx, ny);
             __syncthreads();
         }
-        if (!(isfinite(sx) && isfinite(sy) && isfinite(gx) && isfinite(gy))) {
+        if (!(isfinite(rt.sx) && isfinite(rt.sy) && isfinite(rt.gx) && isfinite(rt.gy))) {
             flags |= VAP_FLAG_DEGENERATE;
             ok = false;
         } else if (!any_free) {
@@ -287,51 +463,17 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_seeds(SeedArgs a)
         if (!ok && a.distance)                                       // no field: +inf everywhere
             for (int idx = tid; idx < ncell; idx += kPlanThreads) a.distance[(size_t)r * ncell + idx] = INFINITY;
         if (ok) {                                                    // every condition below is the same in all threads
-            gc = plan_cell_of(gy, g.ymin, g.cell, ny) * nx + plan_cell_of(gx, g.xmin, g.cell, nx);
+            gc = plan_cell_of(rt.gy, g.ymin, g.cell, ny) * nx + plan_cell_of(rt.gx, g.xmin, g.cell, nx);
             if (!plan_free(fb, gc)) {
-                gc = plan_nearest_free(g, fb, gx, gy, s_key, s_idx);
+                gc = plan_nearest_free(g, fb, rt.gx, rt.gy, s_key, s_idx);
                 flags |= VAP_PLAN_SNAPPED_GOAL;
             }
-            sc = plan_cell_of(sy, g.ymin, g.cell, ny) * nx + plan_cell_of(sx, g.xmin, g.cell, nx);
+            sc = plan_cell_of(rt.sy, g.ymin, g.cell, ny) * nx + plan_cell_of(rt.sx, g.xmin, g.cell, nx);
             if (!plan_free(fb, sc)) {
-                sc = plan_nearest_free(g, fb, sx, sy, s_key, s_idx);
+                sc = plan_nearest_free(g, fb, rt.sx, rt.sy, s_key, s_idx);
                 flags |= VAP_PLAN_SNAPPED_START;
             }
-            // the distance field: d[goal] = 0, d[v] = min over allowed moves v -> u of fl(d[u] + w)
-            for (int idx = tid; idx < ncell; idx += kPlanThreads) d[idx] = idx == gc ? 0.0 : INFINITY;
-            __syncthreads();
-            bool converged = false;
-#pragma unroll 1
-            for (int sweep = 0; sweep < ncell && !converged; sweep++) {
-                double nv[kPlanCellsPerThread];
-#pragma unroll
-                for (int c = 0; c < kPlanCellsPerThread; c++) {
-                    const int idx = tid + c * kPlanThreads;
-                    nv[c] = INFINITY;
-                    if (idx < ncell) {
-                        const unsigned m = mv[idx];
-                        double best = INFINITY;
-                        if (m) {
-#pragma unroll
-                            for (int k = 0; k < 8; k++)
-                                if (m & (1u << k)) best = fmin(best, d[idx + off[k]] + (k < 4 ? wa : wd));
-                        }
-                        nv[c] = best;
-                    }
-                }
-                __syncthreads();                                     // every read of this sweep is done
-                int changed = 0;
-#pragma unroll
-                for (int c = 0; c < kPlanCellsPerThread; c++) {
-                    const int idx = tid + c * kPlanThreads;
-                    if (idx < ncell && nv[c] < d[idx]) {
-                        d[idx] = nv[c];
-                        changed = 1;
-                    }
-                }
-                converged = !__syncthreads_or(changed);
-            }
-            if (!converged) flags |= VAP_FLAG_NOCONVERGE;
+            if (!plan_relax(d, mv, off, wa, wd, ncell, gc)) flags |= VAP_FLAG_NOCONVERGE;
             if (a.distance)
                 for (int idx = tid; idx < ncell; idx += kPlanThreads) a.distance[(size_t)r * ncell + idx] = d[idx];
             if (d[sc] == INFINITY) {
@@ -340,26 +482,10 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_seeds(SeedArgs a)
             }
         }
         if (ok) {
-            // trace: from the start's cell to the allowed neighbour with the smallest fl(d[u] + w), the first on a tie
             if (tid == 0) {
-                int cur = sc, n = 0;
-                path[n++] = (uint16_t)cur;
-                while (d[cur] > 0.0 && n < ncell) {
-                    const unsigned m = mv[cur];
-                    double best = INFINITY;
-                    int bu = -1;
-#pragma unroll
-                    for (int k = 0; k < 8; k++) {
-                        if (!(m & (1u << k))) continue;
-                        const double c = d[cur + off[k]] + (k < 4 ? wa : wd);
-                        if (c < best) { best = c; bu = cur + off[k]; }
-                    }
-                    if (bu < 0) break;
-                    cur = bu;
-                    path[n++] = (uint16_t)cur;
-                }
-                s_n = n;
-                s_fail = d[cur] > 0.0;
+                int fail;
+                s_n = plan_trace(d, mv, off, wa, wd, ncell, sc, path, fail);
+                s_fail = fail;
             }
             __syncthreads();
             const int n = s_n;
@@ -369,79 +495,17 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_seeds(SeedArgs a)
             }
             __syncthreads();
             if (ok) {
-                // pull: from anchor a the largest b whose cell is visible from a's, else a + 1
-                int nv = 1, anchor = 0;
-                while (anchor < n - 1) {
-                    if (tid == 0) s_best = anchor + 1;
-                    __syncthreads();
-                    const int ca = path[anchor];
-                    int bb = anchor + 1;
-                    for (int base = n - 1; base > anchor + 1; base -= kPlanThreads) {
-                        const int b = base - tid;
-                        if (b > anchor + 1 && plan_visible(fb, nx, ca, path[b])) atomicMax(&s_best, b);
-                        __syncthreads();
-                        bb = s_best;
-                        __syncthreads();
-                        if (bb > anchor + 1) break;
-                    }
-                    if (tid == 0) path[nv] = path[bb];               // nv <= bb: the front of the list is done with
-                    nv++;
-                    anchor = bb;
-                }
-                __syncthreads();
-                nvtx = n == 1 ? 2 : nv;
+                const int nv = plan_pull(fb, nx, path, n, &s_best);
+                rt.nvtx = n == 1 ? 2 : nv;
             }
         }
-        // vertex m: the start, the centres of the pulled cells, the goal
-        auto vertex = [&](int m, double &x, double &y) {
-            if (m == 0) { x = sx; y = sy; return; }
-            if (m == nvtx - 1) { x = gx; y = gy; return; }
-            const int c = path[m], j = c / nx;
-            x = plan_centre(g.xmin, c - j * nx, g.cell);
-            y = plan_centre(g.ymin, j, g.cell);
-        };
         double *cum = d;                                             // the field is done with: c_0 .. c_(nvtx-1)
-        if (ok) {
-            for (int m = tid; m < nvtx - 1; m += kPlanThreads) {
-                double x0, y0, x1, y1;
-                vertex(m, x0, y0);
-                vertex(m + 1, x1, y1);
-                const double dx = x1 - x0, dy = y1 - y0;
-                cum[m + 1] = sqrt(dx * dx + dy * dy);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                cum[0] = 0.0;
-                for (int m = 1; m < nvtx; m++) cum[m] = cum[m - 1] + cum[m];
-            }
-            __syncthreads();
-        }
-        const double L = ok ? cum[nvtx - 1] : INFINITY;
+        if (ok) plan_lengths(g, rt, cum);
+        const double L = ok ? cum[rt.nvtx - 1] : INFINITY;
         double *wp = a.wp + (size_t)r * a.W * 2;
         for (int k = tid; k < a.W; k += kPlanThreads) {
             double x = NAN, y = NAN;
-            if (ok) {
-                x = gx;
-                y = gy;
-                if (k == 0) {
-                    x = sx;
-                    y = sy;
-                } else if (k < a.W - 1) {
-                    const double s = ((double)k * L) / (double)(a.W - 1);
-                    for (int m = 0; m < nvtx - 1; m++) {
-                        if (!(cum[m + 1] >= s)) continue;
-                        double x0, y0, x1, y1;
-                        vertex(m, x0, y0);
-                        vertex(m + 1, x1, y1);
-                        const double dx = x1 - x0, dy = y1 - y0, l = sqrt(dx * dx + dy * dy);
-                        if (!(l > 0.0)) continue;
-                        const double t = (s - cum[m]) / l;
-                        x = x0 + t * dx;
-                        y = y0 + t * dy;
-                        break;
-                    }
-                }
-            }
+            if (ok) plan_waypoint(g, rt, cum, L, k, a.W, x, y);
             wp[2 * k] = x;
             wp[2 * k + 1] = y;
         }
@@ -449,18 +513,160 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_seeds(SeedArgs a)
             double *vo = a.vertices + (size_t)r * a.max_vertices * 2;
             for (int m = tid; m < a.max_vertices; m += kPlanThreads) {
                 double x = NAN, y = NAN;
-                if (ok && m < nvtx) vertex(m, x, y);
+                if (ok && m < rt.nvtx) plan_vertex(g, rt, m, x, y);
                 vo[2 * m] = x;
                 vo[2 * m + 1] = y;
             }
-            if (ok && nvtx > a.max_vertices) flags |= VAP_PLAN_VERTICES_TRUNCATED;
+            if (ok && rt.nvtx > a.max_vertices) flags |= VAP_PLAN_VERTICES_TRUNCATED;
         }
         if (tid == 0) {
             if (a.length) a.length[r] = L;
             if (a.flags) a.flags[r] = flags;
-            if (a.n_vertices) a.n_vertices[r] = ok ? nvtx : 0;
+            if (a.n_vertices) a.n_vertices[r] = ok ? rt.nvtx : 0;
         }
         __syncthreads();                                             // the next problem rewrites the field and the list
+    }
+}
+
+struct TravelArgs {
+    PlanGrid g;
+    int R, P, W;
+    const double *points;       // [R][P][2]
+    const uint8_t *free_mask;
+    uint16_t *path_ws;          // [gridDim.x][nx * ny]
+    double *cum_ws;             // [gridDim.x][max(nx * ny, 2)]
+    double *travel;             // [R][P][P]
+    uint32_t *flags;
+    int *n_vertices;
+    double *wp;                 // [R][P][P][W][2]
+    const int *occ_first, *occ_last;   // [ny][nx], both or neither
+    const int *windows;                // [R][2] (t0, t1), NULL: every instant
+};
+
+// Entry (r, a, b) is k_plan_seeds' problem (start = point a, goal = point b): an item is one (problem, goal), whose field is
+// relaxed once and stays in LDS while every start a != b is snapped, traced, pulled and resampled against it.  The running
+// sums therefore live in the workgroup's global workspace, not where the field is.
+__global__ __launch_bounds__(kPlanThreads) void k_plan_travel(TravelArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char plan_lds[];
+    __shared__ double s_key[kPlanWaves];
+    __shared__ int s_idx[kPlanWaves];
+    __shared__ int s_n, s_best, s_fail;
+    const PlanGrid g = a.g;
+    const int tid = threadIdx.x, nx = g.nx, ny = g.ny, ncell = nx * ny, nwords = (ncell + 31) / 32, P = a.P;
+    double *d = reinterpret_cast<double *>(plan_lds);
+    const bool occupied = a.occ_first != nullptr;
+    uint32_t *fbs = reinterpret_cast<uint32_t *>(d + ncell);
+    uint32_t *fb = occupied ? fbs + nwords : fbs;                    // the problem's own mask
+    uint8_t *mv = reinterpret_cast<uint8_t *>(fb + nwords);
+    const int off[8] = {1, nx, -1, -nx, nx + 1, nx - 1, -nx - 1, -nx + 1};
+    const double wa = g.cell, wd = g.cell * kPlanSqrt2;
+
+    bool any_free = plan_static_bits(a.free_mask, fbs, ncell, nwords);
+    if (!occupied) {
+        plan_moves(fb, mv, nx, ny);
+        __syncthreads();
+    }
+
+    uint16_t *path = a.path_ws + (size_t)blockIdx.x * (size_t)ncell;
+    double *cum = a.cum_ws + (size_t)blockIdx.x * (size_t)(ncell < 2 ? 2 : ncell);
+    const int items = a.R * P;
+    int built = -1;                                                  // the problem whose mask and moves are in LDS
+#pragma unroll 1
+    for (int it = blockIdx.x; it < items; it += gridDim.x) {
+        const int r = it / P, b = it - r * P;
+        const double *pts = a.points + (size_t)r * P * 2;
+        const double gx = pts[2 * b], gy = pts[2 * b + 1];
+        if (occupied && r != built) {
+            const int t0 = a.windows ? a.windows[(size_t)r * 2] : INT_MIN, t1 = a.windows ? a.windows[(size_t)r * 2 + 1] : INT_MAX;
+            any_free = plan_window_mask(fbs, fb, nwords, a.occ_first, a.occ_last, t0, t1);
+            plan_moves(fb, mv, nx, ny);
+            __syncthreads();
+            built = r;
+        }
+        // the goal's share of every pair: its cell and its field
+        const bool goal_ok = isfinite(gx) && isfinite(gy);
+        uint32_t gflags = 0;
+        int gc = 0;
+        if (goal_ok && any_free) {
+            gc = plan_cell_of(gy, g.ymin, g.cell, ny) * nx + plan_cell_of(gx, g.xmin, g.cell, nx);
+            if (!plan_free(fb, gc)) {
+                gc = plan_nearest_free(g, fb, gx, gy, s_key, s_idx);
+                gflags |= VAP_PLAN_SNAPPED_GOAL;
+            }
+            if (!plan_relax(d, mv, off, wa, wd, ncell, gc)) gflags |= VAP_FLAG_NOCONVERGE;
+        }
+#pragma unroll 1
+        for (int s = 0; s < P; s++) {
+            const size_t e = ((size_t)r * P + s) * P + b;
+            double *wp = a.wp ? a.wp + e * a.W * 2 : nullptr;
+            if (s == b) {                                            // the diagonal: nowhere to go
+                for (int k = tid; wp && k < a.W; k += kPlanThreads) {
+                    wp[2 * k] = gx;
+                    wp[2 * k + 1] = gy;
+                }
+                if (tid == 0) {
+                    a.travel[e] = 0.0;
+                    if (a.flags) a.flags[e] = 0;
+                    if (a.n_vertices) a.n_vertices[e] = 0;
+                }
+                continue;
+            }
+            PlanRoute rt{pts[2 * s], pts[2 * s + 1], gx, gy, path, 0};
+            uint32_t flags = 0;
+            bool ok = true;
+            if (!(isfinite(rt.sx) && isfinite(rt.sy) && goal_ok)) {
+                flags |= VAP_FLAG_DEGENERATE;
+                ok = false;
+            } else if (!any_free) {
+                flags |= VAP_PLAN_NO_FREE;
+                ok = false;
+            }
+            if (ok) {                                                // every condition below is the same in all threads
+                flags = gflags;
+                int sc = plan_cell_of(rt.sy, g.ymin, g.cell, ny) * nx + plan_cell_of(rt.sx, g.xmin, g.cell, nx);
+                if (!plan_free(fb, sc)) {
+                    sc = plan_nearest_free(g, fb, rt.sx, rt.sy, s_key, s_idx);
+                    flags |= VAP_PLAN_SNAPPED_START;
+                }
+                if (d[sc] == INFINITY) {
+                    flags |= VAP_PLAN_UNREACHABLE;
+                    ok = false;
+                }
+                if (ok) {
+                    if (tid == 0) {
+                        int fail;
+                        s_n = plan_trace(d, mv, off, wa, wd, ncell, sc, path, fail);
+                        s_fail = fail;
+                    }
+                    __syncthreads();
+                    const int n = s_n;
+                    if (s_fail) {
+                        flags |= VAP_FLAG_NOCONVERGE;
+                        ok = false;
+                    }
+                    __syncthreads();
+                    if (ok) {
+                        const int nv = plan_pull(fb, nx, path, n, &s_best);
+                        rt.nvtx = n == 1 ? 2 : nv;
+                    }
+                }
+            }
+            if (ok) plan_lengths(g, rt, cum);
+            const double L = ok ? cum[rt.nvtx - 1] : INFINITY;
+            for (int k = tid; wp && k < a.W; k += kPlanThreads) {
+                double x = NAN, y = NAN;
+                if (ok) plan_waypoint(g, rt, cum, L, k, a.W, x, y);
+                wp[2 * k] = x;
+                wp[2 * k + 1] = y;
+            }
+            if (tid == 0) {
+                a.travel[e] = L;
+                if (a.flags) a.flags[e] = flags;
+                if (a.n_vertices) a.n_vertices[e] = ok ? rt.nvtx : 0;
+            }
+            __syncthreads();                                         // the next start rewrites the list and the sums
+        }
     }
 }
 
@@ -523,6 +729,20 @@ static int plan_launch_grid(vap_ctx *ctx, const PlanGrid &g, int nv, int n_poly,
     return VAP_OK;
 }
 
+// Dynamic LDS above the default limit has to be granted by the runtime; a device attribute that reports more than the default
+// is the opt-in limit and is checked too.
+static int plan_grant_lds(vap_ctx *ctx, const void *kernel, size_t lds, const PlanGrid &g)
+{
+    if (lds <= 64 * 1024) return VAP_OK;
+    int lds_max = 0;
+    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess) lds_max = 0;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess || (lds_max > 64 * 1024 && lds + kPlanStaticLds > (size_t)lds_max))
+        return vap_fail(VAP_ERR_UNSUPPORTED, "a grid of %d x %d cells needs %zu bytes of LDS; the device gives a workgroup %d (%s)",
+                        g.nx, g.ny, lds + kPlanStaticLds, lds_max, hipGetErrorString(e));
+    return VAP_OK;
+}
+
 }  // namespace vap
 
 extern "C" {
@@ -575,16 +795,7 @@ int vap_plan_seeds_occupied(vap_ctx *ctx, int R, int W, const double *d_starts, 
     const size_t ncell = (size_t)g.nx * g.ny, nwords = (ncell + 31) / 32;
     const size_t lds = (ncell < 2 ? 2 : ncell) * sizeof(double) + (d_occ_first ? 2 : 1) * nwords * sizeof(uint32_t) +
                        ((ncell + 15) & ~(size_t)15);
-    if (lds > 64 * 1024) {
-        // above the default limit the runtime has to grant the size; a device attribute that reports more than the default
-        // is the opt-in limit and is checked too
-        int lds_max = 0;
-        if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess) lds_max = 0;
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_plan_seeds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess || (lds_max > 64 * 1024 && lds + kPlanStaticLds > (size_t)lds_max))
-            return vap_fail(VAP_ERR_UNSUPPORTED, "a grid of %d x %d cells needs %zu bytes of LDS; the device gives a workgroup %d (%s)",
-                            g.nx, g.ny, lds + kPlanStaticLds, lds_max, hipGetErrorString(e));
-    }
+    VAP_TRY(plan_grant_lds(ctx, reinterpret_cast<const void *>(k_plan_seeds), lds, g));
     const int blocks = R < kPlanMaxBlocks ? R : kPlanMaxBlocks;
     VAP_TRY(ctx->ensure(ctx->plan_free, ncell));
     VAP_TRY(ctx->ensure(ctx->plan_path, (size_t)blocks * ncell * sizeof(uint16_t)));
@@ -609,6 +820,59 @@ int vap_plan_seeds_occupied(vap_ctx *ctx, int R, int W, const double *d_starts, 
     a.occ_last = d_occ_last;
     a.windows = d_occ_first ? d_windows : nullptr;
     hipLaunchKernelGGL(k_plan_seeds, dim3((unsigned)blocks), dim3(kPlanThreads), lds, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    return VAP_OK;
+}
+
+int vap_plan_travel(vap_ctx *ctx, int R, int P, int W, const double *d_points, const double *h_field, int n_poly,
+                    const int *h_poly_start, const double *h_poly_xy, int n_circle, const double *h_circles, double cell,
+                    double radius, double margin, int max_vertices, const int *d_occ_first, const int *d_occ_last,
+                    const int *d_windows, double *d_travel, uint32_t *d_flags, int *d_n_vertices, double *d_waypoints)
+{
+    using namespace vap;
+    (void)max_vertices;                                              // no output of this call is cut to it
+    if ((d_occ_first == nullptr) != (d_occ_last == nullptr))
+        return vap_fail(VAP_ERR_INVALID, "the occupancy needs both its first and its last instants (or neither)");
+    if (R < 0 || P < 2) return vap_fail(VAP_ERR_INVALID, "bad shape R=%d P=%d", R, P);
+    if (P > VAP_PLAN_TRAVEL_MAX_POINTS) return vap_fail(VAP_ERR_UNSUPPORTED, "P=%d exceeds %d", P, VAP_PLAN_TRAVEL_MAX_POINTS);
+    if (d_waypoints && W < 2) return vap_fail(VAP_ERR_INVALID, "W=%d: a route needs at least 2 waypoints", W);
+    if (d_waypoints && W > kMaxWaypoints) return vap_fail(VAP_ERR_UNSUPPORTED, "W=%d exceeds %d", W, kMaxWaypoints);
+    if (R > 0 && (!d_points || !d_travel)) return vap_fail(VAP_ERR_INVALID, "null points / travel");
+    if ((long long)R * P > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "R=%d problems of P=%d points exceed %d goals", R, P, INT_MAX);
+    PlanGrid g{};
+    int nv = 0;
+    VAP_TRY(plan_check(h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, cell, radius, margin, g, nv));
+    VAP_TRY(vap_set_device(ctx));
+    if (R == 0) return VAP_OK;
+
+    const size_t ncell = (size_t)g.nx * g.ny, nwords = (ncell + 31) / 32, ncum = ncell < 2 ? 2 : ncell;
+    const size_t lds = ncell * sizeof(double) + (d_occ_first ? 2 : 1) * nwords * sizeof(uint32_t) + ((ncell + 15) & ~(size_t)15);
+    VAP_TRY(plan_grant_lds(ctx, reinterpret_cast<const void *>(k_plan_travel), lds, g));
+    const long long items = (long long)R * P;
+    const int blocks = items < kPlanMaxBlocks ? (int)items : kPlanMaxBlocks;
+    // the workspace: every workgroup's running sums, then its cell list
+    const size_t cum_bytes = (size_t)blocks * ncum * sizeof(double);
+    VAP_TRY(ctx->ensure(ctx->plan_free, ncell));
+    VAP_TRY(ctx->ensure(ctx->plan_path, cum_bytes + (size_t)blocks * ncell * sizeof(uint16_t)));
+    VAP_TRY(plan_launch_grid(ctx, g, nv, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, radius, margin, nullptr,
+                             (uint8_t *)ctx->plan_free.ptr));
+    TravelArgs a{};
+    a.g = g;
+    a.R = R;
+    a.P = P;
+    a.W = W;
+    a.points = d_points;
+    a.free_mask = (const uint8_t *)ctx->plan_free.ptr;
+    a.cum_ws = (double *)ctx->plan_path.ptr;
+    a.path_ws = (uint16_t *)((char *)ctx->plan_path.ptr + cum_bytes);
+    a.travel = d_travel;
+    a.flags = d_flags;
+    a.n_vertices = d_n_vertices;
+    a.wp = d_waypoints;
+    a.occ_first = d_occ_first;
+    a.occ_last = d_occ_last;
+    a.windows = d_occ_first ? d_windows : nullptr;
+    hipLaunchKernelGGL(k_plan_travel, dim3((unsigned)blocks), dim3(kPlanThreads), lds, ctx->stream, a);
     HIP_TRY(hipGetLastError());
     return VAP_OK;
 }

@@ -1,5 +1,5 @@
 """Seed routes through a scene, planned on a grid on the device (vap_plan_grid, vap_plan_seeds, vap_plan_occupancy,
-vap_plan_seeds_occupied, include/vap.h).
+vap_plan_seeds_occupied, vap_plan_travel, vap_plan_order, include/vap.h).
 
 ``search.refine`` improves a route that is already roughly right: it draws candidates round a mean, coordinate by
 coordinate, and cannot get round an obstacle that is larger than its sigma.  This module gives it the route to start from.
@@ -17,6 +17,10 @@ A partner's routine is no part of the scene: ``occupancy`` rasterises its time-d
 first and last instant at which its footprint leaves the disc less than ``margin``), and ``seeds(occupancy=..., windows=...)``
 keeps each problem off the cells occupied within its window of instants.
 
+A routine is a start and a handful of sites: ``travel`` plans every ordered pair of P points at the price of P distance
+fields, ``order`` finds the cheapest visiting order from any (P, P) cost matrix on the device, and ``routine`` chains the
+two and gathers the legs in visiting order, ready for ``refine(seeds=...)``, without a host synchronisation.
+
 Units: feet, in the scene's frame.  At most 16384 cells (the distance field of a problem lives in one workgroup's LDS).
 """
 import ctypes as C
@@ -31,7 +35,9 @@ MAX_CELLS = 16384
 MAX_WAYPOINTS = 2048
 FLAGS = {"degenerate": _lib.FLAG_DEGENERATE, "noconverge": _lib.FLAG_NOCONVERGE, "snapped_start": _lib.PLAN_SNAPPED_START,
          "snapped_goal": _lib.PLAN_SNAPPED_GOAL, "no_free": _lib.PLAN_NO_FREE, "unreachable": _lib.PLAN_UNREACHABLE,
-         "vertices_truncated": _lib.PLAN_VERTICES_TRUNCATED}
+         "vertices_truncated": _lib.PLAN_VERTICES_TRUNCATED, "order_infeasible": _lib.ORDER_INFEASIBLE}
+MAX_POINTS = _lib.PLAN_TRAVEL_MAX_POINTS
+MAX_SITES = _lib.PLAN_ORDER_MAX_SITES
 
 
 def circumscribed_radius(footprint):
@@ -247,4 +253,183 @@ def seeds(starts, goals, scene, waypoints, radius, cell=0.25, margin=0.0, max_ve
     res["feasible"] = res["n_vertices"] > 0
     if single:
         res = {k: v[0] for k, v in res.items()}
+    return res
+
+
+def _occupancy_args(occupancy, windows, R, ny, nx, dev):
+    """(first, last, windows) device tensors for the C-ABI, or three Nones without an occupancy."""
+    if occupancy is None:
+        if windows is not None:
+            raise ValueError("windows needs an occupancy")
+        return None, None, None
+    first, last = (occupancy["first"], occupancy["last"]) if isinstance(occupancy, dict) else occupancy
+    for t in (first, last):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.int32 or tuple(t.shape) != (ny, nx):
+            raise ValueError(f"occupancy must be ({ny}, {nx}) int32 tensors on {dev} (plan.occupancy with the same scene and cell)")
+    if windows is not None:
+        if isinstance(windows, torch.Tensor):
+            windows = windows.to(device=dev, dtype=torch.int32)
+        else:
+            windows = torch.as_tensor(np.ascontiguousarray(windows, dtype=np.int32), device=dev)
+        if windows.dim() == 1:
+            windows = windows.unsqueeze(0).expand(R, 2)
+        if tuple(windows.shape) != (R, 2):
+            raise ValueError(f"windows must be ({R}, 2) or (2,), got {tuple(windows.shape)}")
+        windows = windows.contiguous()
+    return first.contiguous(), last.contiguous(), windows
+
+
+def travel(points, scene, radius, cell=0.25, margin=0.0, waypoints=None, occupancy=None, windows=None, out=None, device=0,
+           ctx=None):
+    """All ordered pairs of P points per problem, at the price of P distance fields (vap_plan_travel).
+
+      points          (R, P, 2) or (P, 2) points in feet, 2 <= P <= 16: a device tensor (any float type, used as fp64) or a
+                      host array
+      scene, radius, cell, margin   as ``seeds`` takes them
+      waypoints       W: also return every pair's W waypoints (2..2048); None: lengths, flags and vertex counts only
+      occupancy, windows   as ``seeds`` takes them; problem r's one window (R, 2) or (2,) holds for all its pairs
+      out             optional dict of tensors of the shapes below to reuse
+    Returns a dict of device tensors: travel (R, P, P) fp64, entry [r, a, b] the length of the seed route from point a to
+    point b (+inf where there is none, 0 on the diagonal), flags (R, P, P) int32 (``plan.FLAGS``), n_vertices (R, P, P)
+    int32, feasible (R, P, P) bool (travel is finite), and waypoints (R, P, P, W, 2) if asked.  Off the diagonal every entry
+    is what ``seeds(points[r, a], points[r, b], ...)`` gives, bit for bit; the matrix is not symmetric.  A single (P, 2) set
+    gives results without the leading axis.  Work runs on torch's current stream and is not synchronised."""
+    W = 2
+    if waypoints is not None:
+        W = int(waypoints)
+        if W != waypoints or W < 2:
+            raise ValueError(f"waypoints must be an integer >= 2 (got {waypoints!r})")
+        if W > MAX_WAYPOINTS:
+            raise ValueError(f"waypoints = {W}: at most {MAX_WAYPOINTS}")
+    ny, nx, args = _check(scene, cell, radius, margin)
+    dev = points.device if isinstance(points, torch.Tensor) and points.device.type == "cuda" else torch.device("cuda", device)
+    if isinstance(points, torch.Tensor):
+        pts = points.to(device=dev, dtype=torch.float64)
+    else:
+        pts = torch.as_tensor(np.ascontiguousarray(points, dtype=np.float64), device=dev)
+    single = pts.dim() == 2
+    if single:
+        pts = pts.unsqueeze(0)
+    if pts.dim() != 3 or pts.shape[2] != 2:
+        raise ValueError(f"points must be (R, P, 2) or (P, 2), got {tuple(points.shape)}")
+    pts = pts.contiguous()
+    R, P = int(pts.shape[0]), int(pts.shape[1])
+    if not 2 <= P <= MAX_POINTS:
+        raise ValueError(f"P = {P} points: 2..{MAX_POINTS}")
+    shapes = {"travel": ((R, P, P), torch.float64), "flags": ((R, P, P), torch.int32), "n_vertices": ((R, P, P), torch.int32)}
+    if waypoints is not None:
+        shapes["waypoints"] = ((R, P, P, W, 2), torch.float64)
+    first, last, windows = _occupancy_args(occupancy, windows, R, ny, nx, dev)
+    res = _buffers(out, shapes, dev)
+    ctx = _context(dev, ctx)
+    _lib.check(ctx._L.vap_plan_travel(ctx.handle, R, P, W, _ptr(pts), *args, 0, _ptr(first), _ptr(last), _ptr(windows),
+                                      _ptr(res["travel"]), _ptr(res["flags"]), _ptr(res["n_vertices"]),
+                                      _ptr(res["waypoints"] if waypoints is not None else None)), "vap_plan_travel")
+    res["feasible"] = torch.isfinite(res["travel"])
+    if single:
+        res = {k: v[0] for k, v in res.items()}
+    return res
+
+
+def before_masks(before, R, P):
+    """(R, P) uint32 precedence masks from a list of (earlier, later) site pairs (the same for every problem): bit j - 1 of
+    entry k says site j comes before site k.  Host only."""
+    m = np.zeros(P, dtype=np.int64)
+    for pair in before:
+        if len(pair) != 2:
+            raise ValueError(f"before must hold (earlier, later) pairs, got {pair!r}")
+        j, k = int(pair[0]), int(pair[1])
+        if not (1 <= j < P and 1 <= k < P):
+            raise ValueError(f"before pair {pair!r}: sites are 1..{P - 1}")
+        m[k] |= 1 << (j - 1)
+    return np.broadcast_to(m.astype(np.uint32), (R, P)).copy()
+
+
+def order(cost, end=None, before=None, out=None, ctx=None):
+    """The cheapest order to visit M = P - 1 sites in, starting from point 0, by Held-Karp on the device (vap_plan_order).
+
+      cost     (R, P, P) or (P, P) fp64 device tensor, cost[r, a, b] of going from point a to point b, 2 <= P <= 11: what
+               ``travel`` returned, or anything made of it with torch on the device (seconds, dwell times, +inf for a
+               forbidden leg; NaN and -inf count as +inf)
+      end      None: the routine may end at any site; 1..M: it ends at that site
+      before   precedence: an (R, P) or (P,) integer tensor or array of masks (bit j - 1 of entry k: site j before site k),
+               or a list of (earlier, later) site pairs, turned into the masks on the host
+      out      optional dict of tensors of the shapes below to reuse
+    Returns a dict of device tensors: order (R, M) int32, the sites in visiting order (-1 where infeasible), total (R,) fp64
+    (the left-to-right sum along the order; +inf where infeasible), flags (R,) int32 (``FLAGS["order_infeasible"]``) and
+    feasible (R,) bool.  A single (P, P) matrix gives results without the leading axis.  Work runs on torch's current
+    stream and is not synchronised."""
+    if not isinstance(cost, torch.Tensor) or cost.device.type != "cuda":
+        raise ValueError("cost must be a device tensor")
+    dev = cost.device
+    c = cost.to(dtype=torch.float64)
+    single = c.dim() == 2
+    if single:
+        c = c.unsqueeze(0)
+    if c.dim() != 3 or c.shape[1] != c.shape[2]:
+        raise ValueError(f"cost must be (R, P, P) or (P, P), got {tuple(cost.shape)}")
+    c = c.contiguous()
+    R, P = int(c.shape[0]), int(c.shape[1])
+    M = P - 1
+    if not 1 <= M <= MAX_SITES:
+        raise ValueError(f"P = {P} points: 2..{MAX_SITES + 1} (the start and at most {MAX_SITES} sites)")
+    e = -1 if end is None else int(end)
+    if end is not None and (e != end or not 1 <= e <= M):
+        raise ValueError(f"end must be None or a site 1..{M} (got {end!r})")
+    b = None
+    if before is not None:
+        if isinstance(before, (list, tuple)):                        # (earlier, later) pairs
+            before = before_masks(before, R, P)
+        if isinstance(before, torch.Tensor):
+            b = before.to(device=dev, dtype=torch.int64)
+        else:
+            b = torch.as_tensor(np.ascontiguousarray(before, dtype=np.int64), device=dev)
+        if b.dim() == 1:
+            b = b.unsqueeze(0).expand(R, P)
+        if tuple(b.shape) != (R, P):
+            raise ValueError(f"before must be ({R}, {P}) or ({P},) masks or a list of (earlier, later) pairs, got {tuple(b.shape)}")
+        b = (b & (2 ** MAX_SITES - 1)).to(torch.int32).contiguous()  # bits >= M are ignored anyway
+    res = _buffers(out, {"order": ((R, M), torch.int32), "total": ((R,), torch.float64), "flags": ((R,), torch.int32)}, dev)
+    ctx = _context(dev, ctx)
+    _lib.check(ctx._L.vap_plan_order(ctx.handle, R, P, _ptr(c), e, _ptr(b), _ptr(res["order"]), _ptr(res["total"]),
+                                     _ptr(res["flags"])), "vap_plan_order")
+    res["feasible"] = res["flags"] == 0
+    if single:
+        res = {k: v[0] for k, v in res.items()}
+    return res
+
+
+def routine(points, scene, waypoints, radius, cell=0.25, margin=0.0, occupancy=None, windows=None, end=None, before=None,
+            leg_cost=None, out=None, device=0, ctx=None):
+    """A routine's visiting order and the seed route of each leg: ``travel`` with waypoints, ``order`` on its lengths (or on
+    ``leg_cost(travel)``, a callable on the (R, P, P) device tensor that returns the costs), then the M legs
+    0 -> o_1 -> ... -> o_M gathered out of the travel's waypoints on the device.  points[.., 0, :] is where the routine
+    starts, the other P - 1 <= 10 points are the sites.
+
+    Returns what ``order`` returned (order, total, flags, feasible), the travel outputs under travel, travel_flags,
+    n_vertices and waypoints, and legs (R, M, W, 2): ``legs.reshape(R * M, W, 2)`` is what ``refine(seeds=...)`` takes.  An
+    infeasible problem has NaN legs.  Nothing here reads a result on the host."""
+    if leg_cost is not None and not callable(leg_cost):
+        raise TypeError("leg_cost must be a callable on the travel tensor")
+    out = {} if out is None else out
+    tr = travel(points, scene, radius, cell=cell, margin=margin, waypoints=waypoints, occupancy=occupancy, windows=windows,
+                out=out.setdefault("_travel", {}), device=device, ctx=ctx)
+    single = tr["travel"].dim() == 2
+    if single:
+        tr = {k: v[None] for k, v in tr.items()}
+    t, wp = tr["travel"], tr["waypoints"]
+    R = int(t.shape[0])
+    od = order(t if leg_cost is None else leg_cost(t), end=end, before=before, out=out.setdefault("_order", {}), ctx=ctx)
+    o = od["order"].to(torch.int64)
+    feasible = od["feasible"]
+    to = o.clamp(min=0)
+    frm = torch.cat([torch.zeros_like(to[:, :1]), to[:, :-1]], dim=1)
+    rows = torch.arange(R, device=t.device)[:, None]
+    legs = wp[rows, frm, to]
+    legs = torch.where(feasible[:, None, None, None], legs, torch.full_like(legs, float("nan")))
+    res = {"order": od["order"], "total": od["total"], "flags": od["flags"], "feasible": feasible, "travel": t,
+           "travel_flags": tr["flags"], "n_vertices": tr["n_vertices"], "waypoints": wp, "legs": legs}
+    if single:
+        res = {k: v[0] for k, v in res.items()}
+    out.update(res)
     return res
