@@ -290,7 +290,12 @@ int vap_time_profile(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, const doub
  *   d_counts_out  [B][3] int32: rows, nodes_map entries, actions_map entries
  *   d_nodes_map_out [B][W], d_actions_map_out [B][M] int32
  * Segments / table NULL = those of the last vap_profile_batch.  Turn and reverse nodes are not covered
- * (vap_route_motion_profile). */
+ * (vap_route_motion_profile).
+ * A route that needs more than capacity_out rows is cut there and flagged VAP_FLAG_TRUNCATED (here and in
+ * vap_time_insert_events): rows [0, capacity_out) are exactly those of a call with enough capacity, d_counts_out[b][0] =
+ * capacity_out, and nothing is written at or behind row capacity_out.  d_nodes_map_out, d_actions_map_out and their
+ * counts are NOT cut: they hold what a call with enough capacity gives, so an entry of a truncated route may name a
+ * row >= capacity_out that does not exist; compare entries with d_counts_out[b][0] before indexing rows with them. */
 int vap_time_insert_waits(vap_ctx *ctx, int B, int W, int M, int capacity_in, int capacity_out, double time_step,
                           const double *d_segments, const double *d_lut, const double *d_meta,
                           const double *d_rows_in, const int *d_counts_in, const int *d_nodes_map_in,
