@@ -870,6 +870,59 @@ int vap_plan_travel(vap_ctx *ctx, int R, int P, int W, const double *d_points, c
 int vap_plan_order(vap_ctx *ctx, int R, int P, const double *d_cost, int end, const uint32_t *d_before, int *d_order, double *d_total,
                    uint32_t *d_flags);
 
+/* ---- a routine's legs chained into one timeline ------------------------------------------------------------------------------
+ * vap_plan_order gives a visiting order and the route search refines each leg by itself, every leg profiled from its own
+ * time zero.  vap_routine_timeline puts the legs back together: for every used slot m of routine r the output holds, in this
+ * order, [turn m] [leg m] [dwell m], all in the 8-column rows of vap_time_profile and on one time step, so the result goes
+ * where the rows of vap_time_profile go (vap_footprint_clearance, vap_footprint_conflicts, vap_tracking_rollouts,
+ * vap_plan_occupancy).  The reference chains nothing: a routine is one hand-made path there; the turn is its own
+ * (MPG:319-346 motion_profile_angle over one_dim_mp_generator.py:4-69, inserted as MPG:487-507 handle_turn does).
+ *   inputs    d_rows_in [L][capacity_in][8], d_counts_in [L * counts_stride] (entry l * counts_stride = rows of leg l; a count
+ *             above capacity_in counts as capacity_in): L legs on the device.  d_leg [R][M] int32: the leg driven in slot m;
+ *             a leg may serve several slots and routines.  d_n_legs [R] int32 or NULL (= M): slots used, clamped to 0 .. M.
+ *             d_dwell [R][M] seconds at the end of slot m or NULL; d_start_heading [R] or NULL: the heading the robot stands
+ *             at before slot 0 (NaN: none).  1 <= M <= 32.
+ *   turn      from the heading h of the output row in front (slot 0: the start heading; none: no turn block) to the heading
+ *             of leg m's first row: D = first - h; if D > pi, D -= 2 pi; if D <= -pi, D += 2 pi.  |D| < turn_min: no rows.
+ *             Otherwise the rows of handle_turn for angle = -D radians with c->max_vel, max_acc, track_width: n =
+ *             ceil((total_time + dt) / dt) rows; row j has heading h + wrapped(sum_{i<j} v(i dt) dt / (track_width / 2) * sign)
+ *             (the running sum taken left to right) and angular velocity (difference of the UN-wrapped sums) / dt, 0 in
+ *             row 0; linear velocity and acceleration 0; position, x, y of the row in front (slot 0: position 0 and the
+ *             point of leg 0's first row).
+ *   leg       the leg's rows, with time = in_time + (double)s * dt (s = the block's first output row, vap_time_insert_waits'
+ *             convention) and position = in_position + off_m, off_0 = 0, off_{m+1} = off_m + (last position of leg m), summed
+ *             left to right.  The other six columns are copied.
+ *   dwell     int(dwell / dt) rows (NaN or <= 0: none; saturating at INT_MAX): velocity, acceleration, angular velocity 0;
+ *             heading, x, y, position of the row in front.  Every inserted row (turn or dwell) at output row o has time
+ *             (double)o * dt.
+ *   outputs   d_rows_out [R][capacity_out][8] (must not alias d_rows_in); d_counts_out [R][2] = {rows, slots used}; d_map
+ *             [R][M][3] = the first output row of slot m's turn, leg and dwell block (saturating at INT_MAX; -1 for an unused
+ *             slot): site m is reached at map[r][m][2] * dt, and the routine takes rows * dt; d_seam [R][M][3] = {heading of
+ *             leg m's first row minus the heading of the last turn row (of the row in front without a turn), wrapped as D; x
+ *             and y of leg m's first row minus those of the row in front}: the rectangle-rule sum does not land on the angle
+ *             (6.8e-7 rad for a quarter turn of the default robot at 10 ms), and the x, y gap is what a planner has to keep
+ *             small.  Without a row in front the x, y entries are 0, and the heading entry is NaN unless a start heading was
+ *             given.  d_flags [R] or NULL: bits are OR-ed in.
+ *   failures  a routine with a used slot whose leg index is outside [0, L), whose leg has no rows, or whose first-row or
+ *             last-row x or y is not finite or heading is not within [-2 pi, 2 pi] (the rows of vap_time_profile keep
+ *             [-pi, pi]), or with such a start heading: VAP_FLAG_BAD_ROUTE, 0 rows, map -1, seam NaN, and none of its rows
+ *             is written.  Truncation is vap_time_insert_events': rows [0, capacity_out) are exactly those of a call with
+ *             enough capacity, nothing is written at or behind capacity_out, the count is capacity_out, VAP_FLAG_TRUNCATED;
+ *             d_map and d_seam are NOT cut.
+ * One workgroup per (routine, slot); each derives its routine's offsets itself.  VAP_ERR_INVALID: M < 1, R < 0, L < 0, a negative
+ * capacity, counts_stride < 1, a time_step that is not positive and finite, a turn_min that is negative or not finite, null
+ * constraints or a max_vel, max_acc or track_width that is not positive and finite, a null leg, count, map, seam or row
+ * pointer with R > 0, d_rows_out == d_rows_in, a row pointer that is not 16-byte aligned (hipMalloc's and torch's allocations
+ * are).  VAP_ERR_UNSUPPORTED: M > 32, R * M above INT_MAX, a full turn of more than
+ * 2^20 rows.  The arguments are checked before the context is touched.  R = 0 is a no-op.  Works on the context's stream and
+ * does not synchronise; no atomics beside the flag OR: two calls give the same bits. */
+#define VAP_TIMELINE_MAX_LEGS 32
+int vap_routine_timeline(vap_ctx *ctx, int R, int M, int L, int capacity_in, int capacity_out, double time_step,
+                         const vap_constraints *c, double turn_min, const double *d_rows_in, const int *d_counts_in,
+                         int counts_stride, const int *d_leg, const int *d_n_legs, const double *d_dwell,
+                         const double *d_start_heading, double *d_rows_out, int *d_counts_out, int *d_map, double *d_seam,
+                         uint32_t *d_flags);
+
 #ifdef __cplusplus
 }
 #endif

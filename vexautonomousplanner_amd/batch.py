@@ -503,5 +503,16 @@ class BatchedTrajectoryGenerator:
             raise ValueError(f"rows must be on {self.device}")
         return plan.occupancy(tp, None, footprint, scene, cell, radius, device=self.device.index, ctx=self.ctx, **kw)
 
+    def routine_timeline(self, tp, legs, **kw):
+        """The legs of ``tp`` — the dict ``time_profile`` returned for a batch of legs — chained into routines: per slot the
+        in-place turn to the leg's first heading, the leg, and the dwell at its site (vap_routine_timeline on this
+        generator's context and torch's current stream; see timeline.chain for ``legs`` (R, M), dwell, start_heading,
+        n_legs, constraints, dt, turn_min, capacity_rows, out and the returned dict).  The result goes into
+        ``footprint_clearance``, ``footprint_conflicts``, ``tracking_rollouts`` and ``plan_occupancy`` where ``tp`` goes."""
+        from . import timeline
+        if tp["rows"].device != self.device:
+            raise ValueError(f"rows must be on {self.device}")
+        return timeline.chain(tp["rows"], tp["counts"], legs, device=self.device.index, ctx=self.ctx, **kw)
+
     def timing(self):
         return self.ctx.last_timing()

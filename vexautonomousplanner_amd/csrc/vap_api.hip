@@ -3,6 +3,8 @@
 // Host-side runtime: context (device + stream + scratch arena + stage timers) and the entry points
 // that sequence the kernels of vap_kernels.hip.  There is deliberately no CPU implementation behind
 // any entry point: without a HIP device every call fails with VAP_ERR_NO_DEVICE.
+#include <climits>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -823,6 +825,54 @@ int vap_time_insert_events(vap_ctx *ctx, int B, int W, int M, int capacity_in, i
                                    (const double *)ctx->lut.ptr, d_meta, d_rows_in, d_counts_in, d_nodes_map_in, d_node_wait,
                                    d_action_t, d_action_wait, d_rows_out, d_counts_out, d_nodes_map_out, d_actions_map_out, d_flags, rt,
                                    d_node_turn, d_node_reverse, c->max_vel, c->max_acc, c->track_width));
+    return VAP_OK;
+}
+
+// rows of an in-place turn of `angle` radians: turn_profile(...).n of vap_turn.h, in fp64 so that the caller can bound it
+static double turn_rows_host(double angle, double vmax, double amax, double tw, double dt)
+{
+    const double arc = std::fabs(angle) * tw / 2;
+    double t_acc = vmax / amax, total;
+    const double d_acc = 0.5 * amax * (t_acc * t_acc);
+    if (2 * d_acc > arc) total = 2 * std::sqrt(arc / amax);
+    else total = 2 * t_acc + (arc - 2 * d_acc) / vmax;
+    return std::ceil((total + dt) / dt);
+}
+
+int vap_routine_timeline(vap_ctx *ctx, int R, int M, int L, int capacity_in, int capacity_out, double time_step,
+                         const vap_constraints *c, double turn_min, const double *d_rows_in, const int *d_counts_in,
+                         int counts_stride, const int *d_leg, const int *d_n_legs, const double *d_dwell,
+                         const double *d_start_heading, double *d_rows_out, int *d_counts_out, int *d_map, double *d_seam,
+                         uint32_t *d_flags)
+{
+    if (R < 0 || M < 1 || L < 0 || capacity_in < 0 || capacity_out < 0 || counts_stride < 1)
+        return vap_fail(VAP_ERR_INVALID, "bad shape R=%d M=%d L=%d capacity_in=%d capacity_out=%d counts_stride=%d", R, M, L,
+                        capacity_in, capacity_out, counts_stride);
+    if (M > VAP_TIMELINE_MAX_LEGS) return vap_fail(VAP_ERR_UNSUPPORTED, "M=%d: at most %d legs per routine", M, VAP_TIMELINE_MAX_LEGS);
+    if (!(time_step > 0) || !std::isfinite(time_step)) return vap_fail(VAP_ERR_INVALID, "time_step must be positive and finite");
+    if (!(turn_min >= 0) || !std::isfinite(turn_min)) return vap_fail(VAP_ERR_INVALID, "turn_min must be >= 0 and finite");
+    if (!c) return vap_fail(VAP_ERR_INVALID, "null constraints");
+    if (!(c->max_vel > 0 && c->max_acc > 0 && c->track_width > 0) || !std::isfinite(c->max_vel) || !std::isfinite(c->max_acc) ||
+        !std::isfinite(c->track_width))
+        return vap_fail(VAP_ERR_INVALID, "in-place turns need a positive, finite max_vel, max_acc and track_width");
+    if (R > 0 && (!d_leg || !d_counts_out || !d_map || !d_seam || (!d_rows_out && capacity_out > 0)))
+        return vap_fail(VAP_ERR_INVALID, "null leg / rows / counts / map / seam output");
+    if (R > 0 && L > 0 && (!d_counts_in || (!d_rows_in && capacity_in > 0))) return vap_fail(VAP_ERR_INVALID, "null input rows or counts");
+    if (d_rows_out && d_rows_out == d_rows_in) return vap_fail(VAP_ERR_INVALID, "the rows move: d_rows_out must not be d_rows_in");
+    if ((((uintptr_t)d_rows_in) | ((uintptr_t)d_rows_out)) & 15) return vap_fail(VAP_ERR_INVALID, "the rows move 16 bytes at a time: misaligned row pointer");
+    if ((long long)R * M > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "R * M above INT_MAX");
+    // the longest turn a usable pair of headings can ask for is a full one (headings within [-2 pi, 2 pi], one wrap step)
+    if (!(turn_rows_host(2 * M_PI, c->max_vel, c->max_acc, c->track_width, time_step) <= 1048576.0))
+        return vap_fail(VAP_ERR_UNSUPPORTED, "a turn of more than 2^20 rows at this time step");
+    VAP_TRY(vap_set_device(ctx));
+    if (R == 0) return VAP_OK;
+    vap::TimelineArgs a;
+    a.R = R; a.M = M; a.L = L; a.cap_in = capacity_in; a.cap_out = capacity_out; a.counts_stride = counts_stride;
+    a.dt = time_step; a.turn_min = turn_min; a.max_vel = c->max_vel; a.max_acc = c->max_acc; a.track_width = c->track_width;
+    a.rows_in = d_rows_in; a.counts_in = d_counts_in; a.leg = d_leg; a.n_legs = d_n_legs; a.dwell = d_dwell;
+    a.start_heading = d_start_heading; a.rows_out = d_rows_out; a.counts_out = d_counts_out; a.map = d_map; a.seam = d_seam;
+    a.flags = d_flags;
+    HIP_TRY(vap::launch_routine_timeline(ctx->stream, a));
     return VAP_OK;
 }
 

@@ -136,6 +136,19 @@ hipError_t launch_time_waits(hipStream_t st, int B, int W, int M, int cap_in, in
                              double *rows_out, int *counts_out, int *nodes_out, int *actions_out, uint32_t *flags,
                              RouteTables rt = RouteTables(), const double *node_turn = nullptr, const int *node_reverse = nullptr,
                              double max_vel = 0, double max_acc = 0, double track_width = 0);
+// the legs of a routine chained into one timeline (vap_timeline.hip; vap_routine_timeline)
+struct TimelineArgs {
+    int R, M, L, cap_in, cap_out, counts_stride;
+    double dt, turn_min, max_vel, max_acc, track_width;
+    const double *rows_in;          // [L][cap_in][8]
+    const int *counts_in, *leg, *n_legs;
+    const double *dwell, *start_heading;
+    double *rows_out;               // [R][cap_out][8]
+    int *counts_out, *map;          // [R][2], [R][M][3]
+    double *seam;                   // [R][M][3]
+    uint32_t *flags;                // [R] or NULL
+};
+hipError_t launch_routine_timeline(hipStream_t st, const TimelineArgs &a);
 hipError_t launch_eval(hipStream_t st, int W, const double *seg, double t_max, int order, int n, const double *t,
                        double *out);
 hipError_t launch_basis(hipStream_t st, int order, int n, const double *t, double *out);   // out [n][6]

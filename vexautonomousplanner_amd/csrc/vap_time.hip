@@ -22,6 +22,7 @@
 // All arithmetic is fp64 in the reference's order; only the velocity row is read in the batch dtype.
 #include "vap_device.h"
 #include "vap_kernels.h"
+#include "vap_turn.h"
 
 namespace vap {
 
@@ -758,38 +759,6 @@ hipError_t launch_time_profile(hipStream_t st, bool f64, int B, int W, int S, co
 //              two maps (row counts at the moment of the event, MPG:528, 549);
 //   all        copy row i to i + (rows inserted before it) and write the inserted rows.
 // ------------------------------------------------------------------------------------------------
-// MPG:319-346 motion_profile_angle over ODM:4-69 generate_trapezoidal_profile: the rows an in-place turn inserts
-struct TurnProfile {
-    double t_acc, vpeak, total_time, amax, half_tw, sign;
-    int n;
-};
-__device__ inline TurnProfile turn_profile(double angle, double vmax, double amax, double tw, double dt)
-{
-    TurnProfile p;
-    const double arc = fabs(angle) * tw / 2;
-    p.t_acc = vmax / amax;
-    const double d_acc = 0.5 * amax * (p.t_acc * p.t_acc);
-    p.vpeak = vmax;
-    if (2 * d_acc > arc) {
-        p.t_acc = sqrt(arc / amax);
-        p.vpeak = amax * p.t_acc;
-        p.total_time = 2 * p.t_acc;
-    } else {
-        p.total_time = 2 * p.t_acc + (arc - 2 * d_acc) / p.vpeak;
-    }
-    p.amax = amax;
-    p.half_tw = tw / 2;
-    p.sign = angle > 0 ? -1.0 : 1.0;
-    p.n = (int)ceil((p.total_time + dt) / dt);   // np.arange(0, total_time + dt, dt)
-    return p;
-}
-__device__ inline double turn_velocity(const TurnProfile &p, double tt)
-{
-    if (tt <= p.t_acc) return p.amax * tt;
-    if (tt <= p.total_time - p.t_acc) return p.vpeak;
-    return p.vpeak - p.amax * (tt - (p.total_time - p.t_acc));
-}
-
 struct TimeEventInputs {
     const double *node_wait = nullptr;   // [B][W] seconds
     const double *node_turn = nullptr;   // [B][W] degrees

@@ -1,0 +1,136 @@
+"""The legs of a routine chained into one timeline, with in-place turns and dwells (vap_routine_timeline, include/vap.h).
+
+``plan.routine`` returns a visiting order and one seed route per leg, ``search.refine`` improves each leg by itself, and
+``time_profile`` gives every leg rows that start at its own time zero.  ``chain`` puts them back together: per slot of a
+routine the turn on the spot from the heading the robot arrives with to the heading the next leg starts with (the
+reference's own turn, MPG:319-346 and 487-507), the leg's rows at their place in time and distance, and the rows of the
+dwell at the site.  The result has the rows and counts of ``time_profile``, so it goes where those go: ``footprint.
+clearance`` (does the turning robot clear the post beside the site?), ``footprint.conflicts`` (a later leg against the
+partner at its real start time), ``tracking.rollouts`` and ``plan.occupancy``.
+
+Nothing here reads the device: the visiting order may stay a device tensor from ``plan.order`` to the chained rows.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from .footprint import _side
+from .synth import DEFAULT_CONSTRAINTS
+
+MAX_LEGS = _lib.TIMELINE_MAX_LEGS
+FLAGS = {"truncated": _lib.FLAG_TRUNCATED, "bad_route": _lib.FLAG_BAD_ROUTE}
+
+
+def turn_rows(angle, constraints=DEFAULT_CONSTRAINTS, dt=0.01):
+    """Rows of an in-place turn of ``angle`` radians under ``constraints`` (MPG:319-346 over one_dim_mp_generator.py:4-69):
+    the trapezoid's duration / dt + 1, rounded up."""
+    c = _lib.make_constraints(constraints)
+    arc = abs(float(angle)) * c.track_width / 2
+    t_acc = c.max_vel / c.max_acc
+    d_acc = 0.5 * c.max_acc * (t_acc * t_acc)
+    if 2 * d_acc > arc:
+        total = 2 * math.sqrt(arc / c.max_acc)
+    else:
+        total = 2 * t_acc + (arc - 2 * d_acc) / c.max_vel
+    return int(math.ceil((total + dt) / dt))
+
+
+def _device_array(a, dev, dtype, shape, what):
+    """``a`` as a contiguous device tensor of ``dtype`` and ``shape``: a device tensor is used as it is (converted on the
+    device if it must be), host data is uploaded.  Returns (tensor, whether it came from the host)."""
+    host = not isinstance(a, torch.Tensor)
+    if host:
+        np_dt = np.int32 if dtype == torch.int32 else np.float64
+        a = torch.as_tensor(np.ascontiguousarray(a, dtype=np_dt), device=dev)
+    elif a.device != dev:
+        raise ValueError(f"{what} is on {a.device}, the rows on {dev}")
+    if tuple(a.shape) != shape:
+        raise ValueError(f"{what} must be {shape}, got {tuple(a.shape)}")
+    return a.to(dtype).contiguous(), host
+
+
+def chain(rows, counts, legs, dwell=None, start_heading=None, n_legs=None, constraints=DEFAULT_CONSTRAINTS, dt=0.01,
+          turn_min=math.radians(1.0), capacity_rows=None, out=None, device=0, ctx=None):
+    """Chain legs into routines (vap_routine_timeline): per used slot m of routine r, [turn m] [leg m] [dwell m].
+
+      rows, counts   the L legs as ``time_profile`` returns them: (L, capacity_in, 8) fp64 device tensor (used in place) or
+                     host array (uploaded once), with (L, k) / (L,) counts (column 0 = rows).  All on the time step ``dt``
+      legs           (R, M) int, device tensor or host array: the leg driven in slot m of routine r, 1 <= M <= 32.  A leg
+                     may serve several slots and routines; an index outside [0, L) (the -1 of an infeasible ``plan.order``)
+                     makes the routine bad
+      dwell          (R, M) seconds spent at the end of slot m, device or host; None = none
+      start_heading  (R,) the heading the robot stands at before slot 0 (it turns to leg 0's first heading), NaN = none;
+                     None = none
+      n_legs         (R,) slots used (the rest is ignored); None = M
+      constraints    max_vel, max_acc and track_width shape the turn's trapezoid
+      turn_min       a change of heading below this many radians inserts no turn
+      capacity_rows  rows per routine in the output; None: M capacity_in + M half turns + the longest routine's dwell rows,
+                     which needs ``dwell`` on the host: with a device tensor it must be given
+      out            optional dict of tensors of the shapes below to fill (rows, counts, map, seam, flags)
+    Returns a dict of device tensors: rows (R, capacity_rows, 8), counts (R, 2) int32 {rows, slots used}, map (R, M, 3)
+    int32 (first output row of slot m's turn, leg and dwell block; -1 for an unused slot or a bad routine), seam (R, M, 3)
+    (heading left over after the turn; x and y gap between the row in front and the leg's first row), flags (R,) uint32
+    (FLAGS: bad_route, truncated), arrival (R, M) seconds at which site m is reached (NaN as map is -1) and duration (R,)
+    seconds (NaN for a bad routine).  A truncated routine's rows below capacity_rows are those of an ample call; its map
+    is not cut.  Work runs on torch's current stream and is not synchronised."""
+    dt, turn_min = float(dt), float(turn_min)
+    if not (dt > 0 and math.isfinite(dt)):
+        raise ValueError(f"dt must be positive and finite (got {dt!r})")
+    if not (turn_min >= 0 and math.isfinite(turn_min)):
+        raise ValueError(f"turn_min must be >= 0 and finite (got {turn_min!r})")
+    c = _lib.make_constraints(constraints)
+    rows, counts, single, dev = _side(rows, counts, None, device, "legs")
+    if single:
+        raise ValueError("rows must be (L, capacity_in, 8): a batch of legs")
+    L, cap_in = int(rows.shape[0]), int(rows.shape[1])
+    shape = tuple(legs.shape) if hasattr(legs, "shape") else np.shape(legs)
+    if len(shape) != 2 or not 1 <= shape[1] <= MAX_LEGS:
+        raise ValueError(f"legs must be (R, M) with 1 <= M <= {MAX_LEGS}, got {tuple(shape)}")
+    R, M = int(shape[0]), int(shape[1])
+    legs, _ = _device_array(legs, dev, torch.int32, (R, M), "legs")
+    dwell_host = None
+    if dwell is not None:
+        if not isinstance(dwell, torch.Tensor):
+            dwell_host = np.ascontiguousarray(dwell, dtype=np.float64)
+        dwell, _ = _device_array(dwell, dev, torch.float64, (R, M), "dwell")
+    if start_heading is not None:
+        start_heading, _ = _device_array(start_heading, dev, torch.float64, (R,), "start_heading")
+    if n_legs is not None:
+        n_legs, _ = _device_array(n_legs, dev, torch.int32, (R,), "n_legs")
+    if capacity_rows is None:
+        if dwell is not None and dwell_host is None:
+            raise ValueError("capacity_rows is required when dwell is a device tensor: its rows cannot be counted "
+                             "without reading the device")
+        capacity_rows = M * cap_in + M * turn_rows(math.pi, c, dt)
+        if dwell_host is not None and dwell_host.size:
+            with np.errstate(invalid="ignore"):
+                steps = np.where(dwell_host > 0, np.floor(np.where(dwell_host > 0, dwell_host, 0.0) / dt), 0.0)
+            capacity_rows += int(min(steps.sum(axis=1).max(), 2.0 ** 31))
+    capacity_rows = int(capacity_rows)
+    if capacity_rows < 0:
+        raise ValueError(f"capacity_rows must be >= 0 (got {capacity_rows})")
+    res = {} if out is None else out
+    shapes = {"rows": ((R, capacity_rows, 8), torch.float64), "counts": ((R, 2), torch.int32), "map": ((R, M, 3), torch.int32),
+              "seam": ((R, M, 3), torch.float64), "flags": ((R,), torch.int32)}
+    for k, (shp, dty) in shapes.items():
+        t = res.get(k)
+        if t is None or tuple(t.shape) != shp or t.dtype != dty or t.device != dev or not t.is_contiguous():
+            res[k] = torch.empty(shp, dtype=dty, device=dev)
+    res["flags"].zero_()                          # the call ORs its bits in
+    if ctx is None:
+        ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    _lib.check(ctx._L.vap_routine_timeline(
+        ctx.handle, R, M, L, cap_in, capacity_rows, dt, C.byref(c), turn_min, ptr(rows), ptr(counts), int(counts.shape[1]),
+        ptr(legs), ptr(n_legs), ptr(dwell), ptr(start_heading), ptr(res["rows"]), ptr(res["counts"]), ptr(res["map"]),
+        ptr(res["seam"]), ptr(res["flags"])), "vap_routine_timeline")
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    at = res["map"][:, :, 2]
+    res["arrival"] = torch.where(at >= 0, at.to(torch.float64) * dt, nan)
+    bad = (res["flags"] & _lib.FLAG_BAD_ROUTE) != 0
+    res["duration"] = torch.where(bad, nan, res["counts"][:, 0].to(torch.float64) * dt)
+    return res
