@@ -39,6 +39,7 @@ def main():
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import torch
+    from _timing import timed
     from footprint_bench import field_scene
     from vexautonomousplanner_amd import footprint as fp
     from vexautonomousplanner_amd import plan
@@ -50,29 +51,15 @@ def main():
     out = {"grid": [ny, nx], "cell_ft": CELL, "radius_ft": RADIUS, "margin_ft": MARGIN, "waypoints": W, "reps": a.reps,
            "rounds": a.rounds}
 
-    def timed(fn):
-        fn()                                                   # warm-up: code objects, buffers
-        torch.cuda.synchronize()
-        ts = []
-        for _ in range(a.rounds):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.reps):
-                fn()
-            e1.record()
-            e1.synchronize()
-            ts.append(e0.elapsed_time(e1) / a.reps)
-        return float(np.median(ts)), [float(t) for t in ts]
-
     gbuf = {}
-    out["grid_ms"], out["grid_rounds_ms"] = timed(lambda: plan.clearance_grid(scene, CELL, RADIUS, MARGIN, out=gbuf))
+    out["grid_ms"], out["grid_rounds_ms"] = timed(lambda: plan.clearance_grid(scene, CELL, RADIUS, MARGIN, out=gbuf), a.reps, a.rounds)
     out["free_cells"] = int(gbuf["free"].sum().item())
     rng = np.random.default_rng(7)
     for R in (256, 4096):
         pts = rng.uniform(-5.5, 5.5, (R, 2, 2))
         starts, goals = torch.as_tensor(pts[:, 0].copy(), device="cuda:0"), torch.as_tensor(pts[:, 1].copy(), device="cuda:0")
         buf = {}
-        ms, rounds = timed(lambda: plan.seeds(starts, goals, scene, W, RADIUS, cell=CELL, margin=MARGIN, out=buf))
+        ms, rounds = timed(lambda: plan.seeds(starts, goals, scene, W, RADIUS, cell=CELL, margin=MARGIN, out=buf), a.reps, a.rounds)
         out[f"r{R}_seeds_ms"], out[f"r{R}_seeds_rounds_ms"] = ms, rounds
         out[f"r{R}_feasible"] = int(buf["feasible"].sum().item())
         out[f"r{R}_flags_or"] = int(np.bitwise_or.reduce(buf["flags"].cpu().numpy()))

@@ -24,7 +24,7 @@ rev[:, -1] = False
 turn[:, -1] = turn[:, 0] = 0.0
 
 
-def timed(fn, n=5):
+def stage_times(fn, n=5):
     fn()
     torch.cuda.synchronize()
     gen.ctx.set_timing(True)
@@ -38,10 +38,10 @@ def timed(fn, n=5):
 
 
 out = {}
-print("plain ", timed(lambda: out.update(p=gen.profile(wp, DEFAULT_CONSTRAINTS, samples=S))))
-print("routes", timed(lambda: out.update(r=gen.profile_routes(wp, node_reverse=rev, node_turn=turn, constraints=DEFAULT_CONSTRAINTS, samples=S))),
+print("plain ", stage_times(lambda: out.update(p=gen.profile(wp, DEFAULT_CONSTRAINTS, samples=S))))
+print("routes", stage_times(lambda: out.update(r=gen.profile_routes(wp, node_reverse=rev, node_turn=turn, constraints=DEFAULT_CONSTRAINTS, samples=S))),
       "splines per route: mean %.2f max %d" % (float(out["r"]["spline_counts"].float().mean()), int(out["r"]["spline_counts"].max())))
 none = np.zeros((B, W), dtype=bool)
-print("routes without splits", timed(lambda: out.update(r0=gen.profile_routes(wp, node_reverse=none, node_turn=np.zeros((B, W)), constraints=DEFAULT_CONSTRAINTS, samples=S))))
+print("routes without splits", stage_times(lambda: out.update(r0=gen.profile_routes(wp, node_reverse=none, node_turn=np.zeros((B, W)), constraints=DEFAULT_CONSTRAINTS, samples=S))))
 same = all(torch.equal(out["p"][k], out["r0"][k]) for k in ("x", "y", "heading", "curvature", "velocity"))
 print("routes without splits == plain path, bit for bit:", same)

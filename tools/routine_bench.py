@@ -33,6 +33,7 @@ def main():
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import torch
+    from _timing import timed
     from footprint_bench import field_scene
     from vexautonomousplanner_amd import footprint as fp
     from vexautonomousplanner_amd import plan
@@ -43,20 +44,6 @@ def main():
     ny, nx = plan.grid_shape(scene, CELL)
     out = {"grid": [ny, nx], "cell_ft": CELL, "radius_ft": RADIUS, "margin_ft": MARGIN, "waypoints": W, "points": POINTS,
            "reps": a.reps, "rounds": a.rounds}
-
-    def timed(fn):
-        fn()                                                   # warm-up: code objects, buffers
-        torch.cuda.synchronize()
-        ts = []
-        for _ in range(a.rounds):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.reps):
-                fn()
-            e1.record()
-            e1.synchronize()
-            ts.append(e0.elapsed_time(e1) / a.reps)
-        return float(np.median(ts)), [float(t) for t in ts]
 
     # random points on free cells
     free = plan.clearance_grid(scene, CELL, RADIUS, MARGIN)["free"].cpu().numpy()
@@ -72,8 +59,10 @@ def main():
         pts = torch.as_tensor(cand[:R * POINTS].reshape(R, POINTS, 2).copy(), device="cuda:0")
         starts, goals = pts[:, a_idx].reshape(-1, 2).contiguous(), pts[:, b_idx].reshape(-1, 2).contiguous()
         tbuf, sbuf = {}, {}
-        t_ms, t_rounds = timed(lambda: plan.travel(pts, scene, RADIUS, cell=CELL, margin=MARGIN, waypoints=W, out=tbuf))
-        s_ms, s_rounds = timed(lambda: plan.seeds(starts, goals, scene, W, RADIUS, cell=CELL, margin=MARGIN, out=sbuf))
+        t_ms, t_rounds = timed(lambda: plan.travel(pts, scene, RADIUS, cell=CELL, margin=MARGIN, waypoints=W, out=tbuf),
+                               a.reps, a.rounds)
+        s_ms, s_rounds = timed(lambda: plan.seeds(starts, goals, scene, W, RADIUS, cell=CELL, margin=MARGIN, out=sbuf),
+                               a.reps, a.rounds)
         same = torch.equal(tbuf["waypoints"][:, a_idx, b_idx].reshape(-1, W, 2).view(torch.int64), sbuf["waypoints"].view(torch.int64))
         out[f"r{R}"] = {"pairs": int(starts.shape[0]), "travel_ms": t_ms, "travel_rounds_ms": t_rounds, "seeds_ms": s_ms,
                         "seeds_rounds_ms": s_rounds, "ratio": s_ms / t_ms, "same_bits": bool(same),
@@ -81,7 +70,7 @@ def main():
     for R in (1, 4096):
         cost = torch.as_tensor(rng.uniform(1.0, 20.0, (R, POINTS, POINTS)), device="cuda:0")
         obuf = {}
-        o_ms, o_rounds = timed(lambda: plan.order(cost, out=obuf))
+        o_ms, o_rounds = timed(lambda: plan.order(cost, out=obuf), a.reps, a.rounds)
         out[f"order_r{R}"] = {"sites": POINTS - 1, "order_ms": o_ms, "order_rounds_ms": o_rounds}
     print(json.dumps(out))
     if a.json:

@@ -34,6 +34,7 @@ def main():
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import torch
+    from _timing import timed
     from vexautonomousplanner_amd import timeline
     from vexautonomousplanner_amd.batch import BatchedTrajectoryGenerator
     from vexautonomousplanner_amd.synth import DEFAULT_CONSTRAINTS, make_waypoints
@@ -46,20 +47,6 @@ def main():
     L = int(tp["rows"].shape[0])
     out = {"legs": L, "leg_rows": int(tp["counts"][:, 0].sum().item()), "slots": M, "dwell_s": DWELL, "dt": DT, "reps": a.reps,
            "rounds": a.rounds}
-
-    def timed(fn):
-        fn()                                                   # warm-up: code objects, buffers
-        torch.cuda.synchronize()
-        ts = []
-        for _ in range(a.rounds):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.reps):
-                fn()
-            e1.record()
-            e1.synchronize()
-            ts.append(e0.elapsed_time(e1) / a.reps)
-        return float(np.median(ts)), [float(t) for t in ts]
 
     rng = np.random.default_rng(7)
     for R in (1, 1024):
@@ -78,10 +65,10 @@ def main():
         cap = int(d["rows"].shape[1])
         call = lambda: timeline.chain(tp["rows"], tp["counts"], legs, dwell=dwell_d, start_heading=start, dt=DT, capacity_rows=cap,
                                       out=buf, ctx=gen.ctx)
-        c_ms, c_rounds = timed(call)
+        c_ms, c_rounds = timed(call, a.reps, a.rounds)
         src = torch.empty(nbytes // 2, dtype=torch.uint8, device=gen.device)
         dst = torch.empty_like(src)
-        p_ms, p_rounds = timed(lambda: dst.copy_(src))
+        p_ms, p_rounds = timed(lambda: dst.copy_(src), a.reps, a.rounds)
         out[f"r{R}"] = {"rows_in": rows_in, "rows_out": rows_out, "bytes": nbytes, "chain_ms": c_ms, "chain_rounds_ms": c_rounds,
                         "chain_gbs": nbytes / c_ms / 1e6, "copy_ms": p_ms, "copy_rounds_ms": p_rounds, "copy_gbs": nbytes / p_ms / 1e6}
     print(json.dumps(out))

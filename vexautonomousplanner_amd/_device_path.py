@@ -7,10 +7,7 @@ import numpy as np
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+from ._call import ptr
 
 
 def basis_rows(order, ts, device=0):
@@ -68,9 +65,9 @@ class DevicePath:
         d["fd"] = torch.empty((1, W, 2), dtype=torch.float64, device=dev)
         d["sd"] = torch.empty((1, W, 2), dtype=torch.float64, device=dev)
         self.ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        st = self._L.vap_fit_ex(self.ctx.handle, _lib.VAP_F64, 1, W, _ptr(d["wp"]), _ptr(d["tin"]), _ptr(d["tout"]),
-                                _ptr(d["first"]), _ptr(d["second"]), _ptr(d["stan"]), _ptr(d["etan"]), _ptr(d["seg"]),
-                                _ptr(d["seglen"]), _ptr(d["fd"]), _ptr(d["sd"]), _ptr(d["meta"]), _ptr(d["flags"]))
+        st = self._L.vap_fit_ex(self.ctx.handle, _lib.VAP_F64, 1, W, ptr(d["wp"]), ptr(d["tin"]), ptr(d["tout"]),
+                                ptr(d["first"]), ptr(d["second"]), ptr(d["stan"]), ptr(d["etan"]), ptr(d["seg"]),
+                                ptr(d["seglen"]), ptr(d["fd"]), ptr(d["sd"]), ptr(d["meta"]), ptr(d["flags"]))
         if st == _lib.VAP_ERR_INVALID:
             return False
         _lib.check(st, "vap_fit_ex")
@@ -89,8 +86,8 @@ class DevicePath:
         d = self._d
         d["lut"] = torch.empty((1, _lib.LUT_SAMPLES), dtype=torch.float64, device=self.device)
         self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self._L.vap_build_lut(self.ctx.handle, 1, self.W, _ptr(d["seg"]), _ptr(d["lut"]),
-                                         _ptr(d["meta"]), _ptr(d["flags"])), "vap_build_lut")
+        _lib.check(self._L.vap_build_lut(self.ctx.handle, 1, self.W, ptr(d["seg"]), ptr(d["lut"]),
+                                         ptr(d["meta"]), ptr(d["flags"])), "vap_build_lut")
         self.lut = d["lut"][0].cpu().numpy()
         self.total = float(self.lut[-1])
 
@@ -125,13 +122,13 @@ class DevicePath:
         c = _lib.make_constraints(constraints)
         self.ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
         L = self._L
-        _lib.check(L.vap_sample(self.ctx.handle, _lib.VAP_F64, 1, self.W, cap, float(dd), _ptr(d["seg"]),
-                                _ptr(d["lut"]), _ptr(d["meta"]), _ptr(outs["x"]), _ptr(outs["y"]),
-                                _ptr(outs["heading"]), _ptr(outs["curvature"]), _ptr(outs["dtheta"]),
-                                _ptr(d["flags"])), "vap_sample")
+        _lib.check(L.vap_sample(self.ctx.handle, _lib.VAP_F64, 1, self.W, cap, float(dd), ptr(d["seg"]),
+                                ptr(d["lut"]), ptr(d["meta"]), ptr(outs["x"]), ptr(outs["y"]),
+                                ptr(outs["heading"]), ptr(outs["curvature"]), ptr(outs["dtheta"]),
+                                ptr(d["flags"])), "vap_sample")
         _lib.check(L.vap_velocity_pass(self.ctx.handle, _lib.VAP_F64, 1, cap, C.byref(c), float(start_vel),
-                                       float(end_vel), _ptr(d["meta"]), _ptr(outs["curvature"]),
-                                       _ptr(outs["dtheta"]), None, _ptr(outs["velocity"]), _ptr(d["flags"])),
+                                       float(end_vel), ptr(d["meta"]), ptr(outs["curvature"]),
+                                       ptr(outs["dtheta"]), None, ptr(outs["velocity"]), ptr(d["flags"])),
                    "vap_velocity_pass")
         n = int(d["meta"][0, 3].item())
         if int(d["flags"][0].item()) & _lib.FLAG_NOCONVERGE:
@@ -143,8 +140,8 @@ class DevicePath:
             self.ctx.set_option(_lib.OPT_VELOCITY_KERNEL, _lib.VELOCITY_SEQ_FAST)
             try:
                 _lib.check(L.vap_velocity_pass(self.ctx.handle, _lib.VAP_F64, 1, cap, C.byref(c), float(start_vel),
-                                               float(end_vel), _ptr(d["meta"]), _ptr(outs["curvature"]),
-                                               _ptr(outs["dtheta"]), None, _ptr(outs["velocity"]), _ptr(d["flags"])),
+                                               float(end_vel), ptr(d["meta"]), ptr(outs["curvature"]),
+                                               ptr(outs["dtheta"]), None, ptr(outs["velocity"]), ptr(d["flags"])),
                            "vap_velocity_pass (sequential sweep after a timed-out wait)")
             finally:
                 self.ctx.set_option(_lib.OPT_VELOCITY_KERNEL, _lib.VELOCITY_AUTO)

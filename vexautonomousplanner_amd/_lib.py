@@ -205,10 +205,6 @@ def lib():
     L.vap_plan_order.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     L.vap_routine_timeline.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(Constraints),
                                        C.c_double, vp, vp, C.c_int] + [vp] * 9
-    for name in EXPORTS:
-        fn = getattr(L, name)
-        if fn.restype is C.c_int and name not in ("vap_version", "vap_device_count"):
-            pass
     _lib = L
     return L
 

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._call import buffers, ptr
 from .synth import DEFAULT_CONSTRAINTS, END_VEL, START_VEL
 
 FIELDS = ("x", "y", "heading", "curvature", "velocity")
@@ -114,7 +115,7 @@ class BatchedTrajectoryGenerator:
 
         def p(name):
             t = res.get(name) if (name in want or name == "velocity") else None
-            return C.c_void_p(t.data_ptr()) if t is not None else None
+            return ptr(t)
 
         self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
         st = self._L.vap_profile_batch(self.ctx.handle, self.vdtype, B, W, S, ddv,
@@ -215,8 +216,7 @@ class BatchedTrajectoryGenerator:
 
         def p(name):
             t = res.get(name) if (name in want or name == "velocity") else None
-            return C.c_void_p(t.data_ptr()) if t is not None else None
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+            return ptr(t)
         self.ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
         st = self._L.vap_profile_routes(self.ctx.handle, self.vdtype, B, W, S, ddv, max_splines, ptr(wp), ptr(d_rev), ptr(d_turn),
                                         ptr(d_tan), ptr(d_mag), C.byref(c), float(start_vel), float(end_vel), p("x"), p("y"),
@@ -263,7 +263,7 @@ class BatchedTrajectoryGenerator:
             d_rev = torch.tensor(np.asarray(node_reverse).astype(bool).astype(np.int32).reshape(B, W), device=self.device)
         st = self._L.vap_time_profile_routes(self.ctx.handle, self.vdtype, B, W, S, C.c_void_p(meta.data_ptr()),
                                              C.c_void_p(vel.data_ptr()), C.byref(c), float(dt), int(capacity_rows),
-                                             C.c_void_p(d_rev.data_ptr()) if d_rev is not None else None,
+                                             ptr(d_rev),
                                              C.c_void_p(res["rows"].data_ptr()), C.c_void_p(res["counts"].data_ptr()),
                                              C.c_void_p(res["nodes_map"].data_ptr()), C.c_void_p(result["flags"].data_ptr()))
         _lib.check(st, "vap_time_profile_routes")
@@ -325,7 +325,6 @@ class BatchedTrajectoryGenerator:
         ap_k = torch.empty((B, max(M, 1)), dtype=torch.int32, device=dev)
         c = _lib.make_constraints(constraints)
         self.ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         _lib.check(self._L.vap_route_limits(self.ctx.handle, self.vdtype, B, W, M, S, None, ptr(meta), ptr(d["mv"]), ptr(d["ma"]),
                                             ptr(d["stop"]), ptr(d["ap_t"]), ptr(d["ap_mv"]), ptr(d["ap_ma"]), ptr(d["ap_stop"]),
                                             C.byref(c), float(end_vel), ptr(vcap), ptr(acc_f), ptr(acc_b), ptr(dec_b), ptr(node_k),
@@ -385,7 +384,6 @@ class BatchedTrajectoryGenerator:
         # one upload for the three float arrays
         fl_dev = torch.tensor(np.concatenate([wait.ravel(), ap_t.ravel(), ap_w.ravel()]), device=dev)
         d_wait, d_apt, d_apw = fl_dev[:B * W], fl_dev[B * W:B * W + ap_t.size], fl_dev[B * W + ap_t.size:]
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         self.ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(self._L.vap_time_insert_events(self.ctx.handle, B, W, M, cap_in, cap_out, float(dt), C.byref(c),
                                                   ptr(result["meta"]), ptr(rows_in), ptr(counts_in), ptr(nodes_in), ptr(d_wait),
@@ -422,14 +420,9 @@ class BatchedTrajectoryGenerator:
             raise ValueError(f"queries must be ({B}, Q, 2) or (Q, 2), got {tuple(q.shape)}")
         q = q.contiguous()
         m = _lib.closest_mode(mode)
-        res = {} if out is None else out
         shapes = {"parameter": (B, Q), "point": (B, Q, 2), "distance": (B, Q), "arc_length": (B, Q), "cross_track": (B, Q)}
-        for k, shp in shapes.items():
-            t = res.get(k)
-            if t is None or tuple(t.shape) != shp or t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous():
-                res[k] = torch.empty(shp, dtype=torch.float64, device=self.device)
+        res = buffers(out, {k: (shp, torch.float64) for k, shp in shapes.items()}, self.device)
         res["flags"] = result["flags"].clone()
-        ptr = lambda t: C.c_void_p(t.data_ptr())
         self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
         _lib.check(self._L.vap_closest_points(self.ctx.handle, B, W, Q, m, shared, ptr(q), ptr(res["parameter"]),
                                               ptr(res["point"]), ptr(res["distance"]), ptr(res["arc_length"]),

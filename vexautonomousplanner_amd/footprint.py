@@ -16,12 +16,11 @@ circle (ids P..P+C-1) is defined in include/vap.h; a row's clearance is the mini
 The check is discrete at the rows' dt: motion between rows is not swept; pass ``margin > 0`` for a guard band (one 10 ms
 row moves at most max_vel * dt, 0.04 ft at 4 ft/s).
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
+from ._call import buffers, context_for, dptr, ptr, time_rows
 
 # gui/path.py:366-367: the 2000 px field image spans 12.1090395251 ft
 FIELD_FT = 12.1090395251
@@ -136,10 +135,6 @@ class Scene:
         raise ValueError(f"no element {eid}")
 
 
-def _dptr(a):
-    return a.ctypes.data_as(_lib.dp) if a is not None and a.size else None
-
-
 def clearance(rows, counts, footprint, scene, margin=0.0, per_row=False, out=None, device=0, ctx=None, cull=True):
     """Footprint clearance of a batch of time-domain rows (vap_footprint_clearance).
 
@@ -160,52 +155,19 @@ def clearance(rows, counts, footprint, scene, margin=0.0, per_row=False, out=Non
     if not isinstance(scene, Scene):
         raise TypeError("scene must be a footprint.Scene")
     foot = convex_polygon(footprint, "footprint")
-    if isinstance(rows, torch.Tensor):
-        dev = rows.device
-        if dev.type != "cuda" or rows.dtype != torch.float64:
-            raise ValueError("rows must be an fp64 tensor on a HIP device (or a host array)")
-    else:
-        dev = torch.device("cuda", device)
-        rows = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.float64), device=dev)
-    single = rows.dim() == 2
-    if single:
-        rows = rows.unsqueeze(0)
-    if rows.dim() != 3 or rows.shape[2] != 8:
-        raise ValueError(f"rows must be (B, capacity, 8) or (n, 8), got {tuple(rows.shape)}")
-    rows = rows.contiguous()
+    rows, counts, single, dev = time_rows(rows, counts, None, device)
     B, cap = int(rows.shape[0]), int(rows.shape[1])
-    if counts is None:
-        if not single:
-            raise ValueError("counts is needed for a batch of rows")
-        counts = torch.full((1, 1), cap, dtype=torch.int32, device=dev)
-    elif isinstance(counts, torch.Tensor):
-        counts = counts.to(device=dev, dtype=torch.int32)
-    else:
-        counts = torch.as_tensor(np.asarray(counts, dtype=np.int32), device=dev)
-    if counts.dim() < 2:
-        counts = counts.reshape(B, 1)
-    if counts.dim() != 2 or counts.shape[0] != B:
-        raise ValueError(f"counts must be ({B}, k) or ({B},), got {tuple(counts.shape)}")
-    counts = counts.contiguous()
-    res = {} if out is None else out
     shapes = {"min_clearance": ((B,), torch.float64), "min_row": ((B,), torch.int32), "min_element": ((B,), torch.int32),
               "first_row": ((B,), torch.int32), "n_below": ((B,), torch.int32)}
     if per_row:
         shapes["row_clearance"] = ((B, cap), torch.float64)
-    for k, (shp, dt) in shapes.items():
-        t = res.get(k)
-        if t is None or tuple(t.shape) != shp or t.dtype != dt or t.device != dev or not t.is_contiguous():
-            res[k] = torch.empty(shp, dtype=dt, device=dev)
-    if ctx is None:
-        ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    res = buffers(out, shapes, dev)
+    ctx = context_for(dev, ctx)
     ctx.set_option(_lib.OPT_FOOTPRINT_CULL, 1 if cull else 0)
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    field = scene.field
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     _lib.check(ctx._L.vap_footprint_clearance(
-        ctx.handle, B, cap, ptr(rows), ptr(counts), int(counts.shape[1]), len(foot), _dptr(foot),
-        _dptr(field), scene.n_polygons, scene.poly_start.ctypes.data_as(_lib.ip), _dptr(scene.poly_xy), scene.n_circles,
-        _dptr(scene.circles), float(margin), ptr(res.get("row_clearance") if per_row else None), ptr(res["min_clearance"]),
+        ctx.handle, B, cap, ptr(rows), ptr(counts), int(counts.shape[1]), len(foot), dptr(foot),
+        dptr(scene.field), scene.n_polygons, scene.poly_start.ctypes.data_as(_lib.ip), dptr(scene.poly_xy), scene.n_circles,
+        dptr(scene.circles), float(margin), ptr(res.get("row_clearance") if per_row else None), ptr(res["min_clearance"]),
         ptr(res["min_row"]), ptr(res["min_element"]), ptr(res["first_row"]), ptr(res["n_below"])), "vap_footprint_clearance")
     res["feasible"] = res["n_below"] == 0
     res["min_time"] = _time_at(rows, res["min_row"])
@@ -214,39 +176,6 @@ def clearance(rows, counts, footprint, scene, margin=0.0, per_row=False, out=Non
         for k in list(res):
             res[k] = res[k][0]
     return res
-
-
-def _side(rows, counts, dev, device, what):
-    """One side's rows and counts as contiguous device tensors: (rows (B, cap, 8), counts (B, k), single, device)."""
-    if isinstance(rows, torch.Tensor):
-        if rows.device.type != "cuda" or rows.dtype != torch.float64:
-            raise ValueError(f"{what}: rows must be an fp64 tensor on a HIP device (or a host array)")
-        if dev is not None and rows.device != dev:
-            raise ValueError(f"{what}: rows are on {rows.device}, the other side on {dev}")
-        dev = rows.device
-    else:
-        dev = dev if dev is not None else torch.device("cuda", device)
-        rows = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.float64), device=dev)
-    single = rows.dim() == 2
-    if single:
-        rows = rows.unsqueeze(0)
-    if rows.dim() != 3 or rows.shape[2] != 8:
-        raise ValueError(f"{what}: rows must be (B, capacity, 8) or (n, 8), got {tuple(rows.shape)}")
-    rows = rows.contiguous()
-    B = int(rows.shape[0])
-    if counts is None:
-        if not single:
-            raise ValueError(f"{what}: counts is needed for a batch of rows")
-        counts = torch.full((1, 1), int(rows.shape[1]), dtype=torch.int32, device=dev)
-    elif isinstance(counts, torch.Tensor):
-        counts = counts.to(device=dev, dtype=torch.int32)
-    else:
-        counts = torch.as_tensor(np.asarray(counts, dtype=np.int32), device=dev)
-    if counts.dim() < 2:
-        counts = counts.reshape(B, 1)
-    if counts.dim() != 2 or counts.shape[0] != B:
-        raise ValueError(f"{what}: counts must be ({B}, k) or ({B},), got {tuple(counts.shape)}")
-    return rows, counts.contiguous(), single, dev
 
 
 def _ccw_polygon(vertices, what):
@@ -291,37 +220,30 @@ def conflicts(rows_a, counts_a, footprint_a, rows_o, counts_o, footprint_o=None,
         raise ValueError(f"pairing must be 'all' or 'matched' (got {pairing!r})")
     shift_rows = int(shift_rows)
     given = [r.device for r in (rows_a, rows_o) if isinstance(r, torch.Tensor)]
-    rows_a, counts_a, single, dev = _side(rows_a, counts_a, given[0] if given else None, device, "side A")
-    rows_o, counts_o, _, _ = _side(rows_o, counts_o, dev, device, "side O")
+    rows_a, counts_a, single, dev = time_rows(rows_a, counts_a, given[0] if given else None, device, "side A")
+    rows_o, counts_o, _, _ = time_rows(rows_o, counts_o, dev, device, "side O")
     Ba, cap_a, Bo, cap_o = int(rows_a.shape[0]), int(rows_a.shape[1]), int(rows_o.shape[0]), int(rows_o.shape[1])
     if pairing == "matched" and Ba != Bo:
         raise ValueError(f"matched pairing needs as many routes on both sides (got {Ba} and {Bo})")
     P = 1 if pairing == "matched" else Bo
-    res = {} if out is None else out
     shapes = {"min_clearance": ((Ba,), torch.float64), "min_other": ((Ba,), torch.int32), "min_row": ((Ba,), torch.int32),
               "n_conflicts": ((Ba,), torch.int32), "first_row": ((Ba,), torch.int32)}
     if pairs:
         shapes.update(pair_clearance=((Ba, P), torch.float64), pair_row=((Ba, P), torch.int32),
                       pair_first_row=((Ba, P), torch.int32))
-    for k, (shp, dt) in shapes.items():
-        t = res.get(k)
-        if t is None or tuple(t.shape) != shp or t.dtype != dt or t.device != dev or not t.is_contiguous():
-            res[k] = torch.empty(shp, dtype=dt, device=dev)
+    res = buffers(out, shapes, dev)
     if Bo == 0:                                   # nothing to meet: the C-ABI call is a no-op
         res["min_clearance"].fill_(float("nan"))
         for k in ("min_other", "min_row", "first_row"):
             res[k].fill_(-1)
         res["n_conflicts"].zero_()
-    if ctx is None:
-        ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    ctx = context_for(dev, ctx)
     ctx.set_option(_lib.OPT_FOOTPRINT_CULL, 1 if cull else 0)
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     pp = lambda k: ptr(res[k]) if pairs else None
     _lib.check(ctx._L.vap_footprint_conflicts(
         ctx.handle, PAIRINGS[pairing], shift_rows, float(margin),
-        Ba, cap_a, ptr(rows_a), ptr(counts_a), int(counts_a.shape[1]), len(foot_a), _dptr(foot_a),
-        Bo, cap_o, ptr(rows_o), ptr(counts_o), int(counts_o.shape[1]), len(foot_o), _dptr(foot_o),
+        Ba, cap_a, ptr(rows_a), ptr(counts_a), int(counts_a.shape[1]), len(foot_a), dptr(foot_a),
+        Bo, cap_o, ptr(rows_o), ptr(counts_o), int(counts_o.shape[1]), len(foot_o), dptr(foot_o),
         pp("pair_clearance"), pp("pair_row"), pp("pair_first_row"), ptr(res["min_clearance"]), ptr(res["min_other"]),
         ptr(res["min_row"]), ptr(res["n_conflicts"]), ptr(res["first_row"])), "vap_footprint_conflicts")
     res["compatible"] = res["n_conflicts"] == 0

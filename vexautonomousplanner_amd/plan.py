@@ -23,13 +23,12 @@ two and gathers the legs in visiting order, ready for ``refine(seeds=...)``, wit
 
 Units: feet, in the scene's frame.  At most 16384 cells (the distance field of a problem lives in one workgroup's LDS).
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
-from .footprint import Scene, _ccw_polygon, _side, convex_polygon
+from ._call import buffers, context_for, device_array, dptr, ptr, time_rows
+from .footprint import Scene, _ccw_polygon, convex_polygon
 
 MAX_CELLS = 16384
 MAX_WAYPOINTS = 2048
@@ -64,10 +63,6 @@ def grid_shape(scene, cell):
     return ny, nx
 
 
-def _dptr(a):
-    return a.ctypes.data_as(_lib.dp) if a is not None and a.size else None
-
-
 def _check(scene, cell, radius, margin):
     """Validate what both calls share; returns (ny, nx, the scene arguments of the C-ABI)."""
     if not isinstance(scene, Scene):
@@ -85,29 +80,9 @@ def _check(scene, cell, radius, margin):
     nx, ny = int(np.ceil((f[2] - f[0]) / cell)), int(np.ceil((f[3] - f[1]) / cell))
     if nx * ny > MAX_CELLS:
         raise ValueError(f"a grid of {nx} x {ny} cells: at most {MAX_CELLS} cells (use a larger cell)")
-    args = (_dptr(f), scene.n_polygons, scene.poly_start.ctypes.data_as(_lib.ip), _dptr(scene.poly_xy), scene.n_circles,
-            _dptr(scene.circles), cell, radius, margin)
+    args = (dptr(f), scene.n_polygons, scene.poly_start.ctypes.data_as(_lib.ip), dptr(scene.poly_xy), scene.n_circles,
+            dptr(scene.circles), cell, radius, margin)
     return ny, nx, args
-
-
-def _context(dev, ctx):
-    if ctx is None:
-        ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    return ctx
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _buffers(out, shapes, dev):
-    res = {} if out is None else out
-    for k, (shp, dt) in shapes.items():
-        t = res.get(k)
-        if t is None or tuple(t.shape) != shp or t.dtype != dt or t.device != dev or not t.is_contiguous():
-            res[k] = torch.empty(shp, dtype=dt, device=dev)
-    return res
 
 
 def clearance_grid(scene, cell, radius, margin=0.0, out=None, device=0, ctx=None):
@@ -116,24 +91,30 @@ def clearance_grid(scene, cell, radius, margin=0.0, out=None, device=0, ctx=None
     ymin + (j + 0.5) cell).  Device tensors on torch's current stream, not synchronised; ``out`` keeps the buffers."""
     ny, nx, args = _check(scene, cell, radius, margin)
     dev = torch.device("cuda", device)
-    res = _buffers(out, {"clearance": ((ny, nx), torch.float64), "free_u8": ((ny, nx), torch.uint8)}, dev)
-    ctx = _context(dev, ctx)
-    _lib.check(ctx._L.vap_plan_grid(ctx.handle, *args, _ptr(res["clearance"]), _ptr(res["free_u8"]), None, None), "vap_plan_grid")
+    res = buffers(out, {"clearance": ((ny, nx), torch.float64), "free_u8": ((ny, nx), torch.uint8)}, dev)
+    ctx = context_for(dev, ctx)
+    _lib.check(ctx._L.vap_plan_grid(ctx.handle, *args, ptr(res["clearance"]), ptr(res["free_u8"]), None, None), "vap_plan_grid")
     res["free"] = res["free_u8"].view(torch.bool)
     return res
 
 
+def _waypoint_count(waypoints):
+    W = int(waypoints)
+    if W != waypoints or W < 2:
+        raise ValueError(f"waypoints must be an integer >= 2 (got {waypoints!r})")
+    if W > MAX_WAYPOINTS:
+        raise ValueError(f"waypoints = {W}: at most {MAX_WAYPOINTS}")
+    return W
+
+
 def _points(p, dev, what):
-    if isinstance(p, torch.Tensor):
-        t = p.to(device=dev, dtype=torch.float64)
-    else:
-        t = torch.as_tensor(np.ascontiguousarray(p, dtype=np.float64), device=dev)
+    t = device_array(p, dev, torch.float64)
     single = t.dim() == 1
     if single:
         t = t.unsqueeze(0)
     if t.dim() != 2 or t.shape[1] != 2:
         raise ValueError(f"{what} must be (R, 2) or (2,), got {tuple(p.shape) if hasattr(p, 'shape') else p!r}")
-    return t.contiguous(), single
+    return t, single
 
 
 INT_MIN, INT_MAX = -2 ** 31, 2 ** 31 - 1
@@ -164,18 +145,18 @@ def occupancy(rows, counts, footprint, scene, cell, radius, margin=0.0, shift_ro
         rows, counts = rows["rows"], rows["counts"]
     ny, nx, _ = _check(scene, cell, radius, margin)
     foot = _ccw_polygon(footprint, "footprint")
-    rows, counts, _, dev = _side(rows, counts, None, device, "occupancy")
+    rows, counts, _, dev = time_rows(rows, counts, None, device, "occupancy")
     shift_rows = int(shift_rows)
     shapes = {"first": ((ny, nx), torch.int32), "last": ((ny, nx), torch.int32), "count": ((ny, nx), torch.int32)}
     if min_clearance:
         shapes["min_clearance"] = ((ny, nx), torch.float64)
-    res = _buffers(out, shapes, dev)
-    ctx = _context(dev, ctx)
+    res = buffers(out, shapes, dev)
+    ctx = context_for(dev, ctx)
     ctx.set_option(_lib.OPT_FOOTPRINT_CULL, 1 if cull else 0)
     _lib.check(ctx._L.vap_plan_occupancy(
-        ctx.handle, int(rows.shape[0]), int(rows.shape[1]), _ptr(rows), _ptr(counts), int(counts.shape[1]), len(foot), _dptr(foot),
-        _dptr(scene.field), float(cell), float(radius), float(margin), shift_rows, int(bool(hold_first)), int(bool(hold_last)),
-        _ptr(res["first"]), _ptr(res["last"]), _ptr(res["count"]), _ptr(res["min_clearance"] if min_clearance else None), None,
+        ctx.handle, int(rows.shape[0]), int(rows.shape[1]), ptr(rows), ptr(counts), int(counts.shape[1]), len(foot), dptr(foot),
+        dptr(scene.field), float(cell), float(radius), float(margin), shift_rows, int(bool(hold_first)), int(bool(hold_last)),
+        ptr(res["first"]), ptr(res["last"]), ptr(res["count"]), ptr(res["min_clearance"] if min_clearance else None), None,
         None), "vap_plan_occupancy")
     res["blocked"] = res["first"] <= res["last"]
     return res
@@ -201,11 +182,7 @@ def seeds(starts, goals, scene, waypoints, radius, cell=0.25, margin=0.0, max_ve
     int32 (``plan.FLAGS``), n_vertices (R,) int32, feasible (R,) bool (a route was found), and the optional ones.  A failed
     problem (no free cell, unreachable goal, non-finite point) has NaN waypoints.  A single pair gives (W, 2) and 0-d
     tensors.  Work runs on torch's current stream and is not synchronised."""
-    W = int(waypoints)
-    if W != waypoints or W < 2:
-        raise ValueError(f"waypoints must be an integer >= 2 (got {waypoints!r})")
-    if W > MAX_WAYPOINTS:
-        raise ValueError(f"waypoints = {W}: at most {MAX_WAYPOINTS}")
+    W = _waypoint_count(waypoints)
     max_vertices = int(max_vertices)
     if vertices and max_vertices < 2:
         raise ValueError(f"max_vertices must be >= 2 (got {max_vertices})")
@@ -223,33 +200,16 @@ def seeds(starts, goals, scene, waypoints, radius, cell=0.25, margin=0.0, max_ve
         shapes["vertices"] = ((R, max_vertices, 2), torch.float64)
     if distance:
         shapes["distance"] = ((R, ny, nx), torch.float64)
-    res = _buffers(out, shapes, dev)
-    outs = (_ptr(res["waypoints"]), _ptr(res["length"]), _ptr(res["flags"]), _ptr(res["n_vertices"]),
-            _ptr(res["vertices"] if vertices else None), _ptr(res["distance"] if distance else None))
+    first, last, windows = _occupancy_args(occupancy, windows, R, ny, nx, dev)
+    res = buffers(out, shapes, dev)
+    outs = (ptr(res["waypoints"]), ptr(res["length"]), ptr(res["flags"]), ptr(res["n_vertices"]),
+            ptr(res["vertices"] if vertices else None), ptr(res["distance"] if distance else None))
+    ctx = context_for(dev, ctx)
     if occupancy is None:
-        if windows is not None:
-            raise ValueError("windows needs an occupancy")
-        ctx = _context(dev, ctx)
-        _lib.check(ctx._L.vap_plan_seeds(ctx.handle, R, W, _ptr(starts), _ptr(goals), *args, max_vertices, *outs), "vap_plan_seeds")
+        _lib.check(ctx._L.vap_plan_seeds(ctx.handle, R, W, ptr(starts), ptr(goals), *args, max_vertices, *outs), "vap_plan_seeds")
     else:
-        first, last = (occupancy["first"], occupancy["last"]) if isinstance(occupancy, dict) else occupancy
-        for t in (first, last):
-            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.int32 or tuple(t.shape) != (ny, nx):
-                raise ValueError(f"occupancy must be ({ny}, {nx}) int32 tensors on {dev} (plan.occupancy with the same scene and cell)")
-        first, last = first.contiguous(), last.contiguous()
-        if windows is not None:
-            if isinstance(windows, torch.Tensor):
-                windows = windows.to(device=dev, dtype=torch.int32)
-            else:
-                windows = torch.as_tensor(np.ascontiguousarray(windows, dtype=np.int32), device=dev)
-            if windows.dim() == 1:
-                windows = windows.unsqueeze(0).expand(R, 2)
-            if tuple(windows.shape) != (R, 2):
-                raise ValueError(f"windows must be ({R}, 2) or (2,), got {tuple(windows.shape)}")
-            windows = windows.contiguous()
-        ctx = _context(dev, ctx)
-        _lib.check(ctx._L.vap_plan_seeds_occupied(ctx.handle, R, W, _ptr(starts), _ptr(goals), *args, max_vertices, _ptr(first),
-                                                  _ptr(last), _ptr(windows), *outs), "vap_plan_seeds_occupied")
+        _lib.check(ctx._L.vap_plan_seeds_occupied(ctx.handle, R, W, ptr(starts), ptr(goals), *args, max_vertices, ptr(first),
+                                                  ptr(last), ptr(windows), *outs), "vap_plan_seeds_occupied")
     res["feasible"] = res["n_vertices"] > 0
     if single:
         res = {k: v[0] for k, v in res.items()}
@@ -267,10 +227,7 @@ def _occupancy_args(occupancy, windows, R, ny, nx, dev):
         if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.int32 or tuple(t.shape) != (ny, nx):
             raise ValueError(f"occupancy must be ({ny}, {nx}) int32 tensors on {dev} (plan.occupancy with the same scene and cell)")
     if windows is not None:
-        if isinstance(windows, torch.Tensor):
-            windows = windows.to(device=dev, dtype=torch.int32)
-        else:
-            windows = torch.as_tensor(np.ascontiguousarray(windows, dtype=np.int32), device=dev)
+        windows = device_array(windows, dev, torch.int32)
         if windows.dim() == 1:
             windows = windows.unsqueeze(0).expand(R, 2)
         if tuple(windows.shape) != (R, 2):
@@ -294,25 +251,15 @@ def travel(points, scene, radius, cell=0.25, margin=0.0, waypoints=None, occupan
     int32, feasible (R, P, P) bool (travel is finite), and waypoints (R, P, P, W, 2) if asked.  Off the diagonal every entry
     is what ``seeds(points[r, a], points[r, b], ...)`` gives, bit for bit; the matrix is not symmetric.  A single (P, 2) set
     gives results without the leading axis.  Work runs on torch's current stream and is not synchronised."""
-    W = 2
-    if waypoints is not None:
-        W = int(waypoints)
-        if W != waypoints or W < 2:
-            raise ValueError(f"waypoints must be an integer >= 2 (got {waypoints!r})")
-        if W > MAX_WAYPOINTS:
-            raise ValueError(f"waypoints = {W}: at most {MAX_WAYPOINTS}")
+    W = 2 if waypoints is None else _waypoint_count(waypoints)
     ny, nx, args = _check(scene, cell, radius, margin)
     dev = points.device if isinstance(points, torch.Tensor) and points.device.type == "cuda" else torch.device("cuda", device)
-    if isinstance(points, torch.Tensor):
-        pts = points.to(device=dev, dtype=torch.float64)
-    else:
-        pts = torch.as_tensor(np.ascontiguousarray(points, dtype=np.float64), device=dev)
+    pts = device_array(points, dev, torch.float64)
     single = pts.dim() == 2
     if single:
         pts = pts.unsqueeze(0)
     if pts.dim() != 3 or pts.shape[2] != 2:
         raise ValueError(f"points must be (R, P, 2) or (P, 2), got {tuple(points.shape)}")
-    pts = pts.contiguous()
     R, P = int(pts.shape[0]), int(pts.shape[1])
     if not 2 <= P <= MAX_POINTS:
         raise ValueError(f"P = {P} points: 2..{MAX_POINTS}")
@@ -320,11 +267,11 @@ def travel(points, scene, radius, cell=0.25, margin=0.0, waypoints=None, occupan
     if waypoints is not None:
         shapes["waypoints"] = ((R, P, P, W, 2), torch.float64)
     first, last, windows = _occupancy_args(occupancy, windows, R, ny, nx, dev)
-    res = _buffers(out, shapes, dev)
-    ctx = _context(dev, ctx)
-    _lib.check(ctx._L.vap_plan_travel(ctx.handle, R, P, W, _ptr(pts), *args, 0, _ptr(first), _ptr(last), _ptr(windows),
-                                      _ptr(res["travel"]), _ptr(res["flags"]), _ptr(res["n_vertices"]),
-                                      _ptr(res["waypoints"] if waypoints is not None else None)), "vap_plan_travel")
+    res = buffers(out, shapes, dev)
+    ctx = context_for(dev, ctx)
+    _lib.check(ctx._L.vap_plan_travel(ctx.handle, R, P, W, ptr(pts), *args, 0, ptr(first), ptr(last), ptr(windows),
+                                      ptr(res["travel"]), ptr(res["flags"]), ptr(res["n_vertices"]),
+                                      ptr(res["waypoints"] if waypoints is not None else None)), "vap_plan_travel")
     res["feasible"] = torch.isfinite(res["travel"])
     if single:
         res = {k: v[0] for k, v in res.items()}
@@ -380,19 +327,16 @@ def order(cost, end=None, before=None, out=None, ctx=None):
     if before is not None:
         if isinstance(before, (list, tuple)):                        # (earlier, later) pairs
             before = before_masks(before, R, P)
-        if isinstance(before, torch.Tensor):
-            b = before.to(device=dev, dtype=torch.int64)
-        else:
-            b = torch.as_tensor(np.ascontiguousarray(before, dtype=np.int64), device=dev)
+        b = device_array(before, dev, torch.int64)
         if b.dim() == 1:
             b = b.unsqueeze(0).expand(R, P)
         if tuple(b.shape) != (R, P):
             raise ValueError(f"before must be ({R}, {P}) or ({P},) masks or a list of (earlier, later) pairs, got {tuple(b.shape)}")
         b = (b & (2 ** MAX_SITES - 1)).to(torch.int32).contiguous()  # bits >= M are ignored anyway
-    res = _buffers(out, {"order": ((R, M), torch.int32), "total": ((R,), torch.float64), "flags": ((R,), torch.int32)}, dev)
-    ctx = _context(dev, ctx)
-    _lib.check(ctx._L.vap_plan_order(ctx.handle, R, P, _ptr(c), e, _ptr(b), _ptr(res["order"]), _ptr(res["total"]),
-                                     _ptr(res["flags"])), "vap_plan_order")
+    res = buffers(out, {"order": ((R, M), torch.int32), "total": ((R,), torch.float64), "flags": ((R,), torch.int32)}, dev)
+    ctx = context_for(dev, ctx)
+    _lib.check(ctx._L.vap_plan_order(ctx.handle, R, P, ptr(c), e, ptr(b), ptr(res["order"]), ptr(res["total"]),
+                                     ptr(res["flags"])), "vap_plan_order")
     res["feasible"] = res["flags"] == 0
     if single:
         res = {k: v[0] for k, v in res.items()}

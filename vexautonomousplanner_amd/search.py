@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._call import buffers, context_for, device_array, ptr
 from .synth import DEFAULT_CONSTRAINTS
 
 MAX_CANDIDATES = 4096
@@ -89,10 +90,6 @@ class SearchConfig:
         return self
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _vdtype(t):
     if t.dtype == torch.float32:
         return _lib.VAP_F32
@@ -101,24 +98,12 @@ def _vdtype(t):
     raise ValueError(f"waypoints must be float32 or float64 (got {t.dtype})")
 
 
-def _context(dev, ctx):
-    if ctx is None:
-        ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    return ctx
-
-
 def _dev64(t, dev, what, shape=None):
     """``t`` as a contiguous fp64 tensor on ``dev`` (None stays None)."""
-    if t is None:
-        return None
-    if isinstance(t, torch.Tensor):
-        t = t.to(device=dev, dtype=torch.float64)
-    else:
-        t = torch.as_tensor(np.ascontiguousarray(t, dtype=np.float64), device=dev)
-    if shape is not None and tuple(t.shape) != tuple(shape):
+    t = device_array(t, dev, torch.float64)
+    if t is not None and shape is not None and tuple(t.shape) != tuple(shape):
         raise ValueError(f"{what} must be {tuple(shape)}, got {tuple(t.shape)}")
-    return t.contiguous()
+    return t
 
 
 def sample(mean, sigma, candidates, dtype=torch.float32, seed=0, iteration=0, first_problem=0, best_waypoints=None,
@@ -144,9 +129,9 @@ def sample(mean, sigma, candidates, dtype=torch.float32, seed=0, iteration=0, fi
         raise ValueError(f"best_waypoints must be a contiguous ({R}, {W}, 2) {out.dtype} tensor")
     if best_cost is not None and (tuple(best_cost.shape) != (R,) or best_cost.dtype != torch.float64):
         raise ValueError(f"best_cost must be an ({R},) fp64 tensor")
-    ctx = _context(dev, ctx)
-    _lib.check(ctx._L.vap_search_sample(ctx.handle, vd, R, N, W, _ptr(mean), _ptr(sigma), _ptr(best_waypoints), _ptr(best_cost),
-                                        int(seed), int(iteration) & 0xFFFFFFFF, int(first_problem) & 0xFFFFFFFF, _ptr(out)),
+    ctx = context_for(dev, ctx)
+    _lib.check(ctx._L.vap_search_sample(ctx.handle, vd, R, N, W, ptr(mean), ptr(sigma), ptr(best_waypoints), ptr(best_cost),
+                                        int(seed), int(iteration) & 0xFFFFFFFF, int(first_problem) & 0xFFFFFFFF, ptr(out)),
                "vap_search_sample")
     return out
 
@@ -198,24 +183,20 @@ def update(waypoints, problems, weights=None, counts=None, time_step=0.01, meta=
         if history.dtype != torch.float64 or history.dim() != 2 or history.shape[0] != R or not history.is_contiguous():
             raise ValueError(f"history must be a contiguous ({R}, k) fp64 tensor")
         hist_stride = int(history.shape[1])
-    bufs = {} if out is None else out
     shapes = {"cost": ((B,), torch.float64), "violation": ((B,), torch.float64), "order": ((R, N), torch.int32)}
     if n_feasible is None:
         shapes["n_feasible"] = ((R,), torch.int32)
-    for k, (shp, dt) in shapes.items():
-        t = bufs.get(k)
-        if t is None or tuple(t.shape) != shp or t.dtype != dt or t.device != dev or not t.is_contiguous():
-            bufs[k] = torch.empty(shp, dtype=dt, device=dev)
+    bufs = buffers(out, shapes, dev)
     res = {k: bufs[k] for k in shapes}
     if n_feasible is not None:
         res["n_feasible"] = n_feasible
     ws = weights.as_struct()
-    ctx = _context(dev, ctx)
+    ctx = context_for(dev, ctx)
     _lib.check(ctx._L.vap_search_update(
-        ctx.handle, vd, R, N, W, _ptr(wp), _ptr(counts), stride, float(time_step), _ptr(meta), _ptr(flags), _ptr(clearance),
-        _ptr(conflict_clearance), _ptr(tracking_worst), C.byref(ws), int(elites), float(alpha), float(sigma_min),
-        float(sigma_max), _ptr(mean), _ptr(sigma), _ptr(res["cost"]), _ptr(res["violation"]), _ptr(res["order"]),
-        _ptr(res["n_feasible"]), _ptr(best_cost), _ptr(best_waypoints), _ptr(best_terms), _ptr(history), hist_stride,
+        ctx.handle, vd, R, N, W, ptr(wp), ptr(counts), stride, float(time_step), ptr(meta), ptr(flags), ptr(clearance),
+        ptr(conflict_clearance), ptr(tracking_worst), C.byref(ws), int(elites), float(alpha), float(sigma_min),
+        float(sigma_max), ptr(mean), ptr(sigma), ptr(res["cost"]), ptr(res["violation"]), ptr(res["order"]),
+        ptr(res["n_feasible"]), ptr(best_cost), ptr(best_waypoints), ptr(best_terms), ptr(history), hist_stride,
         int(iteration) & 0xFFFFFFFF), "vap_search_update")
     return res
 

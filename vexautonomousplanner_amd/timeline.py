@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .footprint import _side
+from ._call import buffers, context_for, device_array, ptr, time_rows
 from .synth import DEFAULT_CONSTRAINTS
 
 MAX_LEGS = _lib.TIMELINE_MAX_LEGS
@@ -36,20 +36,6 @@ def turn_rows(angle, constraints=DEFAULT_CONSTRAINTS, dt=0.01):
     else:
         total = 2 * t_acc + (arc - 2 * d_acc) / c.max_vel
     return int(math.ceil((total + dt) / dt))
-
-
-def _device_array(a, dev, dtype, shape, what):
-    """``a`` as a contiguous device tensor of ``dtype`` and ``shape``: a device tensor is used as it is (converted on the
-    device if it must be), host data is uploaded.  Returns (tensor, whether it came from the host)."""
-    host = not isinstance(a, torch.Tensor)
-    if host:
-        np_dt = np.int32 if dtype == torch.int32 else np.float64
-        a = torch.as_tensor(np.ascontiguousarray(a, dtype=np_dt), device=dev)
-    elif a.device != dev:
-        raise ValueError(f"{what} is on {a.device}, the rows on {dev}")
-    if tuple(a.shape) != shape:
-        raise ValueError(f"{what} must be {shape}, got {tuple(a.shape)}")
-    return a.to(dtype).contiguous(), host
 
 
 def chain(rows, counts, legs, dwell=None, start_heading=None, n_legs=None, constraints=DEFAULT_CONSTRAINTS, dt=0.01,
@@ -82,7 +68,7 @@ def chain(rows, counts, legs, dwell=None, start_heading=None, n_legs=None, const
     if not (turn_min >= 0 and math.isfinite(turn_min)):
         raise ValueError(f"turn_min must be >= 0 and finite (got {turn_min!r})")
     c = _lib.make_constraints(constraints)
-    rows, counts, single, dev = _side(rows, counts, None, device, "legs")
+    rows, counts, single, dev = time_rows(rows, counts, None, device, "legs")
     if single:
         raise ValueError("rows must be (L, capacity_in, 8): a batch of legs")
     L, cap_in = int(rows.shape[0]), int(rows.shape[1])
@@ -90,16 +76,22 @@ def chain(rows, counts, legs, dwell=None, start_heading=None, n_legs=None, const
     if len(shape) != 2 or not 1 <= shape[1] <= MAX_LEGS:
         raise ValueError(f"legs must be (R, M) with 1 <= M <= {MAX_LEGS}, got {tuple(shape)}")
     R, M = int(shape[0]), int(shape[1])
-    legs, _ = _device_array(legs, dev, torch.int32, (R, M), "legs")
+
+    def arg(a, dtype, shape, what):
+        if isinstance(a, torch.Tensor) and a.device != dev:
+            raise ValueError(f"{what} is on {a.device}, the rows on {dev}")
+        t = device_array(a, dev, dtype)
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{what} must be {shape}, got {tuple(t.shape)}")
+        return t
+
+    legs = arg(legs, torch.int32, (R, M), "legs")
     dwell_host = None
-    if dwell is not None:
-        if not isinstance(dwell, torch.Tensor):
-            dwell_host = np.ascontiguousarray(dwell, dtype=np.float64)
-        dwell, _ = _device_array(dwell, dev, torch.float64, (R, M), "dwell")
-    if start_heading is not None:
-        start_heading, _ = _device_array(start_heading, dev, torch.float64, (R,), "start_heading")
-    if n_legs is not None:
-        n_legs, _ = _device_array(n_legs, dev, torch.int32, (R,), "n_legs")
+    if dwell is not None and not isinstance(dwell, torch.Tensor):
+        dwell_host = np.ascontiguousarray(dwell, dtype=np.float64)
+    dwell = arg(dwell, torch.float64, (R, M), "dwell")
+    start_heading = arg(start_heading, torch.float64, (R,), "start_heading")
+    n_legs = arg(n_legs, torch.int32, (R,), "n_legs")
     if capacity_rows is None:
         if dwell is not None and dwell_host is None:
             raise ValueError("capacity_rows is required when dwell is a device tensor: its rows cannot be counted "
@@ -112,18 +104,11 @@ def chain(rows, counts, legs, dwell=None, start_heading=None, n_legs=None, const
     capacity_rows = int(capacity_rows)
     if capacity_rows < 0:
         raise ValueError(f"capacity_rows must be >= 0 (got {capacity_rows})")
-    res = {} if out is None else out
     shapes = {"rows": ((R, capacity_rows, 8), torch.float64), "counts": ((R, 2), torch.int32), "map": ((R, M, 3), torch.int32),
               "seam": ((R, M, 3), torch.float64), "flags": ((R,), torch.int32)}
-    for k, (shp, dty) in shapes.items():
-        t = res.get(k)
-        if t is None or tuple(t.shape) != shp or t.dtype != dty or t.device != dev or not t.is_contiguous():
-            res[k] = torch.empty(shp, dtype=dty, device=dev)
+    res = buffers(out, shapes, dev)
     res["flags"].zero_()                          # the call ORs its bits in
-    if ctx is None:
-        ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    ctx = context_for(dev, ctx)
     _lib.check(ctx._L.vap_routine_timeline(
         ctx.handle, R, M, L, cap_in, capacity_rows, dt, C.byref(c), turn_min, ptr(rows), ptr(counts), int(counts.shape[1]),
         ptr(legs), ptr(n_legs), ptr(dwell), ptr(start_heading), ptr(res["rows"]), ptr(res["counts"]), ptr(res["map"]),

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._call import buffers, context_for, device_array, ptr, time_rows
 
 MAX_ROLLOUTS = 4096
 NOMINAL = (0.0, 0.0, 0.0, 1.0, 1.0, 1.0, 0.0, 0.0)      # dx, dy, dphi, gain_left, gain_right, track_scale, tau, reserved
@@ -111,61 +112,25 @@ def rollouts(rows, counts, follower, perturbations, time_step=0.01, executed=Fal
     time_step = float(time_step)
     if not (time_step > 0 and np.isfinite(time_step)):
         raise ValueError(f"time_step must be positive and finite (got {time_step!r})")
-    if isinstance(rows, torch.Tensor):
-        dev = rows.device
-        if dev.type != "cuda" or rows.dtype != torch.float64:
-            raise ValueError("rows must be an fp64 tensor on a HIP device (or a host array)")
-    else:
-        dev = torch.device("cuda", device)
-        rows = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.float64), device=dev)
-    single = rows.dim() == 2
-    if single:
-        rows = rows.unsqueeze(0)
-    if rows.dim() != 3 or rows.shape[2] != 8:
-        raise ValueError(f"rows must be (B, capacity, 8) or (n, 8), got {tuple(rows.shape)}")
-    rows = rows.contiguous()
+    rows, counts, single, dev = time_rows(rows, counts, None, device)
     B, cap = int(rows.shape[0]), int(rows.shape[1])
-    if counts is None:
-        if not single:
-            raise ValueError("counts is needed for a batch of rows")
-        counts = torch.full((1, 1), cap, dtype=torch.int32, device=dev)
-    elif isinstance(counts, torch.Tensor):
-        counts = counts.to(device=dev, dtype=torch.int32)
-    else:
-        counts = torch.as_tensor(np.asarray(counts, dtype=np.int32), device=dev)
-    if counts.dim() < 2:
-        counts = counts.reshape(B, 1)
-    if counts.dim() != 2 or counts.shape[0] != B:
-        raise ValueError(f"counts must be ({B}, k) or ({B},), got {tuple(counts.shape)}")
-    counts = counts.contiguous()
-    if isinstance(perturbations, torch.Tensor):
-        pert = perturbations.to(device=dev, dtype=torch.float64)
-    else:
-        pert = torch.as_tensor(np.ascontiguousarray(perturbations, dtype=np.float64), device=dev)
+    pert = device_array(perturbations, dev, torch.float64)
     shared = pert.dim() == 2
     if pert.dim() not in (2, 3) or pert.shape[-1] != 8 or (not shared and pert.shape[0] != B):
         raise ValueError(f"perturbations must be ({B}, K, 8) or (K, 8), got {tuple(pert.shape)}")
-    pert = pert.contiguous()
     K = int(pert.shape[-2])
     if not 1 <= K <= MAX_ROLLOUTS:
         raise ValueError(f"K = {K} rollouts per route (1..{MAX_ROLLOUTS})")
     cap_exec = cap + int(follower.settle_rows)
-    bufs = {} if out is None else out      # the call's buffers; the returned dict is built apart from it
     shapes = {"stats": ((B, K, 6), torch.float64), "stat_rows": ((B, K, 2), torch.int32), "worst": ((B,), torch.float64),
               "mean": ((B,), torch.float64), "worst_rollout": ((B,), torch.int32), "worst_row": ((B,), torch.int32),
               "n_exceeding": ((B,), torch.int32)}
     if executed:
         shapes["rows"] = ((B * K, cap_exec, 8), torch.float64)
         shapes["counts"] = ((B * K, 2), torch.int32)
-    for k, (shp, dt) in shapes.items():
-        t = bufs.get(k)
-        if t is None or tuple(t.shape) != shp or t.dtype != dt or t.device != dev or not t.is_contiguous():
-            bufs[k] = torch.empty(shp, dtype=dt, device=dev)
+    bufs = buffers(out, shapes, dev)       # the call's buffers; the returned dict is built apart from it
     res = {k: bufs[k] for k in shapes}
-    if ctx is None:
-        ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    ctx = context_for(dev, ctx)
     fs = follower.as_struct()
     _lib.check(ctx._L.vap_tracking_rollouts(
         ctx.handle, B, cap, ptr(rows), ptr(counts), int(counts.shape[1]), time_step, C.byref(fs), K, int(shared), ptr(pert),
