@@ -205,7 +205,8 @@ int vap_sample(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, double dd, const
  * plain-node default max_vel with start/end velocities at the ends.  Entry 0 and the end sample are
  * taken from start_vel / end_vel.  Rows that fit the register-resident relaxation kernel (20 480
  * samples fp32, 10 240 fp64) run there, longer ones in the one-lane sequential sweep.
- * d_dtheta NULL = the rows the last sampling call (vap_sample / vap_profile_batch) of this shape and dtype
+ * d_dtheta NULL = the rows the last sampling call (vap_profile_batch / vap_profile_routes; vap_sample for VAP_F32
+ * with VAP_RECURRENCE_F64 only — in the other modes its rows are the caller's) of this shape and dtype
  * left on the context; for VAP_F32 with VAP_RECURRENCE_F64 these are fp64 curvature AND |dtheta| rows
  * (d_curvature is then not read and may be NULL) and the recurrence runs in fp64.  With an explicit d_dtheta
  * the recurrence runs in `dt` on the caller's rows. */
@@ -235,7 +236,8 @@ int vap_velocity_pass(vap_ctx *ctx, vap_dtype dt, int B, int S, const vap_constr
  *                                    change max_acceleration need only d_vcap)
  *   d_node_sample [B][W], d_action_sample [B][M]  int32 out, optional: the sample at which each takes
  *                                    effect (node 0: 0; INT_MAX: never)
- * d_lut NULL = the table of the last vap_profile_batch.  Reverse / turn nodes are not covered here
+ * d_lut NULL = the table of the last vap_profile_batch / vap_profile_routes (same B, W; after vap_profile_routes
+ * d_lut must be NULL).  Reverse / turn nodes are not covered here
  * (vap_route_* is the general single-route path); waits act in the time domain (vap_time_insert_waits). */
 /* Type of the limit rows (d_vcap, d_acc_forward, d_acc_backward, d_dec_backward) for rows of type dt in this context:
  * the type of the recurrence they enter — VAP_F64 for fp64 rows and for fp32 rows in the default mode
@@ -271,8 +273,9 @@ int vap_velocity_pass_limits(vap_ctx *ctx, vap_dtype dt, int B, int S, const vap
  *                                          quirk Q5: the last node is never recorded)
  * d_velocity is the [B][S] result of vap_velocity_pass / vap_profile_batch in `dt`; d_meta as above.
  * d_segments / d_lut may both be NULL: the tables this context built in its last vap_profile_batch
- * call (same B and W) are used.  A path needing more than capacity_rows rows is cut there and flagged
- * VAP_FLAG_TRUNCATED. */
+ * call (same B and W) are used; those of a vap_profile_routes call, max_splines = 1 included, are refused
+ * (VAP_ERR_UNSUPPORTED: vap_time_profile_routes).  A path needing more than capacity_rows rows is cut there and
+ * flagged VAP_FLAG_TRUNCATED. */
 int vap_time_profile(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, const double *d_segments,
                      const double *d_lut, const double *d_meta, const void *d_velocity,
                      const vap_constraints *c, double time_step, int capacity_rows, double *d_rows,

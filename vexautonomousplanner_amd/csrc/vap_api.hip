@@ -8,7 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "vap_internal.h"
+#include "vap_ctx_state.h"
 #include "vap_kernels.h"
 
 namespace {
@@ -68,7 +68,7 @@ int run_velocity(vap_ctx *ctx, bool f64, bool io64, int B, int S, const double c
                  const void *curv, const void *dth, const void *vcap, const vap::AccRowsV &acc, void *vel, uint32_t *flags)
 {
     int mode = ctx->velocity_kernel;
-    ctx->vres_for = nullptr;
+    ctx->left.vres_for = nullptr;
     // fp32 rows behind the fp64 recurrence: what the fp32 row lost of the fp64 velocities stays on the context as an fp32
     // residual row (VAP_OPT_TIME_DOMAIN_RESIDUAL, on by default) — the lane-per-path kernel writes it itself, the others
     // leave an fp64 row in scratch, converted here.  Always the residual form: the time domain then integrates the caller's
@@ -76,9 +76,9 @@ int run_velocity(vap_ctx *ctx, bool f64, bool io64, int B, int S, const double c
     // address costs at most that rounding.
     const bool want_hi = f64 && !io64 && ctx->keep_residual;
     auto keep_res = [&]() {
-        ctx->vres_for = vel;
-        ctx->vres_B = B;
-        ctx->vres_S = S;
+        ctx->left.vres_for = vel;
+        ctx->left.vres_B = B;
+        ctx->left.vres_S = S;
     };
     auto keep_hi = [&](const void *rows64) -> int {
         VAP_TRY(ctx->ensure(ctx->vres, (size_t)B * S * sizeof(float)));
@@ -180,18 +180,130 @@ int run_velocity(vap_ctx *ctx, bool f64, bool io64, int B, int S, const double c
     return VAP_OK;
 }
 
-// The velocity row a time-domain entry point integrates: always the caller's, as it is now — plus, for an fp32 row whose
-// velocity pass ran the fp64 recurrence in this context, the fp32 residual that pass left behind (row + residual = the
-// fp64 velocity to 2^-48; MPG:566-584 integrates positions from the row, and an fp32 row alone moves a position by ~1e-7
-// relative, now and then across a boundary of the reference's step lookup, SM:550-580).  The residual is below the
-// row's own rounding, so a row the caller has edited since is integrated as edited.
-const void *time_domain_velocity(vap_ctx *ctx, vap_dtype dt, int B, int S, const void *d_velocity, bool &is64, const float *&vres)
+// Quirk Q9: boundary_map always holds sample 0 (MPG:110), so the reference overwrites max_dec with
+// max_accels[0] — max_acc for a plain node — before the first forward step (MPG:194-196) and never
+// restores it until the pass returns: the backward sweep decelerates with max_acc.  (The time loop
+// does see the caller's max_dec, MPG:572-573 — vap_time_profile.)
+void velocity_consts(const vap_constraints *c, double cc[6])
 {
-    is64 = dt == VAP_F64;
-    vres = nullptr;
-    if (dt == VAP_F32 && ctx->vres_for == d_velocity && ctx->vres.ptr && ctx->vres_B == B && ctx->vres_S == S)
-        vres = (const float *)ctx->vres.ptr;
-    return d_velocity;
+    cc[0] = c->max_vel, cc[1] = cc[2] = c->max_acc, cc[3] = c->friction_coef, cc[4] = c->max_jerk, cc[5] = c->track_width;
+}
+
+// What the sampling kernel and the velocity pass of one call work on, resolved once: the caller's buffers or the context's
+// scratch.  hi — VAP_F32 with the fp64 recurrence (the default): the velocity pass reads fp64 curvature / |dtheta| rows,
+// which the sampling kernel leaves in k64 / dth64 next to the caller's fp32 rows.
+struct Stage {
+    bool hi = false;
+    const double *seg = nullptr, *lut = nullptr;
+    double *meta = nullptr;
+    uint32_t *flags = nullptr;
+    void *curv = nullptr, *dth = nullptr;           // rows in the call's dtype (null: not written)
+    double *k64 = nullptr, *dth64 = nullptr;        // hi only
+};
+
+// VAP_F32 with the fp64 recurrence: the fp64 rows of n_pts sample-points; any other mode: nothing
+int hi_rows(vap_ctx *ctx, vap_dtype dt, size_t n_pts, Stage &s)
+{
+    s.hi = dt == VAP_F32 && ctx->f32_recurrence == VAP_RECURRENCE_F64;
+    if (!s.hi) return VAP_OK;
+    VAP_TRY(ctx->ensure(ctx->k64, n_pts * sizeof(double)));
+    VAP_TRY(ctx->ensure(ctx->dth64, n_pts * sizeof(double)));
+    s.k64 = (double *)ctx->k64.ptr;
+    s.dth64 = (double *)ctx->dth64.ptr;
+    return VAP_OK;
+}
+
+// Scratch of a fused call of B x W x S (NS > 0: routes of up to NS splines each), in the order the calls always asked for
+// it — ensure() may synchronise and free — and the call's meta / flags / curvature: the caller's, or scratch where the
+// caller passed NULL and the call itself needs the row.
+int fused_stage(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, int NS, double *d_meta, uint32_t *d_flags, void *d_curvature, Stage &s)
+{
+    const size_t n_seg = (size_t)B * (W - 1), n_pts = (size_t)B * S;
+    VAP_TRY(ctx->ensure(ctx->seg, n_seg * 12 * sizeof(double)));
+    VAP_TRY(ctx->ensure(ctx->power, n_seg * vap::kCoefBlockDoubles * sizeof(double)));
+    VAP_TRY(ctx->ensure(ctx->lut, (size_t)B * (NS > 0 ? NS : 1) * VAP_LUT_SAMPLES * sizeof(double)));
+    if (NS > 0) {
+        VAP_TRY(ctx->ensure(ctx->sptab, (size_t)B * NS * 4 * sizeof(double)));
+        VAP_TRY(ctx->ensure(ctx->nspl, (size_t)B * sizeof(int)));
+    }
+    VAP_TRY(ctx->ensure(ctx->aux, (size_t)B * 4 * sizeof(double)));
+    VAP_TRY(ctx->ensure(ctx->runs, (size_t)B * vap::kGridRunBlockDoubles * sizeof(double)));
+    VAP_TRY(hi_rows(ctx, dt, n_pts, s));
+    if (!s.hi) {
+        VAP_TRY(ctx->ensure(ctx->dth, n_pts * esz(dt)));
+        s.dth = ctx->dth.ptr;
+    }
+    s.meta = d_meta;
+    if (!s.meta) {
+        VAP_TRY(ctx->ensure(ctx->meta, (size_t)B * 4 * sizeof(double)));
+        s.meta = (double *)ctx->meta.ptr;
+    }
+    s.flags = d_flags;
+    if (!s.flags) {
+        VAP_TRY(ctx->ensure(ctx->flags, (size_t)B * sizeof(uint32_t)));
+        s.flags = (uint32_t *)ctx->flags.ptr;
+    }
+    s.curv = d_curvature;
+    if (!s.curv && !s.hi) {
+        VAP_TRY(ctx->ensure(ctx->io[7], n_pts * esz(dt)));
+        s.curv = ctx->io[7].ptr;
+    }
+    s.seg = (const double *)ctx->seg.ptr;
+    s.lut = (const double *)ctx->lut.ptr;
+    return VAP_OK;
+}
+
+// The sampling kernel on the context's power blocks and distance grid: of plain paths, or (routes) of routes cut into splines
+hipError_t launch_stage_sample(vap_ctx *ctx, bool f64, int B, int W, int S, const Stage &s, const vap::RouteTables *routes, void *d_x,
+                               void *d_y, void *d_heading)
+{
+    const double *power = (const double *)ctx->power.ptr, *aux = (const double *)ctx->aux.ptr, *runs = (const double *)ctx->runs.ptr;
+    if (!routes)
+        return vap::launch_sample(ctx->stream, f64, B, W, S, power, s.lut, nullptr, s.meta, aux, runs, d_x, d_y, d_heading, s.curv, s.dth,
+                                  s.k64, s.dth64, s.seg);
+    return vap::launch_sample_routes(ctx->stream, f64, B, W, routes->NS, S, power, s.lut, routes->sptab, routes->nspl, s.meta, aux, runs,
+                                     d_x, d_y, d_heading, s.curv, s.dth, s.k64, s.dth64, s.seg);
+}
+
+// The tail of a fused call: the sampling kernel, then the plain velocity pass on the rows it left
+int sample_and_velocity(vap_ctx *ctx, StageTimer &tm, vap_dtype dt, int B, int W, int S, const Stage &s, const vap::RouteTables *routes,
+                        const vap_constraints *c, double start_vel, double end_vel, void *d_x, void *d_y, void *d_heading, void *d_velocity)
+{
+    const bool f64 = dt == VAP_F64;
+    HIP_TRY(launch_stage_sample(ctx, f64, B, W, S, s, routes, d_x, d_y, d_heading));
+    tm.mark(VAP_T_SAMPLE);
+    double cc[6];
+    velocity_consts(c, cc);
+    VAP_TRY(run_velocity(ctx, f64 || s.hi, f64, B, S, cc, start_vel, end_vel, s.meta, s.hi ? s.k64 : s.curv, s.hi ? s.dth64 : s.dth, nullptr,
+                         vap::AccRowsV(), d_velocity, s.flags));
+    tm.mark(VAP_T_VELOCITY);
+    return VAP_OK;
+}
+
+// d_segments / d_lut of a plain-path time-domain call: both the caller's, or both NULL = the context's tables of B x W
+int plain_tables(const vap_ctx *ctx, int B, int W, const double *&d_segments, const double *&d_lut)
+{
+    if ((d_segments == nullptr) != (d_lut == nullptr)) return vap_fail(VAP_ERR_INVALID, "pass both d_segments and d_lut, or neither");
+    if (d_segments) return VAP_OK;
+    VapTables t;
+    VAP_TRY(vap_ctx_tables(ctx, B, W, true, t));
+    d_segments = t.seg;
+    d_lut = t.lut;
+    return VAP_OK;
+}
+
+// What vap_time_insert_waits and vap_time_insert_events ask of their common arguments (have_c: the latter's constraints)
+int check_insert_args(int B, int W, int M, int capacity_in, int capacity_out, double time_step, bool have_c, const double *d_meta,
+                      const double *d_rows_in, const int *d_counts_in, const int *d_nodes_map_in, const double *d_action_t,
+                      const double *d_rows_out, const int *d_counts_out, const int *d_nodes_map_out, const int *d_actions_map_out)
+{
+    VAP_TRY(check_shape(B, W, 2));
+    if (M < 0 || capacity_in < 1 || capacity_out < 1 || !(time_step > 0) || !have_c) return vap_fail(VAP_ERR_INVALID, "bad argument");
+    if (!d_meta || !d_rows_in || !d_counts_in || !d_nodes_map_in || !d_rows_out || !d_counts_out || !d_nodes_map_out)
+        return vap_fail(VAP_ERR_INVALID, "null buffer");
+    if (M > 0 && (!d_action_t || !d_actions_map_out)) return vap_fail(VAP_ERR_INVALID, "null action-point array");
+    if (d_rows_out == d_rows_in) return vap_fail(VAP_ERR_INVALID, "the rows move: d_rows_out must not be d_rows_in");
+    return VAP_OK;
 }
 
 }  // namespace
@@ -254,13 +366,10 @@ int vap_ctx_destroy(vap_ctx *ctx)
     if (!ctx) return VAP_OK;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    VapBuffer *bufs[] = {&ctx->sptab, &ctx->nspl, &ctx->k64, &ctx->dth64, &ctx->ufwd, &ctx->vhi, &ctx->vres, &ctx->lstate, &ctx->lcount, &ctx->seg, &ctx->power, &ctx->lut, &ctx->slopes, &ctx->aux, &ctx->runs, &ctx->meta, &ctx->dth, &ctx->flags, &ctx->small_in,
-                      &ctx->small_out, &ctx->small_seg, &ctx->small_lut, &ctx->scene, &ctx->conf_pack_a, &ctx->conf_pack_o,
-                      &ctx->conf_blk_a, &ctx->conf_blk_o, &ctx->conf_part, &ctx->track_part, &ctx->plan_free, &ctx->plan_path};
-    for (VapBuffer *b : bufs)
+    for (VapBuffer *b : ctx->owned) {   // (a buffer whose allocation once failed is listed twice)
         if (b->ptr) (void)hipFree(b->ptr);
-    for (VapBuffer &b : ctx->io)
-        if (b.ptr) (void)hipFree(b.ptr);
+        b->ptr = nullptr;
+    }
     for (auto &e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
     if (ctx->scene_ev) (void)hipEventDestroy(ctx->scene_ev);
@@ -293,7 +402,7 @@ int vap_ctx_set_option(vap_ctx *ctx, int option, int value)
     }
     if (option == VAP_OPT_TIME_DOMAIN_RESIDUAL && (value == 0 || value == 1)) {
         ctx->keep_residual = value;
-        ctx->vres_for = nullptr;
+        ctx->left.vres_for = nullptr;
         return VAP_OK;
     }
     if (option == VAP_OPT_TIME_KERNEL && value >= VAP_TIME_KERNEL_AUTO && value <= VAP_TIME_KERNEL_FUSED) {
@@ -306,7 +415,7 @@ int vap_ctx_set_option(vap_ctx *ctx, int option, int value)
     }
     if (option == VAP_OPT_F32_RECURRENCE && (value == VAP_RECURRENCE_F64 || value == VAP_RECURRENCE_F32)) {
         ctx->f32_recurrence = value;
-        ctx->rows_valid = false;   // rows left by an earlier call belong to the other mode
+        ctx->left.rows = VAP_ROWS_NONE;   // rows left by an earlier call belong to the other mode
         return VAP_OK;
     }
     return vap_fail(VAP_ERR_INVALID, "unknown option %d / value %d", option, value);
@@ -341,12 +450,8 @@ int vap_fit(vap_ctx *ctx, vap_dtype dt, int B, int W, const void *d_waypoints, c
             const double *d_tangent_out, double *d_segments, double *d_segment_lengths, double *d_meta,
             uint32_t *d_flags)
 {
-    VAP_TRY(vap_set_device(ctx));
-    VAP_TRY(check_shape(B, W, 2));
-    if (!d_waypoints || !d_segments || !d_meta) return vap_fail(VAP_ERR_INVALID, "null buffer");
-    HIP_TRY(vap::launch_fit(ctx->stream, dt == VAP_F64, B, W, d_waypoints, d_tangent_in, d_tangent_out,
-                            d_segments, nullptr, d_segment_lengths, d_meta, d_flags));
-    return VAP_OK;
+    return vap_fit_ex(ctx, dt, B, W, d_waypoints, d_tangent_in, d_tangent_out, nullptr, nullptr, nullptr, nullptr, d_segments,
+                      d_segment_lengths, nullptr, nullptr, d_meta, d_flags);
 }
 
 int vap_fit_ex(vap_ctx *ctx, vap_dtype dt, int B, int W, const void *d_waypoints, const double *d_tangent_in,
@@ -386,22 +491,16 @@ int vap_sample(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, double dd, const
     VAP_TRY(ctx->ensure(ctx->runs, (size_t)B * vap::kGridRunBlockDoubles * sizeof(double)));
     HIP_TRY(vap::launch_power(ctx->stream, (int)n_seg, d_segments, (double *)ctx->power.ptr));
     HIP_TRY(vap::launch_grid(ctx->stream, B, W, S, dd, d_meta, (double *)ctx->aux.ptr, (double *)ctx->runs.ptr, d_flags));
-    const bool hi = dt == VAP_F32 && ctx->f32_recurrence == VAP_RECURRENCE_F64;
-    if (hi) {
-        VAP_TRY(ctx->ensure(ctx->k64, (size_t)B * S * sizeof(double)));
-        VAP_TRY(ctx->ensure(ctx->dth64, (size_t)B * S * sizeof(double)));
-    }
-    HIP_TRY(vap::launch_sample(ctx->stream, dt == VAP_F64, B, W, S, (const double *)ctx->power.ptr, d_lut,
-                               nullptr, d_meta, (const double *)ctx->aux.ptr,
-                               (const double *)ctx->runs.ptr, d_x, d_y, d_heading, d_curvature, d_dtheta,
-                               hi ? (double *)ctx->k64.ptr : nullptr, hi ? (double *)ctx->dth64.ptr : nullptr, d_segments));
-    ctx->grid_B = B;
-    ctx->grid_W = W;
-    ctx->grid_S = S;
-    ctx->rows_valid = hi;
-    ctx->rows_hi = hi;
-    ctx->rows_dt = dt;
-    ctx->route_NS = 0;
+    Stage s;
+    VAP_TRY(hi_rows(ctx, dt, (size_t)B * S, s));
+    s.seg = d_segments;
+    s.lut = d_lut;
+    s.meta = d_meta;
+    s.curv = d_curvature;
+    s.dth = d_dtheta;
+    HIP_TRY(launch_stage_sample(ctx, dt == VAP_F64, B, W, S, s, nullptr, d_x, d_y, d_heading));
+    // grid and fp64 rows (none in the other modes: the rows are the caller's); the tables of an earlier call stay, NS cleared
+    ctx->left.leave(B, W, S, dt, s.hi ? VAP_ROWS_HI : VAP_ROWS_NONE, 0, false);
     return VAP_OK;
 }
 
@@ -423,29 +522,11 @@ int vap_velocity_pass_limits(vap_ctx *ctx, vap_dtype dt, int B, int S, const vap
         return vap_fail(VAP_ERR_INVALID, "VAP_F32 with VAP_RECURRENCE_F64: the limit rows are fp64 and go with the context's fp64 rows "
                                          "(d_dtheta = NULL); for an fp32 recurrence on caller rows set VAP_OPT_F32_RECURRENCE first");
     bool r64 = dt == VAP_F64;
-    if (!d_dtheta) {    // the rows the last sampling call of this shape and dtype left on the context
-        if (!ctx->rows_valid || ctx->grid_B != B || ctx->grid_S != S || ctx->rows_dt != (int)dt)
-            return vap_fail(VAP_ERR_INVALID, "d_dtheta is NULL and the context holds no rows of this shape and dtype (%d x %d, dtype %d; "
-                            "the last sampling call left %s %d x %d, dtype %d)", B, S, (int)dt, ctx->rows_valid ? "rows of" : "no rows;",
-                            ctx->grid_B, ctx->grid_S, ctx->rows_dt);
-        if (ctx->rows_hi) {   // VAP_F32 with the fp64 recurrence: both rows come from the context, in fp64
-            d_curvature = ctx->k64.ptr;
-            d_dtheta = ctx->dth64.ptr;
-            r64 = true;
-        } else {
-            d_dtheta = ctx->dth.ptr;
-        }
-    }
+    if (!d_dtheta) VAP_TRY(vap_ctx_rows(ctx, dt, B, S, d_curvature, d_dtheta, r64));   // the rows the last sampling call left
     if (!d_curvature) return vap_fail(VAP_ERR_INVALID, "null curvature row");
-    // Quirk Q9: boundary_map always holds sample 0 (MPG:110), so the reference overwrites max_dec with
-    // max_accels[0] — max_acc for a plain node — before the first forward step (MPG:194-196) and never
-    // restores it until the pass returns: the backward sweep decelerates with max_acc.  (The time loop
-    // does see the caller's max_dec, MPG:572-573 — vap_time_profile.)
-    const double cc[6] = {c->max_vel, c->max_acc, c->max_acc, c->friction_coef, c->max_jerk, c->track_width};
-    vap::AccRowsV acc;
-    acc.fwd = d_acc_forward;
-    acc.bwd = d_acc_backward;
-    acc.dec = d_dec_backward;
+    double cc[6];
+    velocity_consts(c, cc);
+    const vap::AccRowsV acc{d_acc_forward, d_acc_backward, d_dec_backward};
     VAP_TRY(run_velocity(ctx, r64, dt == VAP_F64, B, S, cc, start_vel, end_vel, d_meta, d_curvature, d_dtheta, d_vcap, acc,
                          d_velocity, d_flags));
     return VAP_OK;
@@ -473,82 +554,26 @@ int vap_profile_batch(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, double dd
     VAP_TRY(check_shape(B, W, S));
     if (!d_waypoints || !c || !d_velocity) return vap_fail(VAP_ERR_INVALID, "null buffer");
     const bool f64 = dt == VAP_F64;
-    const size_t n_seg = (size_t)B * (W - 1), n_pts = (size_t)B * S;
-    VAP_TRY(ctx->ensure(ctx->seg, n_seg * 12 * sizeof(double)));
-    VAP_TRY(ctx->ensure(ctx->power, n_seg * vap::kCoefBlockDoubles * sizeof(double)));
-    VAP_TRY(ctx->ensure(ctx->lut, (size_t)B * VAP_LUT_SAMPLES * sizeof(double)));
-    VAP_TRY(ctx->ensure(ctx->aux, (size_t)B * 4 * sizeof(double)));
-    VAP_TRY(ctx->ensure(ctx->runs, (size_t)B * vap::kGridRunBlockDoubles * sizeof(double)));
-    // VAP_F32 with the fp64 recurrence (the default): the velocity pass reads fp64 curvature / |dtheta| rows
-    const bool hi = !f64 && ctx->f32_recurrence == VAP_RECURRENCE_F64;
-    if (hi) {
-        VAP_TRY(ctx->ensure(ctx->k64, n_pts * sizeof(double)));
-        VAP_TRY(ctx->ensure(ctx->dth64, n_pts * sizeof(double)));
-    } else {
-        VAP_TRY(ctx->ensure(ctx->dth, n_pts * esz(dt)));
-    }
-    double *meta = d_meta;
-    if (!meta) {
-        VAP_TRY(ctx->ensure(ctx->meta, (size_t)B * 4 * sizeof(double)));
-        meta = (double *)ctx->meta.ptr;
-    }
-    uint32_t *flags = d_flags;
-    if (!flags) {
-        VAP_TRY(ctx->ensure(ctx->flags, (size_t)B * sizeof(uint32_t)));
-        flags = (uint32_t *)ctx->flags.ptr;
-    }
-    void *curv = d_curvature;
-    if (!curv && !hi) {
-        VAP_TRY(ctx->ensure(ctx->io[7], n_pts * esz(dt)));
-        curv = ctx->io[7].ptr;
-    }
-    // Quirk Q9: boundary_map always holds sample 0 (MPG:110), so the reference overwrites max_dec with
-    // max_accels[0] — max_acc for a plain node — before the first forward step (MPG:194-196) and never
-    // restores it until the pass returns: the backward sweep decelerates with max_acc.  (The time loop
-    // does see the caller's max_dec, MPG:572-573 — vap_time_profile.)
-    const double cc[6] = {c->max_vel, c->max_acc, c->max_acc, c->friction_coef, c->max_jerk, c->track_width};
+    Stage s;
+    VAP_TRY(fused_stage(ctx, dt, B, W, S, 0, d_meta, d_flags, d_curvature, s));
     StageTimer tm(ctx);
-    vap::GridArgs grid;     // the distance grid is defined in the tail of the table kernel
-    grid.S = S;
-    grid.dd = dd;
-    grid.aux = (double *)ctx->aux.ptr;
-    grid.runs = (double *)ctx->runs.ptr;
+    // the distance grid is defined in the tail of the table kernel
+    const vap::GridArgs grid{S, dd, (double *)ctx->aux.ptr, (double *)ctx->runs.ptr};
     if (vap::fit_lut_fusable(B, W)) {
         // fit and table of a path by one workgroup, one launch (VAP_T_FIT then reads 0, VAP_T_LUT the pair)
         tm.mark(VAP_T_FIT);
         HIP_TRY(vap::launch_fit_lut(ctx->stream, f64, B, W, d_waypoints, (double *)ctx->seg.ptr, (double *)ctx->power.ptr,
-                                    (double *)ctx->lut.ptr, meta, flags, grid));
+                                    (double *)ctx->lut.ptr, s.meta, s.flags, grid));
     } else {
         HIP_TRY(vap::launch_fit(ctx->stream, f64, B, W, d_waypoints, nullptr, nullptr, (double *)ctx->seg.ptr,
-                                (double *)ctx->power.ptr, nullptr, meta, flags));
+                                (double *)ctx->power.ptr, nullptr, s.meta, s.flags));
         tm.mark(VAP_T_FIT);
-        HIP_TRY(vap::launch_lut(ctx->stream, B, W, (const double *)ctx->seg.ptr, (double *)ctx->lut.ptr,
-                                nullptr, meta, flags, grid));   // (the sampling kernel forms the interval slopes itself)
+        HIP_TRY(vap::launch_lut(ctx->stream, B, W, s.seg, (double *)ctx->lut.ptr, nullptr, s.meta, s.flags,
+                                grid));   // (the sampling kernel forms the interval slopes itself)
     }
     tm.mark(VAP_T_LUT);
-    {
-        HIP_TRY(vap::launch_sample(ctx->stream, f64, B, W, S, (const double *)ctx->power.ptr, (const double *)ctx->lut.ptr, nullptr,
-                                   meta, (const double *)ctx->aux.ptr, (const double *)ctx->runs.ptr, d_x, d_y, d_heading,
-                                   curv, hi ? nullptr : ctx->dth.ptr, hi ? (double *)ctx->k64.ptr : nullptr,
-                                   hi ? (double *)ctx->dth64.ptr : nullptr, (const double *)ctx->seg.ptr));
-        tm.mark(VAP_T_SAMPLE);
-        if (hi)
-            VAP_TRY(run_velocity(ctx, true, false, B, S, cc, start_vel, end_vel, meta, ctx->k64.ptr, ctx->dth64.ptr, nullptr,
-                                 vap::AccRowsV(), d_velocity, flags));
-        else
-            VAP_TRY(run_velocity(ctx, f64, f64, B, S, cc, start_vel, end_vel, meta, curv, ctx->dth.ptr, nullptr, vap::AccRowsV(),
-                                 d_velocity, flags));
-    }
-    tm.mark(VAP_T_VELOCITY);
-    ctx->last_B = B;
-    ctx->last_W = W;
-    ctx->grid_B = B;
-    ctx->grid_W = W;
-    ctx->grid_S = S;
-    ctx->rows_valid = true;
-    ctx->rows_hi = hi;
-    ctx->rows_dt = dt;
-    ctx->route_NS = 0;
+    VAP_TRY(sample_and_velocity(ctx, tm, dt, B, W, S, s, nullptr, c, start_vel, end_vel, d_x, d_y, d_heading, d_velocity));
+    ctx->left.leave(B, W, S, dt, s.hi ? VAP_ROWS_HI : VAP_ROWS_DTH, 0, true);       // tables, grid and rows of plain paths
     return VAP_OK;
 }
 
@@ -568,90 +593,26 @@ int vap_profile_routes(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, double d
     if (d_node_tangent && !d_node_magnitudes) return vap_fail(VAP_ERR_INVALID, "node tangents come with their magnitudes");
     const bool f64 = dt == VAP_F64;
     const int NS = max_splines;
-    const size_t n_seg = (size_t)B * (W - 1), n_pts = (size_t)B * S;
-    VAP_TRY(ctx->ensure(ctx->seg, n_seg * 12 * sizeof(double)));
-    VAP_TRY(ctx->ensure(ctx->power, n_seg * vap::kCoefBlockDoubles * sizeof(double)));
-    VAP_TRY(ctx->ensure(ctx->lut, (size_t)B * NS * VAP_LUT_SAMPLES * sizeof(double)));
-    VAP_TRY(ctx->ensure(ctx->sptab, (size_t)B * NS * 4 * sizeof(double)));
-    VAP_TRY(ctx->ensure(ctx->nspl, (size_t)B * sizeof(int)));
-    VAP_TRY(ctx->ensure(ctx->aux, (size_t)B * 4 * sizeof(double)));
-    VAP_TRY(ctx->ensure(ctx->runs, (size_t)B * vap::kGridRunBlockDoubles * sizeof(double)));
-    const bool hi = !f64 && ctx->f32_recurrence == VAP_RECURRENCE_F64;
-    if (hi) {
-        VAP_TRY(ctx->ensure(ctx->k64, n_pts * sizeof(double)));
-        VAP_TRY(ctx->ensure(ctx->dth64, n_pts * sizeof(double)));
-    } else {
-        VAP_TRY(ctx->ensure(ctx->dth, n_pts * esz(dt)));
-    }
-    double *meta = d_meta;
-    if (!meta) {
-        VAP_TRY(ctx->ensure(ctx->meta, (size_t)B * 4 * sizeof(double)));
-        meta = (double *)ctx->meta.ptr;
-    }
-    uint32_t *flags = d_flags;
-    if (!flags) {
-        VAP_TRY(ctx->ensure(ctx->flags, (size_t)B * sizeof(uint32_t)));
-        flags = (uint32_t *)ctx->flags.ptr;
-    }
-    void *curv = d_curvature;
-    if (!curv && !hi) {
-        VAP_TRY(ctx->ensure(ctx->io[7], n_pts * esz(dt)));
-        curv = ctx->io[7].ptr;
-    }
-    const double cc[6] = {c->max_vel, c->max_acc, c->max_acc, c->friction_coef, c->max_jerk, c->track_width};   // quirk Q9
-    vap::RouteSplitInputs in;
-    in.rev = d_node_reverse;
-    in.turn = d_node_turn;
-    in.tangent = d_node_tangent;
-    in.mag = d_node_magnitudes;
+    Stage s;
+    VAP_TRY(fused_stage(ctx, dt, B, W, S, NS, d_meta, d_flags, d_curvature, s));
+    const vap::RouteSplitInputs in{d_node_reverse, d_node_turn, d_node_tangent, d_node_magnitudes};
     double *sptab = (double *)ctx->sptab.ptr;
     int *nspl = (int *)ctx->nspl.ptr;
+    const vap::RouteTables rt{sptab, nspl, NS};
     StageTimer tm(ctx);
     HIP_TRY(vap::launch_fit_routes(ctx->stream, f64, B, W, NS, d_waypoints, in, (double *)ctx->seg.ptr, (double *)ctx->power.ptr,
-                                   nullptr, sptab, nspl, meta, flags));
+                                   nullptr, sptab, nspl, s.meta, s.flags));
     tm.mark(VAP_T_FIT);
-    vap::RouteTables rt;
-    rt.sptab = sptab;
-    rt.nspl = nspl;
-    rt.NS = NS;
-    // No route of the batch has a split (max_splines == 1: tangent overrides at most): every route is one spline with
-    // zero offsets, i.e. a plain path — the persistent sampling kernel of vap_profile_batch takes it, same rows bit for bit as that entry point and 3-4x faster than the
-    // thread-per-sample kernel the concatenated tables need.
-    const bool single = NS == 1;
-    HIP_TRY(vap::launch_lut(ctx->stream, B, W, (const double *)ctx->seg.ptr, (double *)ctx->lut.ptr, nullptr, meta, flags,
-                            vap::GridArgs(), rt));
-    HIP_TRY(vap::launch_route_offsets(ctx->stream, B, W, NS, S, dd, (const double *)ctx->lut.ptr, sptab, nspl, meta,
-                                      (double *)ctx->aux.ptr, (double *)ctx->runs.ptr, flags));
+    HIP_TRY(vap::launch_lut(ctx->stream, B, W, s.seg, (double *)ctx->lut.ptr, nullptr, s.meta, s.flags, vap::GridArgs(), rt));
+    HIP_TRY(vap::launch_route_offsets(ctx->stream, B, W, NS, S, dd, s.lut, sptab, nspl, s.meta, (double *)ctx->aux.ptr,
+                                      (double *)ctx->runs.ptr, s.flags));
     tm.mark(VAP_T_LUT);
-    if (single)
-        HIP_TRY(vap::launch_sample(ctx->stream, f64, B, W, S, (const double *)ctx->power.ptr, (const double *)ctx->lut.ptr,
-                                   nullptr, meta, (const double *)ctx->aux.ptr,
-                                   (const double *)ctx->runs.ptr, d_x, d_y, d_heading, curv, hi ? nullptr : ctx->dth.ptr,
-                                   hi ? (double *)ctx->k64.ptr : nullptr, hi ? (double *)ctx->dth64.ptr : nullptr,
-                                   (const double *)ctx->seg.ptr));
-    else
-        HIP_TRY(vap::launch_sample_routes(ctx->stream, f64, B, W, NS, S, (const double *)ctx->power.ptr, (const double *)ctx->lut.ptr,
-                                          sptab, nspl, meta, (const double *)ctx->aux.ptr, (const double *)ctx->runs.ptr, d_x, d_y,
-                                          d_heading, curv, hi ? nullptr : ctx->dth.ptr, hi ? (double *)ctx->k64.ptr : nullptr,
-                                          hi ? (double *)ctx->dth64.ptr : nullptr, (const double *)ctx->seg.ptr));
-    tm.mark(VAP_T_SAMPLE);
-    if (hi)
-        VAP_TRY(run_velocity(ctx, true, false, B, S, cc, start_vel, end_vel, meta, ctx->k64.ptr, ctx->dth64.ptr, nullptr,
-                             vap::AccRowsV(), d_velocity, flags));
-    else
-        VAP_TRY(run_velocity(ctx, f64, f64, B, S, cc, start_vel, end_vel, meta, curv, ctx->dth.ptr, nullptr, vap::AccRowsV(),
-                             d_velocity, flags));
-    tm.mark(VAP_T_VELOCITY);
+    // No route of the batch has a split (max_splines == 1: tangent overrides at most): every route is one spline with
+    // zero offsets, i.e. a plain path — the persistent sampling kernel of vap_profile_batch takes it, same rows bit for bit
+    // as that entry point and 3-4x faster than the thread-per-sample kernel the concatenated tables need.
+    VAP_TRY(sample_and_velocity(ctx, tm, dt, B, W, S, s, NS == 1 ? nullptr : &rt, c, start_vel, end_vel, d_x, d_y, d_heading, d_velocity));
     if (d_spline_counts) HIP_TRY(hipMemcpyAsync(d_spline_counts, nspl, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, ctx->stream));
-    ctx->last_B = B;
-    ctx->last_W = W;
-    ctx->grid_B = B;
-    ctx->grid_W = W;
-    ctx->grid_S = S;
-    ctx->rows_valid = true;
-    ctx->rows_hi = hi;
-    ctx->rows_dt = dt;
-    ctx->route_NS = NS;
+    ctx->left.leave(B, W, S, dt, s.hi ? VAP_ROWS_HI : VAP_ROWS_DTH, NS, true);      // tables, grid and rows of routes
     return VAP_OK;
 }
 
@@ -668,15 +629,12 @@ int vap_route_limits(vap_ctx *ctx, vap_dtype dt, int B, int W, int M, int S, con
     const bool any_acc = d_acc_forward || d_acc_backward || d_dec_backward;
     if (any_acc && !(d_acc_forward && d_acc_backward && d_dec_backward))
         return vap_fail(VAP_ERR_INVALID, "the max_acceleration outputs come as a set (forward, backward, dec)");
-    if (ctx->grid_B != B || ctx->grid_W != W || ctx->grid_S != S || !ctx->runs.ptr || !ctx->aux.ptr)
-        return vap_fail(VAP_ERR_INVALID, "no distance grid of this shape on the context (%d x %d x %d; the last sampling call left %d x %d x %d)",
-                        B, W, S, ctx->grid_B, ctx->grid_W, ctx->grid_S);
-    const double *lut = d_lut;
-    if (!lut) {
-        if (ctx->last_B != B || ctx->last_W != W || !ctx->lut.ptr)
-            return vap_fail(VAP_ERR_INVALID, "d_lut is NULL and the context holds no table of this shape");
-        lut = (const double *)ctx->lut.ptr;
-    }
+    const double *aux, *runs;
+    VAP_TRY(vap_ctx_grid(ctx, B, W, S, aux, runs));
+    VapTables t;
+    t.lut = d_lut;
+    if (!d_lut && vap_ctx_tables(ctx, B, W, false, t) != VAP_OK)
+        return vap_fail(VAP_ERR_INVALID, "d_lut is NULL and the context holds no table of this shape");
     // scratch: node samples, action samples, merged event list {sample, max_velocity, max_acceleration, stop}
     const size_t E = (size_t)(W > 2 ? W - 2 : 0) + M;
     const size_t n_int = (size_t)B * (W + M + 2 * E), n_dbl = (size_t)B * 2 * E;
@@ -686,27 +644,14 @@ int vap_route_limits(vap_ctx *ctx, vap_dtype dt, int B, int W, int M, int S, con
     int *ap_k = node_k + (size_t)B * W;
     int *ev_k = ap_k + (size_t)B * M;
     int *ev_stop = ev_k + (size_t)B * E;
-    vap::LimitInputs in;
-    in.node_mv = d_node_max_velocity;
-    in.node_ma = d_node_max_acceleration;
-    in.node_stop = d_node_stop;
-    in.ap_t = d_action_t;
-    in.ap_mv = d_action_max_velocity;
-    in.ap_ma = d_action_max_acceleration;
-    in.ap_stop = d_action_stop;
-    in.max_vel = c->max_vel;
-    in.max_acc = c->max_acc;
-    in.end_vel = end_vel;
-    vap::RouteTables rt;
-    if (ctx->route_NS > 0) {   // the batch on the context is one of routes cut into splines: its own tables only
-        if (d_lut) return vap_fail(VAP_ERR_INVALID, "a batch of routes (vap_profile_routes) is on the context: d_lut must be NULL");
-        rt.sptab = (const double *)ctx->sptab.ptr;
-        rt.nspl = (const int *)ctx->nspl.ptr;
-        rt.NS = ctx->route_NS;
-    }
-    HIP_TRY(vap::launch_route_limits(ctx->stream, vap_limit_rows_dtype(ctx, dt) == VAP_F64, B, W, M, S, lut, d_meta, (const double *)ctx->aux.ptr,
-                                     (const double *)ctx->runs.ptr, in, node_k, ap_k, ev_k, ev_mv, ev_ma, ev_stop, d_vcap,
-                                     d_acc_forward, d_acc_backward, d_dec_backward, rt));
+    const vap::LimitInputs in{d_node_max_velocity, d_node_max_acceleration, d_node_stop, d_action_t, d_action_max_velocity,
+                              d_action_max_acceleration, d_action_stop, c->max_vel, c->max_acc, end_vel};
+    // the batch on the context is one of routes cut into splines: its own tables only
+    if (d_lut && ctx->left.routes())
+        return vap_fail(VAP_ERR_INVALID, "a batch of routes (vap_profile_routes) is on the context: d_lut must be NULL");
+    HIP_TRY(vap::launch_route_limits(ctx->stream, vap_limit_rows_dtype(ctx, dt) == VAP_F64, B, W, M, S, t.lut, d_meta, aux, runs, in,
+                                     node_k, ap_k, ev_k, ev_mv, ev_ma, ev_stop, d_vcap, d_acc_forward, d_acc_backward, d_dec_backward,
+                                     t.rt));
     if (d_node_sample) HIP_TRY(hipMemcpyAsync(d_node_sample, node_k, sizeof(int) * (size_t)B * W, hipMemcpyDeviceToDevice, ctx->stream));
     if (d_action_sample && M > 0)
         HIP_TRY(hipMemcpyAsync(d_action_sample, ap_k, sizeof(int) * (size_t)B * M, hipMemcpyDeviceToDevice, ctx->stream));
@@ -721,23 +666,10 @@ int vap_time_profile(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, const doub
     VAP_TRY(check_shape(B, W, S));
     if (!d_meta || !d_velocity || !c || !d_rows || !d_counts || !d_nodes_map) return vap_fail(VAP_ERR_INVALID, "null buffer");
     if (!(time_step > 0) || capacity_rows < 1) return vap_fail(VAP_ERR_INVALID, "time_step and capacity_rows must be positive");
-    if ((d_segments == nullptr) != (d_lut == nullptr)) return vap_fail(VAP_ERR_INVALID, "pass both d_segments and d_lut, or neither");
-    if (!d_segments) {
-        if (ctx->last_B != B || ctx->last_W != W || !ctx->seg.ptr || !ctx->lut.ptr)
-            return vap_fail(VAP_ERR_UNFITTED, "no tables of a %d x %d batch in this context (last vap_profile_batch: %d x %d)", B,
-                            W, ctx->last_B, ctx->last_W);
-        if (ctx->route_NS > 0)
-            return vap_fail(VAP_ERR_UNSUPPORTED, "the batch on the context is one of split routes (vap_profile_routes): their "
-                                                 "time domain goes through vap_time_profile_routes / vap_time_insert_events");
-        d_segments = (const double *)ctx->seg.ptr;
-        d_lut = (const double *)ctx->lut.ptr;
-    }
-    bool v64;
-    const float *vres;
-    const void *vrow = time_domain_velocity(ctx, dt, B, S, d_velocity, v64, vres);
-    HIP_TRY(vap::launch_time_profile(ctx->stream, v64, B, W, S, d_segments, d_lut, d_meta, vrow, c->max_acc,
+    VAP_TRY(plain_tables(ctx, B, W, d_segments, d_lut));
+    HIP_TRY(vap::launch_time_profile(ctx->stream, dt == VAP_F64, B, W, S, d_segments, d_lut, d_meta, d_velocity, c->max_acc,
                                      c->max_dec, time_step, capacity_rows, d_rows, d_counts, d_nodes_map, d_flags, vap::RouteTables(),
-                                     nullptr, vres, ctx->time_kernel));
+                                     nullptr, vap_ctx_residual(ctx, dt, B, S, d_velocity), ctx->time_kernel));
     return VAP_OK;
 }
 
@@ -748,23 +680,9 @@ int vap_time_insert_waits(vap_ctx *ctx, int B, int W, int M, int capacity_in, in
                           int *d_nodes_map_out, int *d_actions_map_out, uint32_t *d_flags)
 {
     VAP_TRY(vap_set_device(ctx));
-    VAP_TRY(check_shape(B, W, 2));
-    if (M < 0 || capacity_in < 1 || capacity_out < 1 || !(time_step > 0)) return vap_fail(VAP_ERR_INVALID, "bad argument");
-    if (!d_meta || !d_rows_in || !d_counts_in || !d_nodes_map_in || !d_rows_out || !d_counts_out || !d_nodes_map_out)
-        return vap_fail(VAP_ERR_INVALID, "null buffer");
-    if (M > 0 && (!d_action_t || !d_actions_map_out)) return vap_fail(VAP_ERR_INVALID, "null action-point array");
-    if (d_rows_out == d_rows_in) return vap_fail(VAP_ERR_INVALID, "the rows move: d_rows_out must not be d_rows_in");
-    if ((d_segments == nullptr) != (d_lut == nullptr)) return vap_fail(VAP_ERR_INVALID, "pass both d_segments and d_lut, or neither");
-    if (!d_segments) {
-        if (ctx->last_B != B || ctx->last_W != W || !ctx->seg.ptr || !ctx->lut.ptr)
-            return vap_fail(VAP_ERR_UNFITTED, "no tables of a %d x %d batch in this context (last vap_profile_batch: %d x %d)", B,
-                            W, ctx->last_B, ctx->last_W);
-        if (ctx->route_NS > 0)
-            return vap_fail(VAP_ERR_UNSUPPORTED, "the batch on the context is one of split routes (vap_profile_routes): their "
-                                                 "time domain goes through vap_time_profile_routes / vap_time_insert_events");
-        d_segments = (const double *)ctx->seg.ptr;
-        d_lut = (const double *)ctx->lut.ptr;
-    }
+    VAP_TRY(check_insert_args(B, W, M, capacity_in, capacity_out, time_step, true, d_meta, d_rows_in, d_counts_in, d_nodes_map_in,
+                              d_action_t, d_rows_out, d_counts_out, d_nodes_map_out, d_actions_map_out));
+    VAP_TRY(plain_tables(ctx, B, W, d_segments, d_lut));
     HIP_TRY(vap::launch_time_waits(ctx->stream, B, W, M, capacity_in, capacity_out, time_step, d_segments, d_lut, d_meta,
                                    d_rows_in, d_counts_in, d_nodes_map_in, d_node_wait, d_action_t, d_action_wait, d_rows_out,
                                    d_counts_out, d_nodes_map_out, d_actions_map_out, d_flags));
@@ -779,21 +697,11 @@ int vap_time_profile_routes(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, con
     VAP_TRY(check_shape(B, W, S));
     if (!d_meta || !d_velocity || !c || !d_rows || !d_counts || !d_nodes_map) return vap_fail(VAP_ERR_INVALID, "null buffer");
     if (!(time_step > 0) || capacity_rows < 1) return vap_fail(VAP_ERR_INVALID, "time_step and capacity_rows must be positive");
-    if (ctx->last_B != B || ctx->last_W != W || !ctx->seg.ptr || !ctx->lut.ptr)
-        return vap_fail(VAP_ERR_UNFITTED, "no tables of a %d x %d batch in this context (last profile call: %d x %d)", B, W,
-                        ctx->last_B, ctx->last_W);
-    vap::RouteTables rt;
-    if (ctx->route_NS > 0) {
-        rt.sptab = (const double *)ctx->sptab.ptr;
-        rt.nspl = (const int *)ctx->nspl.ptr;
-        rt.NS = ctx->route_NS;
-    }
-    bool v64;
-    const float *vres;
-    const void *vrow = time_domain_velocity(ctx, dt, B, S, d_velocity, v64, vres);
-    HIP_TRY(vap::launch_time_profile(ctx->stream, v64, B, W, S, (const double *)ctx->seg.ptr, (const double *)ctx->lut.ptr,
-                                     d_meta, vrow, c->max_acc, c->max_dec, time_step, capacity_rows, d_rows, d_counts,
-                                     d_nodes_map, d_flags, rt, d_node_reverse, vres, ctx->time_kernel));
+    VapTables t;
+    VAP_TRY(vap_ctx_tables(ctx, B, W, false, t));
+    HIP_TRY(vap::launch_time_profile(ctx->stream, dt == VAP_F64, B, W, S, t.seg, t.lut, d_meta, d_velocity, c->max_acc, c->max_dec,
+                                     time_step, capacity_rows, d_rows, d_counts, d_nodes_map, d_flags, t.rt, d_node_reverse,
+                                     vap_ctx_residual(ctx, dt, B, S, d_velocity), ctx->time_kernel));
     return VAP_OK;
 }
 
@@ -804,27 +712,16 @@ int vap_time_insert_events(vap_ctx *ctx, int B, int W, int M, int capacity_in, i
                            int *d_counts_out, int *d_nodes_map_out, int *d_actions_map_out, uint32_t *d_flags)
 {
     VAP_TRY(vap_set_device(ctx));
-    VAP_TRY(check_shape(B, W, 2));
-    if (M < 0 || capacity_in < 1 || capacity_out < 1 || !(time_step > 0) || !c) return vap_fail(VAP_ERR_INVALID, "bad argument");
-    if (!d_meta || !d_rows_in || !d_counts_in || !d_nodes_map_in || !d_rows_out || !d_counts_out || !d_nodes_map_out)
-        return vap_fail(VAP_ERR_INVALID, "null buffer");
-    if (M > 0 && (!d_action_t || !d_actions_map_out)) return vap_fail(VAP_ERR_INVALID, "null action-point array");
-    if (d_rows_out == d_rows_in) return vap_fail(VAP_ERR_INVALID, "the rows move: d_rows_out must not be d_rows_in");
+    VAP_TRY(check_insert_args(B, W, M, capacity_in, capacity_out, time_step, c != nullptr, d_meta, d_rows_in, d_counts_in, d_nodes_map_in,
+                              d_action_t, d_rows_out, d_counts_out, d_nodes_map_out, d_actions_map_out));
     if (d_node_turn && !(c->max_vel > 0 && c->max_acc > 0 && c->track_width > 0))
         return vap_fail(VAP_ERR_INVALID, "in-place turns need max_vel, max_acc and track_width");
-    if (ctx->last_B != B || ctx->last_W != W || !ctx->seg.ptr || !ctx->lut.ptr)
-        return vap_fail(VAP_ERR_UNFITTED, "no tables of a %d x %d batch in this context (last profile call: %d x %d)", B, W,
-                        ctx->last_B, ctx->last_W);
-    vap::RouteTables rt;
-    if (ctx->route_NS > 0) {
-        rt.sptab = (const double *)ctx->sptab.ptr;
-        rt.nspl = (const int *)ctx->nspl.ptr;
-        rt.NS = ctx->route_NS;
-    }
-    HIP_TRY(vap::launch_time_waits(ctx->stream, B, W, M, capacity_in, capacity_out, time_step, (const double *)ctx->seg.ptr,
-                                   (const double *)ctx->lut.ptr, d_meta, d_rows_in, d_counts_in, d_nodes_map_in, d_node_wait,
-                                   d_action_t, d_action_wait, d_rows_out, d_counts_out, d_nodes_map_out, d_actions_map_out, d_flags, rt,
-                                   d_node_turn, d_node_reverse, c->max_vel, c->max_acc, c->track_width));
+    VapTables t;
+    VAP_TRY(vap_ctx_tables(ctx, B, W, false, t));
+    HIP_TRY(vap::launch_time_waits(ctx->stream, B, W, M, capacity_in, capacity_out, time_step, t.seg, t.lut, d_meta, d_rows_in,
+                                   d_counts_in, d_nodes_map_in, d_node_wait, d_action_t, d_action_wait, d_rows_out, d_counts_out,
+                                   d_nodes_map_out, d_actions_map_out, d_flags, t.rt, d_node_turn, d_node_reverse, c->max_vel,
+                                   c->max_acc, c->track_width));
     return VAP_OK;
 }
 

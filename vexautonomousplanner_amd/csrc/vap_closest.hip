@@ -17,8 +17,7 @@
 #include <cstdint>
 
 #include "vap_device.h"
-#include "vap_internal.h"
-#include "vap_kernels.h"
+#include "vap_ctx_state.h"
 
 namespace vap {
 
@@ -419,9 +418,8 @@ int vap_closest_points(vap_ctx *ctx, int B, int W, int Q, int mode, int shared_q
     VAP_TRY(vap_set_device(ctx));
     if (B < 1 || W < 2 || Q < 0) return vap_fail(VAP_ERR_INVALID, "bad shape B=%d W=%d Q=%d", B, W, Q);
     if (mode != VAP_CLOSEST_GUI && mode != VAP_CLOSEST_EXACT) return vap_fail(VAP_ERR_INVALID, "mode must be VAP_CLOSEST_GUI or VAP_CLOSEST_EXACT");
-    if (ctx->last_B != B || ctx->last_W != W || !ctx->seg.ptr || !ctx->lut.ptr)
-        return vap_fail(VAP_ERR_UNFITTED, "no tables of a %d x %d batch in this context (last profile call: %d x %d)", B, W,
-                        ctx->last_B, ctx->last_W);
+    VapTables t;
+    VAP_TRY(vap_ctx_tables(ctx, B, W, false, t));
     if (Q == 0) return VAP_OK;
     if (!d_queries) return vap_fail(VAP_ERR_INVALID, "null query buffer");
     if ((Q + vap::kClosestQueriesPerBlock - 1) / vap::kClosestQueriesPerBlock > vap::kClosestMaxQueryBlocks)
@@ -429,16 +427,15 @@ int vap_closest_points(vap_ctx *ctx, int B, int W, int Q, int mode, int shared_q
                         vap::kClosestMaxQueryBlocks * vap::kClosestQueriesPerBlock);
     vap::ClosestSrc src;
     src.W = W;
-    src.seg = (const double *)ctx->seg.ptr;
-    src.lut = (const double *)ctx->lut.ptr;
+    src.seg = t.seg;
+    src.lut = t.lut;
     src.lut_n = vap::kLutN;
-    if (ctx->route_NS > 0) {
-        src.sptab = (const double *)ctx->sptab.ptr;
-        src.nspl = (const int *)ctx->nspl.ptr;
-        src.NS = ctx->route_NS;
-        src.lut_stride = (size_t)ctx->route_NS * vap::kLutN;
-    } else {
-        src.lut_stride = vap::kLutN;
+    src.lut_stride = vap::kLutN;
+    if (t.rt.sptab) {
+        src.sptab = t.rt.sptab;
+        src.nspl = t.rt.nspl;
+        src.NS = t.rt.NS;
+        src.lut_stride = (size_t)t.rt.NS * vap::kLutN;
     }
     HIP_TRY(vap::launch_closest(ctx->stream, src, B, Q, mode, shared_queries, d_queries, d_parameter, d_point, d_distance,
                                 d_arc_length, d_cross_track, d_flags));
