@@ -926,6 +926,63 @@ int vap_routine_timeline(vap_ctx *ctx, int R, int M, int L, int capacity_in, int
                          const double *d_start_heading, double *d_rows_out, int *d_counts_out, int *d_map, double *d_seam,
                          uint32_t *d_flags);
 
+/* ---- a routine's visiting order by the clock ----------------------------------------------------------------------------------
+ * vap_plan_order orders the sites by any P x P cost, which cannot carry what a routine's time is made of: a routine lasts
+ * rows * dt, and its rows are, slot by slot, the rows of the turn on the spot (which depend on the heading the robot arrives
+ * with, so on the leg before), the leg's own rows and int(dwell / dt).  vap_plan_order_timed runs Held-Karp over (site set,
+ * last site, site before it) on exactly these integers, read from the legs' time-domain rows, so that its total for an order
+ * IS, bit for bit, the row count vap_routine_timeline gives for that order; optionally it selects the subset of sites worth
+ * the most under a row budget.  The reference has neither (a routine is a hand-ordered list of nodes, gui/path.py).
+ *   points    point 0 is the start, points 1 .. M = P - 1 are the sites, 1 <= M <= 8 (VAP_PLAN_ORDER_TIMED_MAX_SITES): the
+ *             table is 2^M * M * M int32 plus a parent byte each, 80 KiB of LDS at M = 8; at M = 9 it would be 166 KB and
+ *             leaves the LDS, so P > 9 is VAP_ERR_UNSUPPORTED.
+ *   legs      d_rows [L][capacity][8], d_counts [L * counts_stride] (entry l * counts_stride = rows of leg l): L legs on the
+ *             device, exactly as vap_routine_timeline takes them, all on the time step `time_step`.  d_leg [R][P][P] int32:
+ *             the leg from point a to point b of problem r; column 0 and the diagonal are never read.  A leg is USABLE iff
+ *             its index is in [0, L), d_leg_flags (uint32 [L], may be NULL) is 0 for it, c = min(count, capacity) > 0, and
+ *             its first and last row pass the timeline's own test: heading (column 4) within [-2 pi, 2 pi], x and y (columns
+ *             6, 7) finite.  Every other leg is forbidden.  For a usable leg n(a, b) = c, hf(a, b) = the heading of row 0,
+ *             hl(a, b) = the heading of row c - 1.
+ *   turn      turn(h_front, h_first) is 0 rows when h_front is NaN.  Otherwise D = h_first - h_front; if D > pi, D -= 2 pi;
+ *             if D <= -pi, D += 2 pi; |D| < turn_min: 0 rows, else the n = ceil((total_time + dt) / dt) rows of the
+ *             timeline's turn for angle = -D with c->max_vel, max_acc, track_width (compiled from the same text).
+ *   dwell     d_dwell [R][P] seconds at SITE j, or NULL; entry 0 is unused.  w(j) = int(dwell / dt) for a dwell > 0,
+ *             saturating at INT_MAX, else 0.
+ *   rows      of a sequence s_1 .. s_k of distinct sites, s_0 = 0:
+ *               sum over m = 1 .. k of [ turn(h_{m-1}, hf(s_{m-1}, s_m)) + n(s_{m-1}, s_m) + w(s_m) ],
+ *             h_0 = d_start_heading[r] (NULL or NaN: none), h_m = hl(s_{m-1}, s_m); arrival_m = the rows in front of slot m
+ *             + its turn + its leg, the timeline's map[r][m - 1][2].  Summed in 64 bits; a sequence of INT_MAX rows or more
+ *             is inadmissible.  A start heading outside [-2 pi, 2 pi] makes the problem infeasible (the empty sequence
+ *             included), as it makes a routine bad.
+ *   admissible  every leg of the sequence is usable; for every visited k every site of before[k] is visited earlier
+ *             (d_before [R][P] uint32 or NULL, the masks of vap_plan_order; entry 0 and bits >= M are ignored); if end >= 1
+ *             the sequence ends at `end` (so the empty sequence is then not admissible); end = -1: it may end anywhere.
+ *   full mode (d_budget_rows == NULL): k = M and the fewest rows win; among equals the sequence that is smallest read
+ *             BACKWARDS: the lowest last site, then the lowest site before it, and so on.  (The table's minimum over (last,
+ *             previous) in lexicographic order and the lowest parent under a strict < at every step back give exactly this;
+ *             the costs are integers, nothing is rounded.)
+ *   budget mode (d_budget_rows [R] int32; negative counts as 0): over all admissible sequences of any k >= 0 with rows <=
+ *             budget: the largest value(S), then the fewest rows, then the smallest S as an integer (bit j - 1 = site j),
+ *             then the backwards rule.  value(S) is the fp64 sum of d_value[r][j] over the sites of S in ascending j,
+ *             starting from 0.0; d_value [R][P] or NULL (1 each; entry 0 unused); an entry that is NaN, negative or infinite
+ *             counts as 0.  With every value positive and an ample budget the result equals full mode's.
+ *   outputs   d_order [R][M] int32: the visited sites in order, then -1; d_n_visited [R] int32; d_rows_total [R] int32;
+ *             d_arrival_rows [R][M] int32, -1 behind the visited slots; d_value_total [R] fp64 (full mode: value of the full
+ *             set); d_flags [R] uint32, optional, written (not OR-ed).  No admissible sequence: order and arrival -1,
+ *             n_visited 0, rows_total -1, value NaN, VAP_ORDER_INFEASIBLE.
+ * One workgroup per problem at a time with the table in LDS.  VAP_ERR_INVALID: P < 2, R < 0, L < 0, a negative capacity,
+ * counts_stride < 1, end outside {-1, 1 .. M}, a null leg or order / n_visited / rows_total / arrival_rows / value_total pointer
+ * with R > 0, a null row or count pointer with R > 0 and L > 0 (rows: and capacity > 0), and every time step, turn_min and
+ * constraints vap_routine_timeline refuses, its rule that a full turn may not exceed 2^20 rows included.  VAP_ERR_UNSUPPORTED:
+ * P > 9.  The arguments are checked before the context is touched.  R = 0 is a no-op.  Works on the context's stream and does
+ * not synchronise; no atomics: two calls give the same bytes. */
+#define VAP_PLAN_ORDER_TIMED_MAX_SITES 8
+int vap_plan_order_timed(vap_ctx *ctx, int R, int P, int L, int capacity, double time_step, const vap_constraints *c,
+                         double turn_min, const double *d_rows, const int *d_counts, int counts_stride, const int *d_leg,
+                         const uint32_t *d_leg_flags, const double *d_dwell, const double *d_start_heading, const double *d_value,
+                         const int *d_budget_rows, int end, const uint32_t *d_before, int *d_order, int *d_n_visited,
+                         int *d_rows_total, int *d_arrival_rows, double *d_value_total, uint32_t *d_flags);
+
 #ifdef __cplusplus
 }
 #endif

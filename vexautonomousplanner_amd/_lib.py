@@ -26,6 +26,7 @@ FLAG_BAD_ROUTE = 8
 PLAN_SNAPPED_START, PLAN_SNAPPED_GOAL, PLAN_NO_FREE, PLAN_UNREACHABLE, PLAN_VERTICES_TRUNCATED = 16, 32, 64, 128, 256
 ORDER_INFEASIBLE = 512
 PLAN_TRAVEL_MAX_POINTS, PLAN_ORDER_MAX_SITES = 16, 10
+PLAN_ORDER_TIMED_MAX_SITES = 8
 TIMELINE_MAX_LEGS = 32
 T_FIT, T_LUT, T_SAMPLE, T_VELOCITY, T_TOTAL, T_COUNT = 0, 1, 2, 3, 4, 8
 OPT_VELOCITY_KERNEL = 0
@@ -69,7 +70,7 @@ EXPORTS = (
     "vap_closest_points", "vap_route_closest", "vap_footprint_clearance", "vap_footprint_conflicts",
     "vap_tracking_rollouts", "vap_search_sample", "vap_search_update", "vap_plan_grid", "vap_plan_seeds",
     "vap_plan_occupancy", "vap_plan_seeds_occupied", "vap_plan_travel", "vap_plan_order",
-    "vap_routine_timeline",
+    "vap_routine_timeline", "vap_plan_order_timed",
 )
 
 
@@ -205,6 +206,8 @@ def lib():
     L.vap_plan_order.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     L.vap_routine_timeline.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(Constraints),
                                        C.c_double, vp, vp, C.c_int] + [vp] * 9
+    L.vap_plan_order_timed.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(Constraints), C.c_double,
+                                       vp, vp, C.c_int] + [vp] * 6 + [C.c_int] + [vp] * 7
     _lib = L
     return L
 

@@ -486,6 +486,15 @@ class BatchedTrajectoryGenerator:
         from . import plan
         return plan.routine(points, scene, waypoints, radius, device=self.device.index, ctx=self.ctx, **kw)
 
+    def plan_timed_routine(self, points, scene, waypoints, radius, **kw):
+        """The visiting order of the sites ``points[1:]`` from ``points[0]`` that takes the fewest seconds — turns on the
+        spot, legs and dwells counted in the rows of the timeline — or, with ``budget=`` seconds, the most valuable sites
+        that fit, and that routine chained into one timeline: travel, profile and time_profile of every pair that can be a
+        leg, vap_plan_order_timed and vap_routine_timeline on this generator's device and context, without a host read (see
+        plan.timed_routine for the keyword arguments and the returned dict)."""
+        from . import plan
+        return plan.timed_routine(self, points, scene, waypoints, radius, **kw)
+
     def plan_occupancy(self, tp, footprint, scene, cell, radius, **kw):
         """The rows of ``tp`` — the dict ``time_profile``, ``insert_waits`` or ``tracking_rollouts`` returned — rasterised
         onto the planner's grid over ``scene``'s field box: per cell the first and last instant and the number of rows at

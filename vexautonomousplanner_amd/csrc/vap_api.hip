@@ -725,17 +725,6 @@ int vap_time_insert_events(vap_ctx *ctx, int B, int W, int M, int capacity_in, i
     return VAP_OK;
 }
 
-// rows of an in-place turn of `angle` radians: turn_profile(...).n of vap_turn.h, in fp64 so that the caller can bound it
-static double turn_rows_host(double angle, double vmax, double amax, double tw, double dt)
-{
-    const double arc = std::fabs(angle) * tw / 2;
-    double t_acc = vmax / amax, total;
-    const double d_acc = 0.5 * amax * (t_acc * t_acc);
-    if (2 * d_acc > arc) total = 2 * std::sqrt(arc / amax);
-    else total = 2 * t_acc + (arc - 2 * d_acc) / vmax;
-    return std::ceil((total + dt) / dt);
-}
-
 int vap_routine_timeline(vap_ctx *ctx, int R, int M, int L, int capacity_in, int capacity_out, double time_step,
                          const vap_constraints *c, double turn_min, const double *d_rows_in, const int *d_counts_in,
                          int counts_stride, const int *d_leg, const int *d_n_legs, const double *d_dwell,
@@ -759,7 +748,7 @@ int vap_routine_timeline(vap_ctx *ctx, int R, int M, int L, int capacity_in, int
     if ((((uintptr_t)d_rows_in) | ((uintptr_t)d_rows_out)) & 15) return vap_fail(VAP_ERR_INVALID, "the rows move 16 bytes at a time: misaligned row pointer");
     if ((long long)R * M > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "R * M above INT_MAX");
     // the longest turn a usable pair of headings can ask for is a full one (headings within [-2 pi, 2 pi], one wrap step)
-    if (!(turn_rows_host(2 * M_PI, c->max_vel, c->max_acc, c->track_width, time_step) <= 1048576.0))
+    if (!(vap_turn_rows_host(2 * M_PI, c->max_vel, c->max_acc, c->track_width, time_step) <= 1048576.0))
         return vap_fail(VAP_ERR_UNSUPPORTED, "a turn of more than 2^20 rows at this time step");
     VAP_TRY(vap_set_device(ctx));
     if (R == 0) return VAP_OK;

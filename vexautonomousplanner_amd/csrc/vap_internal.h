@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <string>
@@ -113,3 +114,15 @@ struct vap_ctx {
 };
 
 int vap_set_device(vap_ctx *ctx);
+
+// rows of an in-place turn of `angle` radians: turn_profile(...).n of vap_turn.h, in fp64 so that the caller can bound it
+// (vap_routine_timeline, vap_plan_order_timed)
+inline double vap_turn_rows_host(double angle, double vmax, double amax, double tw, double dt)
+{
+    const double arc = std::fabs(angle) * tw / 2;
+    double t_acc = vmax / amax, total;
+    const double d_acc = 0.5 * amax * (t_acc * t_acc);
+    if (2 * d_acc > arc) total = 2 * std::sqrt(arc / amax);
+    else total = 2 * t_acc + (arc - 2 * d_acc) / vmax;
+    return std::ceil((total + dt) / dt);
+}

@@ -36,14 +36,6 @@ struct TimelineSlot {       // what the body of one (routine, slot) workgroup ne
     int n_turn, cnt, n_dwell, leg, bad, n_used, has_front;
 };
 
-__device__ inline bool tl_heading_ok(double h) { return fabs(h) <= 2 * M_PI; }   // false for NaN and the infinities
-__device__ inline bool tl_finite(double v) { return fabs(v) <= 1.79769313486231570815e308; }
-__device__ inline double tl_wrap_delta(double d)
-{
-    if (d > M_PI) d -= 2 * M_PI;
-    if (d <= -M_PI) d += 2 * M_PI;
-    return d;
-}
 __device__ inline int tl_sat(long long v) { return v < (long long)INT_MAX ? (int)v : INT_MAX; }
 
 __global__ __launch_bounds__(kTlThreads) void k_routine_timeline(TimelineArgs a)

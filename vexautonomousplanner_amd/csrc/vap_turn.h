@@ -1,5 +1,5 @@
 // vap_turn.h — the in-place turn's wheel-speed profile, shared by the kernels that insert turn rows (k_time_waits,
-// k_routine_timeline).
+// k_routine_timeline) or count them (k_plan_order_timed), and the timeline's tests of a leg's end rows.
 #pragma once
 #include <cmath>
 
@@ -35,6 +35,17 @@ __device__ inline double turn_velocity(const TurnProfile &p, double tt)
     if (tt <= p.t_acc) return p.amax * tt;
     if (tt <= p.total_time - p.t_acc) return p.vpeak;
     return p.vpeak - p.amax * (tt - (p.total_time - p.t_acc));
+}
+
+// what makes a leg's first or last row usable in a timeline, and the change of heading a turn covers: shared by
+// k_routine_timeline and k_plan_order_timed, so that the order's rows are the timeline's
+__device__ inline bool tl_heading_ok(double h) { return fabs(h) <= 2 * M_PI; }   // false for NaN and the infinities
+__device__ inline bool tl_finite(double v) { return fabs(v) <= 1.79769313486231570815e308; }
+__device__ inline double tl_wrap_delta(double d)
+{
+    if (d > M_PI) d -= 2 * M_PI;
+    if (d <= -M_PI) d += 2 * M_PI;
+    return d;
 }
 
 }  // namespace vap

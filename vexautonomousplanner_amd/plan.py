@@ -1,5 +1,5 @@
 """Seed routes through a scene, planned on a grid on the device (vap_plan_grid, vap_plan_seeds, vap_plan_occupancy,
-vap_plan_seeds_occupied, vap_plan_travel, vap_plan_order, include/vap.h).
+vap_plan_seeds_occupied, vap_plan_travel, vap_plan_order, vap_plan_order_timed, include/vap.h).
 
 ``search.refine`` improves a route that is already roughly right: it draws candidates round a mean, coordinate by
 coordinate, and cannot get round an obstacle that is larger than its sigma.  This module gives it the route to start from.
@@ -19,16 +19,23 @@ keeps each problem off the cells occupied within its window of instants.
 
 A routine is a start and a handful of sites: ``travel`` plans every ordered pair of P points at the price of P distance
 fields, ``order`` finds the cheapest visiting order from any (P, P) cost matrix on the device, and ``routine`` chains the
-two and gathers the legs in visiting order, ready for ``refine(seeds=...)``, without a host synchronisation.
+two and gathers the legs in visiting order, ready for ``refine(seeds=...)``, without a host synchronisation.  ``order_timed``
+orders the sites by the clock instead — the rows of the chained timeline, turns on the spot and dwells included, optionally
+the most valuable sites within a budget of seconds — and ``timed_routine`` runs the whole chain from the scene to that
+timeline.
 
 Units: feet, in the scene's frame.  At most 16384 cells (the distance field of a problem lives in one workgroup's LDS).
 """
+import ctypes as C
+import math
+
 import numpy as np
 import torch
 
 from . import _lib
 from ._call import buffers, context_for, device_array, dptr, ptr, time_rows
 from .footprint import Scene, _ccw_polygon, convex_polygon
+from .synth import DEFAULT_CONSTRAINTS
 
 MAX_CELLS = 16384
 MAX_WAYPOINTS = 2048
@@ -375,5 +382,212 @@ def routine(points, scene, waypoints, radius, cell=0.25, margin=0.0, occupancy=N
            "travel_flags": tr["flags"], "n_vertices": tr["n_vertices"], "waypoints": wp, "legs": legs}
     if single:
         res = {k: v[0] for k, v in res.items()}
+    out.update(res)
+    return res
+
+
+MAX_TIMED_SITES = _lib.PLAN_ORDER_TIMED_MAX_SITES
+_INT_MAX = 2147483647
+
+
+def order_timed(rows, counts, leg, dwell=None, start_heading=None, value=None, budget=None, end=None, before=None,
+                leg_flags=None, constraints=DEFAULT_CONSTRAINTS, dt=0.01, turn_min=math.radians(1.0), out=None, ctx=None):
+    """The visiting order that takes the fewest ROWS of the chained timeline, by Held-Karp over (site set, last site, site
+    before it) on the device (vap_plan_order_timed): per slot the rows of the turn on the spot (they depend on the heading
+    the robot arrives with, so on the leg before, which no (P, P) cost matrix can carry), the leg's own rows and
+    int(dwell / dt).  ``rows_total`` IS ``timeline.chain(...)["counts"][:, 0]`` for the returned order, and
+    ``arrival_rows`` its ``map[:, :, 2]``.
+
+      rows, counts   the L legs as ``time_profile`` returns them: (L, capacity, 8) fp64 device tensor or host array, with
+                     (L, k) / (L,) counts (column 0 = rows), all on the time step ``dt``.  Any legs' rows will do: profile
+                     ``search.refine``'s ``best_waypoints`` of all pairs first and the order is that of the refined legs
+      leg            (R, P, P) or (P, P) int: the leg from point a to point b (point 0 = the start, 1..M = P - 1 <= 8 the
+                     sites); column 0 and the diagonal are not read.  A leg outside [0, L), with a non-zero ``leg_flags``
+                     entry, without rows, or whose first or last row the timeline would refuse, is forbidden
+      dwell          (R, P) seconds spent at SITE j (entry 0 unused), device or host; None = none
+      start_heading  (R,) the heading the robot stands at before the first leg, NaN = none; None = none
+      value          (R, P) worth of site j in budget mode (NaN, negative, infinite: 0); None = 1 each
+      budget         None: visit every site in the fewest rows.  Seconds (a scalar, an (R,) host array or device tensor):
+                     the most valuable set of sites whose routine takes at most int(budget / dt) rows, then the fewest
+                     rows, then the lowest set; turned into rows on the device, nothing is read back
+      end, before    as ``order`` takes them
+      leg_flags      (L,) int, e.g. the ``flags`` of the legs' profile; a non-zero entry forbids the leg
+      constraints, dt, turn_min   as ``timeline.chain`` takes them
+      out            optional dict of tensors of the shapes below to reuse
+    Returns a dict of device tensors: order (R, M) int32 (the visited sites, then -1), n_visited (R,) int32, rows_total
+    (R,) int32 (-1 where infeasible), arrival_rows (R, M) int32 (-1 behind the visited slots), value_total (R,) fp64, flags
+    (R,) int32 (``FLAGS["order_infeasible"]``), feasible (R,) bool, and in seconds duration (R,) = rows_total * dt and
+    arrival (R, M) = arrival_rows * dt (NaN where the rows are -1).  A single (P, P) ``leg`` gives results without the
+    leading axis.  Work runs on torch's current stream and is not synchronised."""
+    dt, turn_min = float(dt), float(turn_min)
+    if not (dt > 0 and math.isfinite(dt)):
+        raise ValueError(f"dt must be positive and finite (got {dt!r})")
+    if not (turn_min >= 0 and math.isfinite(turn_min)):
+        raise ValueError(f"turn_min must be >= 0 and finite (got {turn_min!r})")
+    c = _lib.make_constraints(constraints)
+    rows, counts, one_leg, dev = time_rows(rows, counts, None, 0, "legs")
+    if one_leg:
+        raise ValueError("rows must be (L, capacity, 8): a batch of legs")
+    L, cap = int(rows.shape[0]), int(rows.shape[1])
+    shape = tuple(leg.shape) if hasattr(leg, "shape") else np.shape(leg)
+    single = len(shape) == 2
+    if len(shape) not in (2, 3) or shape[-1] != shape[-2]:
+        raise ValueError(f"leg must be (R, P, P) or (P, P), got {shape}")
+    P = int(shape[-1])
+    R = 1 if single else int(shape[0])
+    M = P - 1
+    if not 1 <= M <= MAX_TIMED_SITES:
+        raise ValueError(f"P = {P} points: 2..{MAX_TIMED_SITES + 1} (the start and at most {MAX_TIMED_SITES} sites)")
+    e = -1 if end is None else int(end)
+    if end is not None and (e != end or not 1 <= e <= M):
+        raise ValueError(f"end must be None or a site 1..{M} (got {end!r})")
+
+    def arg(a, dtype, shp, what):
+        if isinstance(a, torch.Tensor) and a.device.type == "cuda" and a.device != dev:
+            raise ValueError(f"{what} is on {a.device}, the rows on {dev}")
+        t = device_array(a, dev, dtype)
+        if t is not None and single and t.dim() == len(shp) - 1:
+            t = t.unsqueeze(0)
+        if t is not None and tuple(t.shape) != shp:
+            raise ValueError(f"{what} must be {shp}, got {tuple(t.shape)}")
+        return None if t is None else t.contiguous()
+
+    leg = arg(leg, torch.int32, (R, P, P), "leg")
+    dwell = arg(dwell, torch.float64, (R, P), "dwell")
+    value = arg(value, torch.float64, (R, P), "value")
+    if start_heading is not None and single:
+        start_heading = device_array(start_heading, dev, torch.float64).reshape(-1)
+    start_heading = arg(start_heading, torch.float64, (R,), "start_heading")
+    leg_flags = device_array(leg_flags, dev, torch.int32)
+    if leg_flags is not None and tuple(leg_flags.shape) != (L,):
+        raise ValueError(f"leg_flags must be ({L},), got {tuple(leg_flags.shape)}")
+    b = None
+    if before is not None:
+        if isinstance(before, (list, tuple)):                        # (earlier, later) pairs
+            before = before_masks(before, R, P)
+        b = device_array(before, dev, torch.int64)
+        if b.dim() == 1:
+            b = b.unsqueeze(0).expand(R, P)
+        if tuple(b.shape) != (R, P):
+            raise ValueError(f"before must be ({R}, {P}) or ({P},) masks or a list of (earlier, later) pairs, got {tuple(b.shape)}")
+        b = (b & (2 ** MAX_TIMED_SITES - 1)).to(torch.int32).contiguous()
+    budget_rows = None
+    if budget is not None:                                           # int(budget / dt), saturating; NaN and negatives: 0
+        q = device_array(budget, dev, torch.float64)
+        if q.numel() == 1:
+            q = q.reshape(()).expand(R)
+        if tuple(q.shape) != (R,):
+            raise ValueError(f"budget must be a scalar or ({R},) seconds, got {tuple(q.shape)}")
+        q = torch.nan_to_num(q / dt, nan=0.0, posinf=float(_INT_MAX), neginf=0.0)
+        budget_rows = q.clamp(0.0, float(_INT_MAX)).to(torch.int32).contiguous()
+    res = buffers(out, {"order": ((R, M), torch.int32), "n_visited": ((R,), torch.int32), "rows_total": ((R,), torch.int32),
+                        "arrival_rows": ((R, M), torch.int32), "value_total": ((R,), torch.float64),
+                        "flags": ((R,), torch.int32)}, dev)
+    ctx = context_for(dev, ctx)
+    _lib.check(ctx._L.vap_plan_order_timed(
+        ctx.handle, R, P, L, cap, dt, C.byref(c), turn_min, ptr(rows), ptr(counts), int(counts.shape[1]), ptr(leg),
+        ptr(leg_flags), ptr(dwell), ptr(start_heading), ptr(value), ptr(budget_rows), e, ptr(b), ptr(res["order"]),
+        ptr(res["n_visited"]), ptr(res["rows_total"]), ptr(res["arrival_rows"]), ptr(res["value_total"]), ptr(res["flags"])),
+        "vap_plan_order_timed")
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    res["feasible"] = res["flags"] == 0
+    res["duration"] = torch.where(res["rows_total"] >= 0, res["rows_total"].to(torch.float64) * dt, nan)
+    res["arrival"] = torch.where(res["arrival_rows"] >= 0, res["arrival_rows"].to(torch.float64) * dt, nan)
+    if single:
+        res = {k: v[0] for k, v in res.items()}
+    return res
+
+
+def timed_routine(gen, points, scene, waypoints, radius, cell=0.25, margin=0.0, occupancy=None, windows=None, dwell=None,
+                  start_heading=None, value=None, budget=None, end=None, before=None, constraints=DEFAULT_CONSTRAINTS, dt=0.01,
+                  turn_min=math.radians(1.0), dd=0.005, path_capacity=None, leg_capacity_rows=None, capacity_rows=None,
+                  out=None):
+    """A routine ordered by the clock and chained, in one call on ``gen``'s device and context: ``travel`` with waypoints,
+    ``gen.profile`` and ``gen.time_profile`` of the (P - 1)^2 pairs that can be legs (not the diagonal or column 0, whose
+    waypoints are degenerate), ``order_timed`` on their rows with the profile's and the travel's flags as ``leg_flags``,
+    the legs and the per-slot dwells gathered in visiting order, and ``timeline.chain(..., n_legs=n_visited)``.
+
+      points         (R, P, 2) or (P, 2): points[.., 0, :] is where the routine starts, the other P - 1 <= 8 are the sites
+      scene, waypoints, radius, cell, margin, occupancy, windows   as ``travel`` takes them (``waypoints`` = W per leg)
+      dwell, start_heading, value, budget, end, before, constraints, dt, turn_min   as ``order_timed`` takes them
+      dd, path_capacity     the legs' profile grid (``gen.profile(dd=, capacity=)``)
+      leg_capacity_rows     rows per leg of ``gen.time_profile`` (None: 4096); a leg that needs more is flagged and forbidden
+      capacity_rows         rows per routine of the chained timeline, as ``timeline.chain`` takes it; required when ``dwell``
+                            is a device tensor
+    A pair the travel could not plan (its length is not finite) is profiled along the straight segment instead, so that
+    every leg has rows, and is forbidden by its flag; a travel flag that only reports a snapped start or goal forbids
+    nothing, as in ``routine``.
+    Returns what ``order_timed`` returned, plus timeline (the dict of ``timeline.chain``), legs (R, M, W, 2) the seed routes
+    in visiting order (NaN behind the visited slots; ``legs.reshape(R * M, W, 2)`` is what ``refine(seeds=...)`` takes),
+    leg_index (R, M) int32 (-1 behind the visited slots), leg_matrix (R, P, P) int32, leg_rows / leg_counts / leg_flags of
+    all R (P - 1)^2 profiled pairs, and the travel outputs under travel, travel_flags and waypoints.  Nothing here reads a
+    result on the host."""
+    from . import timeline
+    out = {} if out is None else out
+    dev = gen.device
+    tr = travel(points, scene, radius, cell=cell, margin=margin, waypoints=waypoints, occupancy=occupancy, windows=windows,
+                out=out.setdefault("_travel", {}), device=dev.index, ctx=gen.ctx)
+    single = tr["travel"].dim() == 2
+    if single:
+        tr = {k: v[None] for k, v in tr.items()}
+    t, wp = tr["travel"], tr["waypoints"]
+    R, P = int(t.shape[0]), int(t.shape[1])
+    M, W = P - 1, int(wp.shape[3])
+    if M > MAX_TIMED_SITES:
+        raise ValueError(f"P = {P} points: 2..{MAX_TIMED_SITES + 1} (the start and at most {MAX_TIMED_SITES} sites)")
+    pairs = [(a, b) for a in range(P) for b in range(1, P) if a != b]            # the (P - 1)^2 pairs that can be legs
+    pa = torch.tensor([p[0] for p in pairs], device=dev)
+    pb = torch.tensor([p[1] for p in pairs], device=dev)
+    n_pairs = len(pairs)
+    mat = np.full((P, P), -1, dtype=np.int64)
+    for k, (a, b) in enumerate(pairs):
+        mat[a, b] = k
+    mat = torch.as_tensor(mat, device=dev)
+    base = torch.arange(R, device=dev)[:, None, None] * n_pairs
+    leg_matrix = torch.where(mat[None] >= 0, mat[None] + base, mat[None]).to(torch.int32)
+    pts = device_array(points, dev, torch.float64).reshape(R, P, 2)
+    host_dwell = None if dwell is None or isinstance(dwell, torch.Tensor) else np.asarray(dwell, dtype=np.float64).reshape(R, P)
+    dwell = None if dwell is None else device_array(dwell, dev, torch.float64).reshape(R, P)
+    value = None if value is None else device_array(value, dev, torch.float64).reshape(R, P)
+    start_heading = None if start_heading is None else device_array(start_heading, dev, torch.float64).reshape(R)
+    planned = torch.isfinite(t[:, pa, pb])                                       # (R, n_pairs)
+    along = torch.linspace(0.0, 1.0, W, dtype=torch.float64, device=dev)[None, None, :, None]
+    straight = pts[:, pa][:, :, None, :] * (1.0 - along) + pts[:, pb][:, :, None, :] * along
+    pair_wp = torch.where(planned[:, :, None, None], wp[:, pa, pb], straight)    # (R, n_pairs, W, 2)
+    prof = gen.profile(pair_wp.reshape(R * n_pairs, W, 2).to(gen.tdtype).contiguous(), constraints, dd=dd, capacity=path_capacity)
+    tp = gen.time_profile(prof, constraints, dt=dt, capacity_rows=leg_capacity_rows, out=out.setdefault("_time", {}))
+    failed = torch.where(planned, torch.zeros_like(tr["flags"][:, pa, pb]),
+                         tr["flags"][:, pa, pb] | FLAGS["unreachable"])
+    leg_flags = prof["flags"] | failed.reshape(R * n_pairs)
+    od = order_timed(tp["rows"], tp["counts"], leg_matrix, dwell=dwell, start_heading=start_heading, value=value, budget=budget,
+                     end=end, before=before, leg_flags=leg_flags, constraints=constraints, dt=dt, turn_min=turn_min,
+                     out=out.setdefault("_order", {}), ctx=gen.ctx)
+    o = od["order"].to(torch.int64)
+    used = o >= 1
+    to = o.clamp(min=0)
+    frm = torch.cat([torch.zeros_like(to[:, :1]), to[:, :-1]], dim=1)
+    rr = torch.arange(R, device=dev)[:, None]
+    leg_index = torch.where(used, leg_matrix[rr, frm, to], torch.full_like(leg_matrix[rr, frm, to], -1))
+    slot_dwell = None
+    if dwell is not None:
+        slot_dwell = torch.where(used, dwell[rr, to], torch.zeros_like(dwell[rr, to]))
+        if capacity_rows is None and host_dwell is not None:                      # the longest dwell sum any order can have
+            with np.errstate(invalid="ignore"):
+                host = host_dwell[:, 1:]
+                steps = np.where(host > 0, np.floor(np.where(host > 0, host, 0.0) / dt), 0.0)
+            cap_in = int(tp["rows"].shape[1])
+            capacity_rows = M * cap_in + M * timeline.turn_rows(math.pi, constraints, dt) + int(min(steps.sum(axis=1).max(), 2.0 ** 31))
+    tl = timeline.chain(tp["rows"], tp["counts"], leg_index, dwell=slot_dwell, start_heading=start_heading,
+                        n_legs=od["n_visited"], constraints=constraints, dt=dt, turn_min=turn_min, capacity_rows=capacity_rows,
+                        out=out.setdefault("_timeline", {}), device=dev.index, ctx=gen.ctx)
+    legs = wp[rr, frm, to]
+    legs = torch.where(used[:, :, None, None], legs, torch.full_like(legs, float("nan")))
+    res = dict(od)
+    res.update({"timeline": tl, "legs": legs, "leg_index": leg_index, "leg_matrix": leg_matrix, "leg_rows": tp["rows"],
+                "leg_counts": tp["counts"], "leg_flags": leg_flags, "travel": t, "travel_flags": tr["flags"], "waypoints": wp})
+    if single:
+        res = {k: (v[0] if k in ("order", "n_visited", "rows_total", "arrival_rows", "value_total", "flags", "feasible",
+                                 "duration", "arrival", "legs", "leg_index", "leg_matrix", "travel", "travel_flags", "waypoints")
+                   else v) for k, v in res.items()}
     out.update(res)
     return res
