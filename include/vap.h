@@ -238,7 +238,9 @@ int vap_velocity_pass(vap_ctx *ctx, vap_dtype dt, int B, int S, const vap_constr
  *                                    effect (node 0: 0; INT_MAX: never)
  * d_lut NULL = the table of the last vap_profile_batch / vap_profile_routes (same B, W; after vap_profile_routes
  * d_lut must be NULL).  Reverse / turn nodes are not covered here
- * (vap_route_* is the general single-route path); waits act in the time domain (vap_time_insert_waits). */
+ * (vap_route_* is the general single-route path); waits act in the time domain (vap_time_insert_waits).
+ * The output rows need no alignment beyond that of their element type: a row address that is not 16-byte aligned is
+ * written element by element. */
 /* Type of the limit rows (d_vcap, d_acc_forward, d_acc_backward, d_dec_backward) for rows of type dt in this context:
  * the type of the recurrence they enter — VAP_F64 for fp64 rows and for fp32 rows in the default mode
  * (VAP_RECURRENCE_F64: the fp64 recurrence amplifies an fp32-rounded limit such as 13.9 ft/s^2 past 1e-5, MPG:194-196,
@@ -298,7 +300,16 @@ int vap_time_profile(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, const doub
  * vap_time_insert_events): rows [0, capacity_out) are exactly those of a call with enough capacity, d_counts_out[b][0] =
  * capacity_out, and nothing is written at or behind row capacity_out.  d_nodes_map_out, d_actions_map_out and their
  * counts are NOT cut: they hold what a call with enough capacity gives, so an entry of a truncated route may name a
- * row >= capacity_out that does not exist; compare entries with d_counts_out[b][0] before indexing rows with them. */
+ * row >= capacity_out that does not exist; compare entries with d_counts_out[b][0] before indexing rows with them.
+ * Limits (here and in vap_time_insert_events):
+ *   d_rows_in and d_rows_out must be 16-byte aligned — the rows move 16 bytes at a time; any other pointer is refused
+ *   with VAP_ERR_INVALID before anything is launched.
+ *   The kernel keeps its event list and the node arrays in LDS: 44 W + 12 M + 16 bytes of dynamic LDS and one static
+ *   word, 44 W + 12 M + 20 bytes in all.  Up to 64 KB that runs on every device (W = 1488 with M = 1); above, the sum
+ *   has to fit what the device gives one workgroup (hipDeviceAttributeMaxSharedMemoryPerBlock: 160 KB on an MI355X, which
+ *   covers W = 2048 with up to M = 6142 action points and every route vap_profile_routes accepts) and is put to the
+ *   runtime first.  A request that does not fit or is not granted returns VAP_ERR_UNSUPPORTED — the message names W, M,
+ *   the bytes needed and the bytes available — before anything is launched or written. */
 int vap_time_insert_waits(vap_ctx *ctx, int B, int W, int M, int capacity_in, int capacity_out, double time_step,
                           const double *d_segments, const double *d_lut, const double *d_meta,
                           const double *d_rows_in, const int *d_counts_in, const int *d_nodes_map_in,
@@ -351,7 +362,9 @@ int vap_profile_batch(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, double dd
  * A route with a reverse / turn attribute on its LAST node (IndexError in the reference, SM:97) or with more
  * splines than max_splines is flagged VAP_FLAG_BAD_ROUTE; its rows are undefined.  Afterwards the context holds the
  * batch's tables: vap_route_limits + vap_velocity_pass_limits apply node / action-point limits as for plain paths.
- * The time domain of such a batch: vap_time_profile_routes, vap_time_insert_events. */
+ * The time domain of such a batch: vap_time_profile_routes, vap_time_insert_events.
+ * The per-sample output rows of a batch with max_splines > 1 need no alignment beyond that of their element type (a row
+ * address that is not 16-byte aligned is written element by element). */
 #define VAP_FLAG_BAD_ROUTE 8u
 int vap_profile_routes(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, double dd, int max_splines,
                        const void *d_waypoints, const int *d_node_reverse, const double *d_node_turn,

@@ -303,6 +303,26 @@ int check_insert_args(int B, int W, int M, int capacity_in, int capacity_out, do
         return vap_fail(VAP_ERR_INVALID, "null buffer");
     if (M > 0 && (!d_action_t || !d_actions_map_out)) return vap_fail(VAP_ERR_INVALID, "null action-point array");
     if (d_rows_out == d_rows_in) return vap_fail(VAP_ERR_INVALID, "the rows move: d_rows_out must not be d_rows_in");
+    if ((((uintptr_t)d_rows_in) | ((uintptr_t)d_rows_out)) & 15) return vap_fail(VAP_ERR_INVALID, "the rows move 16 bytes at a time: misaligned row pointer");
+    return VAP_OK;
+}
+
+// The LDS of k_time_waits grows with W and M.  Up to 64 KB every device launches it as it is; above, the request has to
+// fit the device's workgroup limit and is put to the runtime first.  Refused here, before anything is launched.
+int grant_waits_lds(vap_ctx *ctx, int W, int M)
+{
+    const size_t lds = vap::time_waits_lds_bytes(W, M), need = lds + vap::kTimeWaitsStaticLds;
+    if (need <= 64 * 1024) return VAP_OK;
+    int lds_max = 0;
+    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess) lds_max = 0;
+    const size_t avail = lds_max > 64 * 1024 ? (size_t)lds_max : (size_t)64 * 1024;
+    if (need > avail)
+        return vap_fail(VAP_ERR_UNSUPPORTED, "waits of W=%d nodes and M=%d action points need %zu bytes of LDS; the device gives a "
+                        "workgroup %zu", W, M, need, avail);
+    const hipError_t e = vap::time_waits_grant_lds(lds);
+    if (e != hipSuccess)
+        return vap_fail(VAP_ERR_UNSUPPORTED, "waits of W=%d nodes and M=%d action points need %zu bytes of LDS; the device gives a "
+                        "workgroup %zu and the request was not granted (%s)", W, M, need, avail, hipGetErrorString(e));
     return VAP_OK;
 }
 
@@ -683,6 +703,7 @@ int vap_time_insert_waits(vap_ctx *ctx, int B, int W, int M, int capacity_in, in
     VAP_TRY(check_insert_args(B, W, M, capacity_in, capacity_out, time_step, true, d_meta, d_rows_in, d_counts_in, d_nodes_map_in,
                               d_action_t, d_rows_out, d_counts_out, d_nodes_map_out, d_actions_map_out));
     VAP_TRY(plain_tables(ctx, B, W, d_segments, d_lut));
+    VAP_TRY(grant_waits_lds(ctx, W, M));
     HIP_TRY(vap::launch_time_waits(ctx->stream, B, W, M, capacity_in, capacity_out, time_step, d_segments, d_lut, d_meta,
                                    d_rows_in, d_counts_in, d_nodes_map_in, d_node_wait, d_action_t, d_action_wait, d_rows_out,
                                    d_counts_out, d_nodes_map_out, d_actions_map_out, d_flags));
@@ -718,6 +739,7 @@ int vap_time_insert_events(vap_ctx *ctx, int B, int W, int M, int capacity_in, i
         return vap_fail(VAP_ERR_INVALID, "in-place turns need max_vel, max_acc and track_width");
     VapTables t;
     VAP_TRY(vap_ctx_tables(ctx, B, W, false, t));
+    VAP_TRY(grant_waits_lds(ctx, W, M));
     HIP_TRY(vap::launch_time_waits(ctx->stream, B, W, M, capacity_in, capacity_out, time_step, t.seg, t.lut, d_meta, d_rows_in,
                                    d_counts_in, d_nodes_map_in, d_node_wait, d_action_t, d_action_wait, d_rows_out, d_counts_out,
                                    d_nodes_map_out, d_actions_map_out, d_flags, t.rt, d_node_turn, d_node_reverse, c->max_vel,

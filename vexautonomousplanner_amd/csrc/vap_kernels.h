@@ -130,6 +130,11 @@ hipError_t launch_route_limits(hipStream_t st, bool f64, int B, int W, int M, in
                                int *ev_k, double *ev_mv, double *ev_ma, int *ev_stop, void *vcap, void *acc_fwd,
                                void *acc_bwd, void *dec_bwd, RouteTables rt = RouteTables());
 // waits of nodes / action points and actions_map on top of the rows of launch_time_profile (vap_time.hip)
+// k_time_waits keeps its event list and the node arrays in dynamic LDS, time_waits_lds_bytes(W, M) of it, beside one static
+// word; a request above 64 KB is put to the runtime by time_waits_grant_lds before the launch (vap_api.hip: grant_waits_lds)
+constexpr size_t kTimeWaitsStaticLds = sizeof(int);
+size_t time_waits_lds_bytes(int W, int M);
+hipError_t time_waits_grant_lds(size_t lds);
 hipError_t launch_time_waits(hipStream_t st, int B, int W, int M, int cap_in, int cap_out, double dt, const double *segments,
                              const double *lut, const double *meta, const double *rows_in, const int *counts_in,
                              const int *nodes_in, const double *node_wait, const double *ap_t, const double *ap_wait,

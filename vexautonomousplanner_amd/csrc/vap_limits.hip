@@ -210,7 +210,7 @@ __global__ void k_limit_fill(int B, int W, int S, int E, const double *__restric
         }
         const size_t o = (size_t)b * S + k0;
         auto put = [&](R *__restrict__ row, const R (&x)[4]) {
-            if (k0 + 3 < S && (o & 3) == 0) {
+            if (k0 + 3 < S && ((uintptr_t)(row + o) & 15) == 0) {      // the address, not the offset: the caller's base may sit anywhere
                 if constexpr (sizeof(R) == 8) {
                     *reinterpret_cast<double2 *>(row + o) = make_double2(x[0], x[1]);
                     *reinterpret_cast<double2 *>(row + o + 2) = make_double2(x[2], x[3]);

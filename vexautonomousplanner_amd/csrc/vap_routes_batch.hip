@@ -414,10 +414,10 @@ __global__ __launch_bounds__(kRouteThreads) void k_sample_routes(int W, int NS, 
     }
     if (kb < S) {
         const size_t o = row + kb;
-        const bool whole = kb + kRouteSPT <= S && (o & 3) == 0;
+        const bool whole = kb + kRouteSPT <= S;
         auto put = [&](auto *__restrict__ dst, const auto (&x)[kRouteSPT]) {
             using T = std::remove_reference_t<decltype(x[0])>;
-            if (whole) {
+            if (whole && ((uintptr_t)(dst + o) & 15) == 0) {       // the address, not the offset: the caller's base may sit anywhere
                 if constexpr (sizeof(T) == 4) {
                     *reinterpret_cast<float4 *>(dst + o) = make_float4(x[0], x[1], x[2], x[3]);
                 } else {

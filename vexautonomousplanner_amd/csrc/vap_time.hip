@@ -935,14 +935,24 @@ __global__ __launch_bounds__(256) void k_time_waits(int W, int M, int cap_in, in
     }
 }
 
+// events [E][3] ints (E = 2 W + M), then the node arrays: W ints (+ one of padding) and 2 W doubles: 44 W + 12 M + 16 bytes
+size_t time_waits_lds_bytes(int W, int M)
+{
+    return sizeof(int) * (3 * (2 * (size_t)W + (size_t)M) + W + 2) + sizeof(double) * 2 * (size_t)W + 8;
+}
+
+hipError_t time_waits_grant_lds(size_t lds)
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(k_time_waits), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
 hipError_t launch_time_waits(hipStream_t st, int B, int W, int M, int cap_in, int cap_out, double dt, const double *segments,
                              const double *lut, const double *meta, const double *rows_in, const int *counts_in,
                              const int *nodes_in, const double *node_wait, const double *ap_t, const double *ap_wait,
                              double *rows_out, int *counts_out, int *nodes_out, int *actions_out, uint32_t *flags, RouteTables rt,
                              const double *node_turn, const int *node_reverse, double max_vel, double max_acc, double track_width)
 {
-    // events [E][3] ints, then the node arrays: W ints (+ one of padding) and 2 W doubles
-    const size_t lds = sizeof(int) * (3 * (size_t)(2 * W + M) + W + 2) + sizeof(double) * 2 * (size_t)W + 8;
+    const size_t lds = time_waits_lds_bytes(W, M);
     TimeEventInputs ev;
     ev.node_wait = node_wait;
     ev.node_turn = node_turn;
