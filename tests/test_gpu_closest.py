@@ -127,8 +127,7 @@ def test_exact_mode_on_the_fixture_paths(torch_mod, name):
 
 
 def _random_path_ref(m, W):
-    r = m._route
-    return cr.RefPath.from_arrays(r.segments, r.sp_param_last, r.sp_npts, W)
+    return cr.path_of_route(m._route, W)
 
 
 @pytest.mark.parametrize("W", [8, 32])

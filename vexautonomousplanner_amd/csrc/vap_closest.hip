@@ -131,8 +131,9 @@ __device__ __forceinline__ double poly9_d(const double g[10], double u)
     return v;
 }
 // Sign variations of the Bernstein coefficients of g restricted to [a, a+h] (zeros skipped).  By Descartes' rule in the
-// Bernstein basis the count bounds the roots in the interval and has their parity; 0 or 1 decides it.
-__device__ int bernstein_variations(const double g[10], double a, double h)
+// Bernstein basis the count bounds the roots in the interval and has their parity; 0 or 1 decides it.  `first` gets
+// the sign of the first coefficient that is not zero: the sign of g just inside the interval's left end.
+__device__ int bernstein_variations(const double g[10], double a, double h, int &first)
 {
     double c[10];
 #pragma unroll
@@ -148,6 +149,7 @@ __device__ int bernstein_variations(const double g[10], double a, double h)
     constexpr double binom9[10] = {1, 9, 36, 84, 126, 126, 84, 36, 9, 1};
     int var = 0;
     int last = 0;
+    first = 0;
 #pragma unroll
     for (int i = 0; i < 10; i++) {
         double b = 0.0, cik = 1.0;   // C(i, k)
@@ -159,15 +161,21 @@ __device__ int bernstein_variations(const double g[10], double a, double h)
         const int s = b > 0.0 ? 1 : (b < 0.0 ? -1 : 0);
         if (s != 0) {
             if (last != 0 && s != last) var++;
+            if (last == 0) first = s;
             last = s;
         }
     }
     return var;
 }
-// The one root of g in [lo, hi]: Newton inside a bracket that bisection keeps shrinking.
-__device__ double bracketed_root(const double g[10], double lo, double hi)
+// The one root of g in [lo, hi]: Newton inside a bracket that bisection keeps shrinking.  Where g(lo) is exactly zero (a
+// segment that starts at a cusp: P'(lo) = 0, and lo is a node the node pass has taken) the bracket's left sign is the
+// one just inside: `first`, from the Bernstein coefficients of this same interval.  With the zero itself the bracket
+// closed on lo and lost the root.  On a deeper interval the Taylor-shifted first coefficient and poly9(g, lo) round
+// differently, so `first` may come from a tiny first coefficient that is not zero; it is still the sign just inside.
+__device__ double bracketed_root(const double g[10], double lo, double hi, int first)
 {
     double glo = poly9(g, lo);
+    if (glo == 0.0) glo = (double)first;
     double x = 0.5 * (lo + hi);
 #pragma unroll 1
     for (int it = 0; it < 80; it++) {
@@ -227,14 +235,15 @@ __device__ void exact_segment(const ClosestPath &p, int s, double qx, double qy,
     for (int n = 0; n < kExactMaxIntervals; n++) {
         const double h = ldexp(1.0, -depth);
         const double a = (double)idx * h;
-        const int var = bernstein_variations(g, a, h);
+        int first;
+        const int var = bernstein_variations(g, a, h, first);
         if (var >= 2 && depth < kExactMaxDepth) {
             consider(p, qx, qy, base + (a + 0.5 * h), b);   // a root exactly at the split point is caught here
             idx <<= 1;
             depth++;
             continue;
         }
-        if (var >= 1) consider(p, qx, qy, base + bracketed_root(g, a, a + h), b);
+        if (var >= 1) consider(p, qx, qy, base + bracketed_root(g, a, a + h, first), b);
         while (depth > 0 && (idx & 1)) { idx >>= 1; depth--; }
         if (depth == 0) break;
         idx += 1;
@@ -397,11 +406,9 @@ hipError_t launch_closest(hipStream_t st, ClosestSrc src, int B, int Q, int mode
     bool seg_lds = false;
     const size_t lds = closest_lds_bytes(src, seg_lds);
     src.seg_lds = seg_lds ? 1 : 0;
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_closest),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    // lds never exceeds the 64 KB any launch may have, so no larger limit is asked for: staged rows mean W <= 342 and at
+    // most 341 splines (32 736 + 341 * 32 = 43 648 B); unstaged rows leave the spline table alone, at most
+    // kMaxRouteWaypoints - 1 = 1499 rows of 32 B (47 968 B).  tests/test_closest_cpu.py pins the arithmetic.
     const dim3 grid(B, (Q + kClosestQueriesPerBlock - 1) / kClosestQueriesPerBlock);
     hipLaunchKernelGGL(k_closest, grid, dim3(kClosestThreads), lds, st, src, Q, mode, shared_queries, queries, t, pt, d, s, ct, flags);
     return hipGetLastError();
