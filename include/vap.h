@@ -32,6 +32,7 @@
  *            (VAP_VELOCITY_SEQ_LITERAL) gives the same 1.9e-6 and the fp64 CPU restatement itself is 7.9e-8 from the
  *            reference: the reference's own recurrence amplifies last-bit differences of its inputs by up to 1e9
  *            there.  The bound that holds for both dtypes on every path tried is north_star's 1e-5.
+ *            vap_velocity_conditioning measures that amplification per path and names the paths in that regime.
  */
 #ifndef VAP_H
 #define VAP_H
@@ -105,7 +106,8 @@ int vap_ctx_synchronize(vap_ctx *ctx);
  * direction; RELAX_ROUNDS forces the earlier form of that kernel (one launch per super-round, convergence checked
  * on the host) — the same rows bit for bit (tests). */
 enum { VAP_OPT_VELOCITY_KERNEL = 0, VAP_OPT_F32_RECURRENCE = 1, /* 2: retired (sampling inside the velocity kernel, rounds 3-4) */
-       VAP_OPT_TIME_DOMAIN_RESIDUAL = 3, VAP_OPT_TIME_KERNEL = 4, VAP_OPT_FOOTPRINT_CULL = 5 };
+       VAP_OPT_TIME_DOMAIN_RESIDUAL = 3, VAP_OPT_TIME_KERNEL = 4, VAP_OPT_FOOTPRINT_CULL = 5,
+       VAP_OPT_CONDITIONING_SCRATCH_MB = 6 };
 enum { VAP_VELOCITY_AUTO = 0, VAP_VELOCITY_SEQ_LITERAL = 1, VAP_VELOCITY_SEQ_FAST = 2, VAP_VELOCITY_RELAX = 3,
        VAP_VELOCITY_RELAX_BLOCK = 4 /* workgroup per path */, VAP_VELOCITY_RELAX_WAVE = 5 /* wave per path, fp32 */,
        VAP_VELOCITY_LANES = 6 /* lane per path, fp64 recurrence */, VAP_VELOCITY_LANES_16 = 7, VAP_VELOCITY_LANES_32 = 8,
@@ -136,6 +138,9 @@ enum { VAP_TIME_KERNEL_AUTO = 0, VAP_TIME_KERNEL_LANE = 1, VAP_TIME_KERNEL_QUAD 
  * bounding-circle lower bound exceeds the row's running minimum (plus a small slack).  A skipped element could not have
  * become the row's minimum, so every output is the same bit for bit either way; 0 tests every element (tests).
  * vap_footprint_conflicts: the same switch for its block and row bounds (0 tests every row of every pair exactly). */
+/* VAP_OPT_CONDITIONING_SCRATCH_MB (1 .. 16384, default 512): the context scratch vap_velocity_conditioning may hold at a
+ * time, in MiB.  The call cuts its batch into launches whose probe rows fit (one path's rows at the least); its outputs do
+ * not depend on the cut. */
 int vap_ctx_set_option(vap_ctx *ctx, int option, int value);
 /* Enable/disable per-stage hipEvent timing (replaces the reference's time.time() log lines,
  * SM:587-594, MPG:398-411).  Off by default. */
@@ -263,6 +268,49 @@ int vap_velocity_pass_limits(vap_ctx *ctx, vap_dtype dt, int B, int S, const vap
                              const void *d_curvature, const void *d_dtheta, const void *d_vcap,
                              const void *d_acc_forward, const void *d_acc_backward,
                              const void *d_dec_backward, void *d_velocity, uint32_t *d_flags);
+
+/* How far a path's velocity recurrence amplifies a relative change of its inputs: MPG:188-311 is swept on the rows as they
+ * are and on K copies whose curvature and heading differences are changed by a relative +-delta, and the largest relative
+ * change of a squared velocity, divided by 2 delta, is the path's conditioning number.  cond x (relative noise of the rows)
+ * predicts how far two correct implementations of the recurrence — this library and the reference, say — may differ on the
+ * path: ~1 to ~300 on ordinary paths, 1e6 to 1e8 on fixture big_w2048_p2.  Where cond is large the
+ * reference's own profile oscillates from sample to sample.
+ *   rows      curvature, |dtheta|, d_vcap, the three acceleration rows and d_meta are those of vap_velocity_pass_limits,
+ *             resolved by the same code: d_dtheta NULL = the rows the last sampling call left on the context, and so on.
+ *             N = meta[b][3] (taken as 0 below 0 and as S above S), dd = meta[b][2].  fp32 rows are widened: all
+ *             arithmetic is fp64 whatever `dt` is.
+ *   probes    k = 0 is the rows as they are.  For k = 1 .. K: curvature'[j] = curvature[j] * (1 + s delta) and
+ *             dtheta'[j] = dtheta[j] * (1 + s' delta), one rounded product each (1 + s delta is exact), with (s, s') from one
+ *             Philox4x32-10 block x (vap_search_sample's generator) of counter (j, k, 0x434f4e44, first_path + b) and key
+ *             (seed & 0xffffffff, seed >> 32): s = +1 if x[0] & 1 else -1, s' likewise from x[1].  d_vcap and the
+ *             acceleration rows are not perturbed.
+ *   sweeps    each probe is MPG:188-311 in u = v^2, statement by statement — the sweep of VAP_VELOCITY_SEQ_LITERAL, compiled
+ *             from the same text — and gives U_k[j], the squared velocity of sample j after the backward sweep
+ *             (U_k[N - 1] = end_vel^2).
+ *   deviation r_k[j] = |U_k[j] - U_0[j]| / U_0[j] where U_0[j] > 0; where U_0[j] == 0: 0 if U_k[j] == 0, else +inf; NaN for
+ *             any other U_0[j].  sens[j] = (max over k of r_k[j]) / (2 delta) for j < N and 0 for j >= N; cond[b] = max over
+ *             j of sens[j].  Every maximum starts from 0.0 and is taken under a strict >, so a NaN never wins.  Among equal
+ *             values the smallest j, then the smallest k, gives worst_sample / worst_probe; both are -1 when cond is 0.
+ *             N < 2 gives cond 0.
+ *   flag      d_flags[b] |= VAP_FLAG_ILLCONDITIONED iff cond[b] > cond_limit (+inf: never).  d_flags [B] is this call's own
+ *             array (optional, OR-ed into): no call of the pipeline writes the bit, and a caller who wants it among a
+ *             profile result's flags — where vap_search_update would read it as an infeasible candidate — puts it there.
+ *   outputs   d_cond [B] fp64; d_worst_sample, d_worst_probe [B] int32, optional; d_sensitivity [B][S] fp64, optional;
+ *             d_velocity [B][S] fp64, optional: the velocity of U_0[j] (the row vap_velocity_pass gives under
+ *             VAP_VELOCITY_SEQ_LITERAL on fp64 rows, bit for bit), 0 for j >= N.
+ * VAP_ERR_INVALID: K not in {1, 3, 7, 15}; delta not a power of two in [2^-48, 2^-20]; cond_limit NaN or <= 0; B < 0; with
+ * B > 0 the argument errors of vap_velocity_pass_limits and a null d_cond.  These are checked before the context is touched;
+ * B = 0 is a no-op.  The probes' forward rows, B (K + 1) S 8 bytes, live in context scratch: the batch is cut into
+ * launches that stay under VAP_OPT_CONDITIONING_SCRATCH_MB.  Works on the context's stream and does not synchronise; no
+ * atomics: two calls give the same bits, and path b's outputs depend on (seed, first_path + b, its rows) only — not on B
+ * or on the cut. */
+#define VAP_FLAG_ILLCONDITIONED 1024u
+int vap_velocity_conditioning(vap_ctx *ctx, vap_dtype dt, int B, int S, const vap_constraints *c, double start_vel,
+                              double end_vel, const double *d_meta, const void *d_curvature, const void *d_dtheta,
+                              const void *d_vcap, const void *d_acc_forward, const void *d_acc_backward,
+                              const void *d_dec_backward, int K, double delta, uint64_t seed, uint32_t first_path,
+                              double cond_limit, double *d_cond, int *d_worst_sample, int *d_worst_probe, uint32_t *d_flags,
+                              double *d_sensitivity, double *d_velocity);
 
 /* MPG:413-628, the time-domain resample that generate_motion_profile runs after
  * forward_backward_pass, for B plain-node paths (no turn / wait / reverse nodes and no action points:

@@ -25,6 +25,7 @@ FLAG_NOCONVERGE = 4
 FLAG_BAD_ROUTE = 8
 PLAN_SNAPPED_START, PLAN_SNAPPED_GOAL, PLAN_NO_FREE, PLAN_UNREACHABLE, PLAN_VERTICES_TRUNCATED = 16, 32, 64, 128, 256
 ORDER_INFEASIBLE = 512
+FLAG_ILLCONDITIONED = 1024
 PLAN_TRAVEL_MAX_POINTS, PLAN_ORDER_MAX_SITES = 16, 10
 PLAN_ORDER_TIMED_MAX_SITES = 8
 TIMELINE_MAX_LEGS = 32
@@ -34,6 +35,7 @@ OPT_TIME_DOMAIN_RESIDUAL = 3
 OPT_F32_RECURRENCE = 1
 OPT_TIME_KERNEL = 4
 OPT_FOOTPRINT_CULL = 5
+OPT_CONDITIONING_SCRATCH_MB = 6
 TIME_KERNEL_AUTO, TIME_KERNEL_LANE, TIME_KERNEL_QUAD, TIME_KERNEL_FUSED = 0, 1, 2, 3
 RECURRENCE_F64, RECURRENCE_F32 = 0, 1
 VELOCITY_AUTO, VELOCITY_SEQ_LITERAL, VELOCITY_SEQ_FAST, VELOCITY_RELAX = 0, 1, 2, 3
@@ -70,7 +72,7 @@ EXPORTS = (
     "vap_closest_points", "vap_route_closest", "vap_footprint_clearance", "vap_footprint_conflicts",
     "vap_tracking_rollouts", "vap_search_sample", "vap_search_update", "vap_plan_grid", "vap_plan_seeds",
     "vap_plan_occupancy", "vap_plan_seeds_occupied", "vap_plan_travel", "vap_plan_order",
-    "vap_routine_timeline", "vap_plan_order_timed",
+    "vap_routine_timeline", "vap_plan_order_timed", "vap_velocity_conditioning",
 )
 
 
@@ -208,6 +210,8 @@ def lib():
                                        C.c_double, vp, vp, C.c_int] + [vp] * 9
     L.vap_plan_order_timed.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(Constraints), C.c_double,
                                        vp, vp, C.c_int] + [vp] * 6 + [C.c_int] + [vp] * 7
+    L.vap_velocity_conditioning.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(Constraints), C.c_double, C.c_double] + [vp] * 7 + \
+        [C.c_int, C.c_double, C.c_uint64, C.c_uint32, C.c_double] + [vp] * 6
     _lib = L
     return L
 

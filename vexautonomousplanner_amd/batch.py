@@ -342,6 +342,39 @@ class BatchedTrajectoryGenerator:
         result["action_sample"] = ap_k[:, :M]
         return result
 
+    def conditioning(self, result, constraints=DEFAULT_CONSTRAINTS, start_vel=START_VEL, end_vel=END_VEL, limits=None, probes=3,
+                     delta=2.0 ** -40, seed=0, *, limit, per_sample=False):
+        """How far the velocity recurrence of every path of ``result`` — what ``profile`` / ``profile_routes`` has just
+        returned with this generator — amplifies rounding (vap_velocity_conditioning on the rows that call left; see
+        conditioning.probe for probes, delta and seed).  ``constraints``, ``start_vel`` and ``end_vel`` are those of the
+        profile call; ``limits``: the rows a limited velocity pass ran on, a dict with "vcap" and optionally "acc_forward",
+        "acc_backward", "dec_backward" (``apply_node_limits`` leaves "vcap" in its result).
+        Returns a dict of device tensors: cond, worst_sample, worst_probe, flags (B,) — FLAG_ILLCONDITIONED where cond >
+        ``limit``, which has no default: the calibration of conditioning.ETA gave none that clears every ordinary path
+        (ordinary paths measure up to ~3e3, fixture big_w2048_p2 1e8, conditioning.limit_for(tol) turns
+        a tolerance into a limit, inf flags nothing) — and predicted_error = cond * conditioning.ETA (+ 2^-24 for fp32 rows):
+        an upper bound of the relative velocity difference to expect against the reference; ``per_sample``: also sensitivity
+        (B, S).  ``result["flags"]`` is never touched: a caller
+        who wants the bit there — the route search reads any flag as an infeasible candidate — ORs it in."""
+        from . import conditioning as cd
+        vel, meta = result["velocity"], result["meta"]
+        B, S = vel.shape
+        last = getattr(self, "_last_shape", None)
+        if last is None or (last[0], last[2]) != (B, S):
+            raise ValueError("conditioning needs the result of this generator's last profile() call")
+        self._check_current(result, "conditioning")
+        curv = result.get("curvature")
+        ctx_rows = self.vdtype == _lib.VAP_F32 and self.recurrence == "f64"   # the context holds the fp64 rows itself
+        if curv is None and not ctx_rows:
+            raise ValueError("conditioning needs the curvature rows (profile(want=...) must include 'curvature')")
+        lim = dict(limits) if limits is not None else {}
+        res = cd.probe(meta, None if ctx_rows else curv, None, constraints=constraints, start_vel=start_vel, end_vel=end_vel,
+                       samples=S, dtype=self.tdtype, vcap=lim.get("vcap"), acc_forward=lim.get("acc_forward"),
+                       acc_backward=lim.get("acc_backward"), dec_backward=lim.get("dec_backward"), probes=probes, delta=delta,
+                       seed=seed, limit=float(limit), per_sample=per_sample, ctx=self.ctx)
+        res["predicted_error"] = res["cond"] * cd.ETA + (cd.F32_ROW_NOISE if self.tdtype == torch.float32 else 0.0)
+        return res
+
     def insert_waits(self, result, tp, node_wait_time=None, action_points=None, dt=0.01, capacity_rows=None,
                      node_turn=None, node_reverse=None, constraints=DEFAULT_CONSTRAINTS):
         """Waits of nodes / action points and ``actions_map`` on top of ``tp = time_profile(result, ...)``

@@ -189,6 +189,47 @@ void velocity_consts(const vap_constraints *c, double cc[6])
     cc[0] = c->max_vel, cc[1] = cc[2] = c->max_acc, cc[3] = c->friction_coef, cc[4] = c->max_jerk, cc[5] = c->track_width;
 }
 
+// What vap_velocity_pass_limits and vap_velocity_conditioning ask of the arguments they share, before any context is
+// looked at (d_out: the output the call cannot do without) ...
+int check_velocity_args(int B, int S, const vap_constraints *c, const double *d_meta, const void *d_vcap, const void *d_acc_forward,
+                        const void *d_acc_backward, const void *d_dec_backward, const void *d_out)
+{
+    VAP_TRY(check_shape(B, 2, S));
+    if (!c || !d_meta || !d_out) return vap_fail(VAP_ERR_INVALID, "null buffer");
+    const bool any_acc = d_acc_forward || d_acc_backward || d_dec_backward;
+    if (any_acc && !(d_acc_forward && d_acc_backward && d_dec_backward && d_vcap))
+        return vap_fail(VAP_ERR_INVALID, "max_acceleration rows come as a set (forward, backward, dec) together with d_vcap");
+    return VAP_OK;
+}
+
+// ... and the rows their sweeps run on: the caller's, or (d_dtheta == NULL) the rows the last sampling call left on the
+// context.  r64: the curvature / |dtheta| rows, and with them the limit rows, are fp64.
+struct VelocityRows {
+    const void *curv = nullptr, *dth = nullptr;
+    bool r64 = false;
+    vap::AccRowsV acc;
+    double cc[6];
+};
+int resolve_velocity_rows(vap_ctx *ctx, vap_dtype dt, int B, int S, const vap_constraints *c, const void *d_curvature,
+                          const void *d_dtheta, const void *d_vcap, const void *d_acc_forward, const void *d_acc_backward,
+                          const void *d_dec_backward, VelocityRows &r)
+{
+    // The limit rows have the type of the recurrence they enter (vap_limit_rows_dtype): a limit such as 13.9 ft/s^2 rounded
+    // to fp32 and then amplified by the fp64 recurrence (DESIGN.md section 3) left the 1e-5 bound.  An explicit fp32
+    // d_dtheta makes this call an fp32 recurrence, which cannot take the fp64 limit rows of the default mode.
+    if (dt == VAP_F32 && d_dtheta && (d_vcap || d_acc_forward) && ctx->f32_recurrence == VAP_RECURRENCE_F64)
+        return vap_fail(VAP_ERR_INVALID, "VAP_F32 with VAP_RECURRENCE_F64: the limit rows are fp64 and go with the context's fp64 rows "
+                                         "(d_dtheta = NULL); for an fp32 recurrence on caller rows set VAP_OPT_F32_RECURRENCE first");
+    r.r64 = dt == VAP_F64;
+    if (!d_dtheta) VAP_TRY(vap_ctx_rows(ctx, dt, B, S, d_curvature, d_dtheta, r.r64));   // the rows the last sampling call left
+    if (!d_curvature) return vap_fail(VAP_ERR_INVALID, "null curvature row");
+    r.curv = d_curvature;
+    r.dth = d_dtheta;
+    velocity_consts(c, r.cc);
+    r.acc = vap::AccRowsV{d_acc_forward, d_acc_backward, d_dec_backward};
+    return VAP_OK;
+}
+
 // What the sampling kernel and the velocity pass of one call work on, resolved once: the caller's buffers or the context's
 // scratch.  hi — VAP_F32 with the fp64 recurrence (the default): the velocity pass reads fp64 curvature / |dtheta| rows,
 // which the sampling kernel leaves in k64 / dth64 next to the caller's fp32 rows.
@@ -433,6 +474,10 @@ int vap_ctx_set_option(vap_ctx *ctx, int option, int value)
         ctx->footprint_cull = value;
         return VAP_OK;
     }
+    if (option == VAP_OPT_CONDITIONING_SCRATCH_MB && value >= 1 && value <= 16384) {
+        ctx->cond_scratch_mb = value;
+        return VAP_OK;
+    }
     if (option == VAP_OPT_F32_RECURRENCE && (value == VAP_RECURRENCE_F64 || value == VAP_RECURRENCE_F32)) {
         ctx->f32_recurrence = value;
         ctx->left.rows = VAP_ROWS_NONE;   // rows left by an earlier call belong to the other mode
@@ -530,25 +575,46 @@ int vap_velocity_pass_limits(vap_ctx *ctx, vap_dtype dt, int B, int S, const vap
                              const void *d_dec_backward, void *d_velocity, uint32_t *d_flags)
 {
     VAP_TRY(vap_set_device(ctx));
-    VAP_TRY(check_shape(B, 2, S));
-    if (!c || !d_meta || !d_velocity) return vap_fail(VAP_ERR_INVALID, "null buffer");
-    const bool any_acc = d_acc_forward || d_acc_backward || d_dec_backward;
-    if (any_acc && !(d_acc_forward && d_acc_backward && d_dec_backward && d_vcap))
-        return vap_fail(VAP_ERR_INVALID, "max_acceleration rows come as a set (forward, backward, dec) together with d_vcap");
-    // The limit rows have the type of the recurrence they enter (vap_limit_rows_dtype): a limit such as 13.9 ft/s^2 rounded
-    // to fp32 and then amplified by the fp64 recurrence (DESIGN.md section 3) left the 1e-5 bound.  An explicit fp32
-    // d_dtheta makes this call an fp32 recurrence, which cannot take the fp64 limit rows of the default mode.
-    if (dt == VAP_F32 && d_dtheta && (d_vcap || any_acc) && ctx->f32_recurrence == VAP_RECURRENCE_F64)
-        return vap_fail(VAP_ERR_INVALID, "VAP_F32 with VAP_RECURRENCE_F64: the limit rows are fp64 and go with the context's fp64 rows "
-                                         "(d_dtheta = NULL); for an fp32 recurrence on caller rows set VAP_OPT_F32_RECURRENCE first");
-    bool r64 = dt == VAP_F64;
-    if (!d_dtheta) VAP_TRY(vap_ctx_rows(ctx, dt, B, S, d_curvature, d_dtheta, r64));   // the rows the last sampling call left
-    if (!d_curvature) return vap_fail(VAP_ERR_INVALID, "null curvature row");
-    double cc[6];
-    velocity_consts(c, cc);
-    const vap::AccRowsV acc{d_acc_forward, d_acc_backward, d_dec_backward};
-    VAP_TRY(run_velocity(ctx, r64, dt == VAP_F64, B, S, cc, start_vel, end_vel, d_meta, d_curvature, d_dtheta, d_vcap, acc,
-                         d_velocity, d_flags));
+    VAP_TRY(check_velocity_args(B, S, c, d_meta, d_vcap, d_acc_forward, d_acc_backward, d_dec_backward, d_velocity));
+    VelocityRows r;
+    VAP_TRY(resolve_velocity_rows(ctx, dt, B, S, c, d_curvature, d_dtheta, d_vcap, d_acc_forward, d_acc_backward, d_dec_backward, r));
+    VAP_TRY(run_velocity(ctx, r.r64, dt == VAP_F64, B, S, r.cc, start_vel, end_vel, d_meta, r.curv, r.dth, d_vcap, r.acc, d_velocity,
+                         d_flags));
+    return VAP_OK;
+}
+
+int vap_velocity_conditioning(vap_ctx *ctx, vap_dtype dt, int B, int S, const vap_constraints *c, double start_vel, double end_vel,
+                              const double *d_meta, const void *d_curvature, const void *d_dtheta, const void *d_vcap,
+                              const void *d_acc_forward, const void *d_acc_backward, const void *d_dec_backward, int K, double delta,
+                              uint64_t seed, uint32_t first_path, double cond_limit, double *d_cond, int *d_worst_sample,
+                              int *d_worst_probe, uint32_t *d_flags, double *d_sensitivity, double *d_velocity)
+{
+    if (K != 1 && K != 3 && K != 7 && K != 15) return vap_fail(VAP_ERR_INVALID, "K=%d: 1, 3, 7 or 15 probes beside the unperturbed sweep", K);
+    int e2 = 0;
+    if (!(std::frexp(delta, &e2) == 0.5 && e2 - 1 >= -48 && e2 - 1 <= -20))
+        return vap_fail(VAP_ERR_INVALID, "delta=%g: a power of two in [2^-48, 2^-20]", delta);
+    if (!(cond_limit > 0)) return vap_fail(VAP_ERR_INVALID, "cond_limit must be positive (+inf: never flag)");
+    if (B < 0) return vap_fail(VAP_ERR_INVALID, "batch must be >= 0 (got %d)", B);
+    if (B > 0) VAP_TRY(check_velocity_args(B, S, c, d_meta, d_vcap, d_acc_forward, d_acc_backward, d_dec_backward, d_cond));
+    VAP_TRY(vap_set_device(ctx));
+    if (B == 0) return VAP_OK;
+    VelocityRows r;
+    VAP_TRY(resolve_velocity_rows(ctx, dt, B, S, c, d_curvature, d_dtheta, d_vcap, d_acc_forward, d_acc_backward, d_dec_backward, r));
+    vap::CondArgs g;
+    g.S = S; g.K = K;
+    memcpy(g.c, r.cc, sizeof(g.c));
+    g.start_vel = start_vel; g.end_vel = end_vel; g.delta = delta; g.limit = cond_limit;
+    g.seed = seed; g.first_path = first_path;
+    g.meta = d_meta; g.curv = r.curv; g.dth = r.dth; g.vcap = d_vcap; g.acc = r.acc;
+    g.cond = d_cond; g.worst_sample = d_worst_sample; g.worst_probe = d_worst_probe; g.flags = d_flags;
+    g.sens = d_sensitivity; g.vel = d_velocity;
+    // the probes' rows of one launch stay under the budget (one path's rows are the least a launch needs)
+    const size_t per_path = (size_t)(K + 1) * S * sizeof(double);
+    size_t fit = ((size_t)ctx->cond_scratch_mb << 20) / per_path;
+    const int per = fit < 1 ? 1 : (fit > (size_t)B ? B : (int)fit);
+    VAP_TRY(ctx->ensure(ctx->cond_u, per_path * per));
+    for (int b0 = 0; b0 < B; b0 += per)
+        HIP_TRY(vap::launch_conditioning(ctx->stream, r.r64, g, b0, B - b0 < per ? B - b0 : per, (double *)ctx->cond_u.ptr));
     return VAP_OK;
 }
 

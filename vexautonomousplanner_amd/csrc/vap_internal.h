@@ -94,6 +94,9 @@ struct vap_ctx {
     VapBuffer track_part;
     // vap_plan_seeds: the grid's free mask, and the traced cell lists (one per resident workgroup)
     VapBuffer plan_free, plan_path;
+    // vap_velocity_conditioning: the probes' squared velocities of one launch, at most cond_scratch_mb MiB of them
+    VapBuffer cond_u;
+    int cond_scratch_mb = 512;        // VAP_OPT_CONDITIONING_SCRATCH_MB
 
     int ensure(VapBuffer &b, size_t bytes)
     {

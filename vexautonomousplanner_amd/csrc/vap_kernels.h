@@ -96,6 +96,24 @@ size_t velocity_chase_counter_bytes(int B);
 hipError_t launch_velocity_chase(hipStream_t st, bool f64, bool io64, int B, int S, const double c[6], double sv, double ev,
                                  const double *meta, const void *curv, const void *dth, void *vel, uint32_t *flags,
                                  void *ufwd, void *state, int *counters, void *vhi = nullptr);
+// vap_velocity_conditioning (vap_conditioning.hip): paths [b0, b0 + nb) of the call in one launch; `scratch` holds
+// nb x (K + 1) x S doubles.  The rows are the whole call's, fp64 (r64) or fp32 — limit rows in the same type.
+constexpr uint32_t VAP_FLAG_ILLCONDITIONED_BIT = 1024u;
+struct CondArgs {
+    int S = 0, K = 0;
+    double c[6] = {};
+    double start_vel = 0.0, end_vel = 0.0, delta = 0.0, limit = 0.0;
+    uint64_t seed = 0;
+    uint32_t first_path = 0;
+    const double *meta = nullptr;
+    const void *curv = nullptr, *dth = nullptr, *vcap = nullptr;
+    AccRowsV acc;
+    double *cond = nullptr;
+    int *worst_sample = nullptr, *worst_probe = nullptr;
+    uint32_t *flags = nullptr;
+    double *sens = nullptr, *vel = nullptr;
+};
+hipError_t launch_conditioning(hipStream_t st, bool r64, const CondArgs &g, int b0, int nb, double *scratch);
 // res[i] = (float)(v64[i] - (double)v32[i]): the fp32 residual row the time domain adds back to the caller's fp32 row
 hipError_t launch_velocity_residual(hipStream_t st, size_t n, const double *v64, const float *v32, float *res);
 // K5w (vap_velocity_lanes.hip), fp64 recurrence only: lane per path, `group` paths per workgroup (0 = by batch size).

@@ -23,30 +23,12 @@
 
 #include "vap_internal.h"
 #include "vap_kernels.h"
+#include "vap_philox.h"          // philox4x32_10 (shared with vap_conditioning.hip)
 
 namespace vap {
 
 constexpr int kSearchMaxCandidates = 4096;
 constexpr int kSearchSampleThreads = 256;
-
-struct uint4x {
-    uint32_t x, y, z, w;
-};
-
-// Philox4x32-10 (Salmon et al., SC'11): counter c, key k
-__device__ __forceinline__ uint4x philox4x32_10(uint4x c, uint32_t k0, uint32_t k1)
-{
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int i = 0; i < 10; i++) {
-        const uint32_t hi0 = __umulhi(M0, c.x), lo0 = M0 * c.x;
-        const uint32_t hi1 = __umulhi(M1, c.z), lo1 = M1 * c.z;
-        c = uint4x{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-        k0 += W0;
-        k1 += W1;
-    }
-    return c;
-}
 
 template <typename T>
 struct Pair;
