@@ -690,6 +690,72 @@ int vap_tracking_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_ro
                           double *d_stats, int *d_stat_rows, double *d_worst, double *d_mean, int *d_worst_rollout,
                           int *d_worst_row, int *d_n_exceeding, long cap_exec, double *d_exec_rows, int *d_exec_counts);
 
+/* ---- closed-loop rollouts under a pure-pursuit follower ------------------------------------------------------------
+ * The same question as vap_tracking_rollouts for the follower most teams run.  Pure pursuit is indexed by where the robot
+ * is on the path, not by the clock: it reads the polyline of the rows and their speeds and steers for a goal one lookahead
+ * further along it.  Layout conventions, perturbation records, the plant (lag, exact arc), saturation, the executed rows
+ * and the per-route summary are vap_tracking_rollouts'; what differs is stated here.  fp64 throughout.
+ *
+ *   path      of a route with n rows (the count clamped to [0, capacity]): points P_i = columns 6, 7 and speeds v_i =
+ *             column 2, i = 0 .. n - 1.  Columns 1, 4 and 5 are not read, except row 0's columns 4 and 5 for the start
+ *             state.  Segment i = 0 .. n - 2: s_i = P_(i+1) - P_i, len_i = sqrt(s_x^2 + s_y^2); cumulative chord length
+ *             c_0 = 0, c_(i+1) = c_i + len_i summed strictly in index order.  Segments without length (wait rows, in-place
+ *             turns) are legal and passed over.  u_end = s_i / len_i of the last segment with len_i > 0, (1, 0) if none.
+ *             Every norm below is sqrt(dx^2 + dy^2).
+ *   status    d_route_status [B], a bit mask over rows 0 .. n - 1, written before the rollouts: bit 0 a row with v_i < 0,
+ *             bit 1 a non-finite x, y or v.  A route with a non-zero status is treated as a route with n = 0.
+ *   NOT EXECUTED BY THIS FOLLOWER: reverse legs (status bit 0), and in-place turns and dwells (their rows have no
+ *             length: the robot drives on, it neither stops to wait nor turns on the spot).
+ *   follower  vap_pursuit: track_width T (ft), lookahead (ft), min_speed (ft/s: the commanded speed never falls below
+ *             it before arrival), arrive_tolerance (ft), the wheel speed limit (ft/s), the tolerance the route summary
+ *             counts against (ft), n_substeps, settle_rows.
+ *   perturb   vap_tracking_rollouts' record {dx, dy, dphi, gain_left, gain_right, track_scale, tau, lookahead} and its
+ *             validity rule; slot 7 is the ROLLOUT'S LOOKAHEAD L: 0 means f->lookahead, > 0 is L in feet, < 0 or
+ *             non-finite makes the record invalid.  So K can span perturbations x lookaheads.
+ *   state     the pose and wheels start as in vap_tracking_rollouts: (x_0 + dx, y_0 + dy, -heading_0 + dphi), wheels
+ *             from v_0 and omega_0 = -column 5 of row 0.  Besides: ic = 0 (closest segment), il = 0 (lookahead segment),
+ *             arrived = -1.
+ *   step      r = 0 .. n + settle_rows - 1, in this order:
+ *             1. closest point (n >= 2).  For a segment i: t_i = clamp(((p - P_i) . s_i) / (s_i . s_i), 0, 1), 0 if
+ *                s_i . s_i == 0; q_i = P_i + t_i s_i; D_i = |p - q_i|^2.  While ic < n - 2 and D_(ic+1) <= D_ic: ic += 1.
+ *                Then e_ct = sqrt(D_ic), v_t = v_ic + t (v_(ic+1) - v_ic), s_c = c_ic + t len_ic, at_end = (ic == n - 2
+ *                and t == 1).  n = 1: e_ct = |p - P_0|, v_t = v_0, at_end.
+ *             2. statistics: the maximum e_ct and the first step that strictly exceeds the running maximum.
+ *             3. executed row r (if requested): vap_tracking_rollouts' step 3.
+ *             4. arrival: if arrived < 0 and (at_end or |P_(n-1) - p| <= arrive_tolerance): arrived = r.  From that step
+ *                on c_L = c_R = 0.
+ *             5. while not arrived: s* = s_c + L; il = max(il, ic); while il < n - 2 and c_(il+1) < s*: il += 1.  If
+ *                s* >= c_(n-1) the goal is G = P_(n-1) + (s* - c_(n-1)) u_end (the path prolonged along its last
+ *                tangent); otherwise f = clamp((s* - c_il) / len_il, 0, 1), 0 if len_il == 0, and G = P_il + f s_il.
+ *                l_y = -sin(phi) (G_x - x) + cos(phi) (G_y - y); a2 = |G - p|^2; kappa = 2 l_y / a2, 0 if a2 == 0;
+ *                sp = max(v_t, min_speed); c_L = sp - sp kappa T / 2, c_R = sp + sp kappa T / 2.
+ *             6. saturation and 7. substeps: vap_tracking_rollouts' steps 5 and 6.
+ *             After the last step: the final position error |P_(n-1) - p|.
+ *   outputs   any pointer may be NULL.
+ *             per rollout: d_stats [B][K][6] = {max e_ct, final position error, arrival time = arrived * time_step (NaN
+ *             if it never arrived), the rollout's lookahead, 0, 0}; d_stat_rows [B][K][4] = {step of max e_ct, saturated
+ *             rows, arrived step (-1 if never), final ic}.
+ *             per route [B]: d_worst, d_worst_rollout, d_worst_row, d_mean, d_n_exceeding as vap_tracking_rollouts over
+ *             max e_ct; d_n_unfinished (valid rollouts with arrived < 0); d_route_status.
+ *             executed rows: d_exec_rows, d_exec_counts and cap_exec exactly as vap_tracking_rollouts.
+ *   edges     n = 0, a non-zero status and an invalid record: NaN in all six stats, -1 in all four stat rows, executed
+ *             count 0, no part in the route's summary (a route without a valid rollout: NaN, NaN, -1, -1, 0, 0).
+ *   alignment as vap_tracking_rollouts: d_rows, d_perturb, d_stats, d_exec_rows 16-byte aligned, else VAP_ERR_INVALID.
+ * VAP_ERR_INVALID: a non-positive (or non-finite) track_width, lookahead, wheel_speed_max or time_step; a negative (or
+ * non-finite) min_speed or arrive_tolerance; a NaN tolerance; n_substeps outside 1..16; settle_rows outside 0..10000; K
+ * outside 1..4096; a null rows, counts or perturbation pointer with B > 0; cap_exec below capacity + settle_rows.  The
+ * arguments are checked before the context is touched.  B = 0 is a no-op.  Works on the context's stream and does not
+ * synchronise.  Two calls on the same inputs give the same bits: every reduction has a fixed order, no float atomics. */
+typedef struct {
+    double track_width, lookahead, min_speed, arrive_tolerance, wheel_speed_max, tolerance;
+    int n_substeps, settle_rows;
+} vap_pursuit;
+int vap_pursuit_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride,
+                         double time_step, const vap_pursuit *f, int K, int shared_perturb, const double *d_perturb,
+                         double *d_stats, int *d_stat_rows, double *d_worst, double *d_mean, int *d_worst_rollout,
+                         int *d_worst_row, int *d_n_exceeding, int *d_n_unfinished, int *d_route_status, long cap_exec,
+                         double *d_exec_rows, int *d_exec_counts);
+
 /* ---- cross-entropy route search over batches of candidate trajectories --------------------------------------------
  * The calls above judge candidate routes; these two make the candidates and act on the verdicts, so that a search
  *   sample -> vap_profile_batch -> vap_time_profile -> vap_footprint_clearance [-> conflicts, rollouts] -> update

@@ -1,0 +1,595 @@
+"""GPU: pure-pursuit rollouts (vap_pursuit_rollouts, tracking.rollouts with a tracking.Pursuit) against the NumPy reference
+of tests/pursuit_ref.py in float64: the plain golden routes' full time-domain rows, synthetic drives with K from 1 to 300
+(several routes per workgroup, idle lanes, several workgroups per route and the reduce kernel), one workgroup holding
+routes of 0, 1, 2, 37 and capacity rows, a route whose lookahead pointer runs hundreds of rows ahead of the closest one,
+a lookahead sweep through slot 7, shared against per-route records, a route with a status bit among good ones, a
+saturating drive, two calls bit for bit, the executed rows through footprint.clearance, the C-ABI's checks with a live
+context, and search.refine with a Pursuit.
+
+Tolerance (the convention of section 13).  Per case the reference runs in float64 and in
+np.longdouble; D = |float64 - longdouble| per output value is the reference's own rounding error, and the kernel must lie
+within max(1e-12, 8 D), capped at 1e-9 (ft, s), of the float64 reference.  The integer outputs (step of the maximum,
+saturated rows, arrived step, final ic) must be equal.  A rollout is excused from the integer comparison on two grounds
+only: the reference's float64 and longdouble runs disagree on that integer, or the deciding quantity is within 1e-9 of its
+threshold in the reference (a second step's e_ct against the maximum; some step's command against the wheel limit; some
+step's end distance against arrive_tolerance).  At most 2 % of a test's rollouts may be excused.  In-place-turn routes
+(feat_turn), where the reference disagrees with itself, are compared for finiteness and determinism only."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import footprint_ref as fr
+import golden_util as gu
+import pursuit_ref as pr
+
+pytestmark = pytest.mark.gpu
+
+FLOOR, FACTOR, CAP = 1e-12, 8.0, 1e-9
+AMBIGUOUS = 1e-9
+DT = 0.01
+STAT_NAMES = ("max e_ct", "final error", "arrival time", "lookahead", "0", "0")
+INT_NAMES = ("step of max e_ct", "saturated rows", "arrived step", "final ic")
+SUMMARY = ("worst", "mean", "worst_rollout", "worst_row", "n_exceeding", "n_unfinished", "route_status")
+
+
+@pytest.fixture(scope="module")
+def torch_mod():
+    import torch
+    assert torch.cuda.is_available()
+    return torch
+
+
+def trk():
+    from vexautonomousplanner_amd import tracking
+    return tracking
+
+
+def ref_dict(f):
+    return pr.pursuit(**{k: getattr(f, k) for k in pr.DEFAULTS})
+
+
+def tol_of(a64, ald):
+    d = np.abs(a64.astype(np.longdouble) - ald).astype(np.float64)
+    return np.minimum(np.maximum(FLOOR, FACTOR * d), CAP), d
+
+
+class Tally:
+    """Rollouts compared and excused, and the largest reference rounding error D and kernel difference seen."""
+
+    def __init__(self):
+        self.n, self.excused, self.d, self.k = 0, 0, 0.0, 0.0
+
+    def take(self, d, k):
+        if np.size(d):
+            self.d, self.k = max(self.d, float(np.nanmax(d))), max(self.k, float(np.nanmax(k)))
+
+    def check(self):
+        assert self.excused <= 0.02 * max(self.n, 1), f"{self.excused} of {self.n} rollouts excused from the integer comparison"
+
+    def __str__(self):
+        return f"{self.n} rollouts compared, {self.excused} excused, worst D {self.d:.2e}, worst |kernel - reference| {self.k:.2e}"
+
+
+def excusable(r64, rld, k, f):
+    """The two grounds on which rollout k's integers may differ from the reference's."""
+    if not np.array_equal(r64["stat_rows"][k], rld["stat_rows"][k]):
+        return True
+    e = r64["e_ct"][k]
+    if int((np.abs(e - r64["stats"][k, 0]) <= AMBIGUOUS).sum()) > 1:
+        return True
+    if (np.abs(r64["cmd_max"][k] - f["wheel_speed_max"]) <= AMBIGUOUS).any():
+        return True
+    return bool((np.abs(r64["end_dist"][k] - f["arrive_tolerance"]) <= AMBIGUOUS).any())
+
+
+def compare(res, rows, counts, follower, P, executed=False, tally=None, routes=None):
+    """Every output of a kernel call against the reference, for ``routes`` (default: all).  P: (B, K, 8).  Returns the
+    reference's float64 outputs per compared route."""
+    f = ref_dict(follower)
+    tally = tally if tally is not None else Tally()
+    stats, srows = res["stats"].cpu().numpy(), res["stat_rows"].cpu().numpy()
+    summ = {k: res[k].cpu().numpy() for k in SUMMARY}
+    B, K = P.shape[:2]
+    assert stats.shape == (B, K, 6) and srows.shape == (B, K, 4)
+    if executed:
+        erows, ecounts = res["rows"].cpu().numpy(), res["counts"].cpu().numpy()
+        assert erows.shape[0] == B * K and ecounts.shape == (B * K, 2)
+    refs = {}
+    for b in (range(B) if routes is None else routes):
+        n = min(max(int(counts[b]), 0), rows.shape[1])
+        r64 = pr.rollout(rows[b], n, f, P[b], DT, executed=executed)
+        rld = pr.rollout(rows[b], n, f, P[b], DT, executed=executed, dtype=np.longdouble)
+        refs[b] = r64
+        assert summ["route_status"][b] == r64["status"], (b, summ["route_status"][b], r64["status"])
+        ok = r64["stat_rows"][:, 0] >= 0
+        # rollouts without a result: NaN / -1, no executed rows
+        assert np.isnan(stats[b, ~ok]).all() and (srows[b, ~ok] == -1).all(), b
+        assert np.isfinite(stats[b, ok][:, [0, 1, 3, 4, 5]]).all() and (srows[b, ok][:, [0, 1, 3]] >= 0).all(), b
+        if executed:
+            assert (ecounts[b * K:(b + 1) * K, 0] == r64["counts"]).all() and (ecounts[b * K:(b + 1) * K, 1] == 0).all(), b
+        t, d = tol_of(r64["stats"], rld["stats"])
+        diff = np.abs(stats[b] - r64["stats"])
+        excused_here = 0
+        for k in np.nonzero(ok)[0]:
+            tally.n += 1
+            same = np.array_equal(srows[b, k], r64["stat_rows"][k])
+            if not same:
+                assert excusable(r64, rld, k, f), (b, k, dict(zip(INT_NAMES, zip(srows[b, k], r64["stat_rows"][k]))))
+                tally.excused += 1
+                excused_here += 1
+                assert np.isfinite(stats[b, k, :2]).all()
+                continue
+            for c in range(6):
+                if c == 2 and r64["stat_rows"][k, 2] < 0:
+                    assert np.isnan(stats[b, k, 2]), (b, k, "arrival time of a rollout that never arrived")
+                    continue
+                assert diff[k, c] <= t[k, c], (b, k, STAT_NAMES[c], stats[b, k, c], r64["stats"][k, c], d[k, c])
+                tally.take(d[k, c], diff[k, c])
+            assert stats[b, k, 3] == (P[b, k, 7] if P[b, k, 7] > 0 else f["lookahead"]) and (stats[b, k, 4:] == 0).all()
+            if executed:
+                m = int(r64["counts"][k])
+                got, want = erows[b * K + k, :m], r64["rows"][k]
+                te, de = tol_of(want, rld["rows"][k])
+                dd = np.abs(got - want)
+                assert (np.abs(got[:, 4]) <= np.pi).all(), (b, k, "executed heading outside [-pi, pi]")
+                at_pi = np.abs(np.abs(want[:, 4]) - np.pi) <= AMBIGUOUS      # either side of the wrap
+                dd[at_pi, 4] = np.abs(pr.wrap(got[at_pi, 4] - want[at_pi, 4]))
+                bad = np.argwhere(dd > te)
+                assert not len(bad), (b, k, "executed", bad[0], got[tuple(bad[0])], want[tuple(bad[0])], de[tuple(bad[0])])
+                tally.take(de, dd)
+        # the route's summary
+        s64 = pr.route_summary(r64["stats"], r64["stat_rows"], f["tolerance"])
+        sld = pr.route_summary(rld["stats"], rld["stat_rows"], f["tolerance"])
+        if not ok.any():
+            assert np.isnan(summ["worst"][b]) and np.isnan(summ["mean"][b]), b
+            assert [int(summ[key][b]) for key in ("worst_rollout", "worst_row", "n_exceeding", "n_unfinished")] == [-1, -1, 0, 0], b
+            continue
+        # the kernel's own summary is exactly the fixed-order reduction of its own per-rollout outputs
+        own = pr.route_summary(stats[b], srows[b], f["tolerance"])
+        wk = int(summ["worst_rollout"][b])
+        assert (summ["worst"][b], summ["mean"][b], wk, summ["worst_row"][b], summ["n_exceeding"][b], summ["n_unfinished"][b]) == \
+            (own["worst"], own["mean"], own["worst_rollout"], own["worst_row"], own["n_exceeding"], own["n_unfinished"]), b
+        if excused_here == 0:
+            for key in ("worst", "mean"):
+                t1, _ = tol_of(np.float64(s64[key]), np.longdouble(sld[key]))
+                assert abs(summ[key][b] - s64[key]) <= t1, (b, key, summ[key][b], s64[key])
+            assert ok[wk] and abs(r64["stats"][wk, 0] - s64["worst"]) <= AMBIGUOUS, (b, wk)
+            if np.min(np.abs(r64["stats"][ok, 0] - f["tolerance"])) > AMBIGUOUS:
+                assert summ["n_exceeding"][b] == s64["n_exceeding"], b
+            assert summ["n_unfinished"][b] == s64["n_unfinished"], b
+    return refs
+
+
+def bits(res, keys=("stats", "stat_rows") + SUMMARY):
+    return {k: res[k].cpu().numpy().view(np.int64 if res[k].dtype.itemsize == 8 else np.int32).copy() for k in keys if k in res}
+
+
+def same_bits(a, b, keys=("stats", "stat_rows") + SUMMARY):
+    x, y = bits(a, keys), bits(b, keys)
+    for k in x:
+        np.testing.assert_array_equal(x[k], y[k], err_msg=k)
+
+
+def synth_rows(rng, B, cap, v0=2.0):
+    """Consistent rows of smooth random drives: v(t) > 0, omega(t) are sums of a few sines, integrated by the exact arc."""
+    rows = np.zeros((B, cap, 8))
+    t = np.arange(cap) * DT
+    for b in range(B):
+        v = v0 + sum(rng.uniform(0, 0.25 * v0) * np.sin(rng.uniform(0.5, 4) * t + rng.uniform(0, 6)) for _ in range(3))
+        w = sum(rng.uniform(0, 0.8) * np.sin(rng.uniform(0.5, 5) * t + rng.uniform(0, 6)) for _ in range(3))
+        x, y, phi = rng.uniform(-4, 4), rng.uniform(-4, 4), rng.uniform(-np.pi, np.pi)
+        s = 0.0
+        for r in range(cap):
+            rows[b, r] = [t[r], s, v[r], 0.0, -pr.wrap(phi), -w[r], x, y]
+            u = w[r] * DT / 2
+            d = v[r] * DT * float(pr.sinc(u))
+            x, y, phi, s = x + d * np.cos(phi + u), y + d * np.sin(phi + u), phi + w[r] * DT, s + abs(d)
+        rows[b, 1:, 3] = np.diff(rows[b, :, 2]) / DT
+    return rows
+
+
+# ---- the golden routes' full rows: values, executed rows, clearance of the executed rows ---------------------------------
+def full_rows(torch, name):
+    from vexautonomousplanner_amd.batch import BatchedTrajectoryGenerator
+    g = gu.load(name)
+    gen = BatchedTrajectoryGenerator(0, "f64")
+    cons = [float(v) for v in g["constraints"]]
+    rep = lambda a: np.asarray(a)[None]
+    wp = torch.tensor(rep(g["waypoints"]), dtype=torch.float64, device=gen.device)
+    res = gen.profile_routes(wp, node_reverse=rep(g["node_is_reverse_node"]), node_turn=rep(g["node_turn"]),
+                             node_tangent=rep(g["node_tangent"]), node_magnitudes=rep(g["node_magnitudes"]),
+                             constraints=cons, dd=0.005, capacity=16384)
+    gen.apply_node_limits(res, cons, node_max_velocity=rep(g["node_max_velocity"]), node_stop=rep(g["node_stop"]),
+                          node_max_acceleration=rep(g["node_max_acceleration"]))
+    tp = gen.time_profile(res, cons, dt=DT, capacity_rows=4096, node_reverse=rep(g["node_is_reverse_node"]))
+    out = gen.insert_waits(res, tp, node_wait_time=rep(g["node_wait_time"]), dt=DT, node_turn=rep(g["node_turn"]),
+                           node_reverse=rep(g["node_is_reverse_node"]), constraints=cons)
+    torch.cuda.synchronize()
+    assert not res["flags"].any().item()
+    return gen, out
+
+
+def golden_records(tk, K):
+    """sample_perturbations' default sigmas, tau = 50 ms; one record with tau = 0 beside the nominal one, one invalid."""
+    P = tk.sample_perturbations(1, K, seed=11)
+    P[0, 5, 6] = 0.0
+    P[0, 9, 4] = 0.0                                             # invalid: gain_right <= 0
+    return P
+
+
+@pytest.mark.parametrize("name", ["c1_w8", "feat_limits", "feat_stop", "feat_wait"])
+def test_plain_golden_routes_full_rows(torch_mod, name):
+    from vexautonomousplanner_amd import footprint as fp
+    torch = torch_mod
+    tk = trk()
+    gen, out = full_rows(torch, name)
+    rows, counts = out["rows"].cpu().numpy(), out["counts"][:, 0].cpu().numpy()
+    n = int(counts[0])
+    K = 16
+    follower = tk.Pursuit()
+    P = golden_records(tk, K)
+    res = gen.tracking_rollouts(out, follower, P, time_step=DT, executed=True)
+    torch.cuda.synchronize()
+    tally = Tally()
+    refs = compare(res, rows, counts, follower, P, executed=True, tally=tally)
+    print(f"{name}: {n} rows, {tally}; undisturbed max e_ct {res['max_cross_track'][0, 0].item():.4f} ft, arrived at step "
+          f"{int(res['arrived_row'][0, 0])}; worst of {K} {res['worst'][0].item():.4f} ft (rollout {int(res['worst_rollout'][0])})")
+    tally.check()
+    assert tally.n == K - 1 and int(res["route_status"][0]) == 0
+    assert int(res["arrived_row"][0, 0]) >= 0, "the undisturbed rollout arrives"
+    assert torch.isnan(res["stats"][0, 9]).all() and (res["stat_rows"][0, 9] == -1).all() and int(res["counts"][9, 0]) == 0
+    assert res["rows"].shape == (K, rows.shape[1] + follower.settle_rows, 8) and res["counts"].shape == (K, 2)
+    # composition: the executed rows go to the clearance call as they are
+    foot = fp.rectangle(18, 18, 2)
+    rng = np.random.default_rng(n)
+    pts = rows[0, rng.integers(0, n, 4), 6:8]
+    lo, hi = rows[0, :n, 6:8].min(axis=0), rows[0, :n, 6:8].max(axis=0)
+    scene = fp.Scene(field=(lo[0] - 1.0, lo[1] - 1.6, hi[0] + 1.5, hi[1] + 1.2),
+                     circles=[(*(p + rng.normal(0, 0.8, 2)), rng.uniform(0.1, 0.5)) for p in pts])
+    cl = gen.footprint_clearance(res, foot, scene, margin=0.1, per_row=True)
+    torch.cuda.synchronize()
+    got = {k: cl[k].cpu().numpy() for k in ("min_clearance", "min_row", "row_clearance")}
+    wc = 0.0
+    for k in (0, 5, 12):
+        m = int(refs[0]["counts"][k])
+        s = fr.route_summary(refs[0]["rows"][k].astype(np.float64), m, foot, field=scene.field, circles=scene.circles, margin=0.1)
+        d = max(abs(got["min_clearance"][k] - s["min_clearance"]), float(np.max(np.abs(got["row_clearance"][k, :m] - s["rows"]))))
+        wc = max(wc, d)
+        assert d <= 1e-9, (k, d)
+        assert abs(s["rows"][int(got["min_row"][k])] - s["min_clearance"]) <= AMBIGUOUS
+        assert np.isnan(got["row_clearance"][k, m:]).all()
+    print(f"{name}: clearance of the executed rows against the reference's: max diff {wc:.2e} ft")
+
+
+def test_in_place_turn_route_is_finite_and_deterministic(torch_mod):
+    torch = torch_mod
+    tk = trk()
+    gen, out = full_rows(torch, "feat_turn")
+    P = tk.sample_perturbations(1, 8, seed=11)
+    a = gen.tracking_rollouts(out, tk.Pursuit(), P, time_step=DT)
+    b = gen.tracking_rollouts(out, tk.Pursuit(), P, time_step=DT)
+    torch.cuda.synchronize()
+    same_bits(a, b)
+    assert int(a["route_status"][0]) == 0 and torch.isfinite(a["stats"][..., [0, 1, 3]]).all() and (a["max_row"] >= 0).all()
+    print(f"feat_turn: undisturbed max e_ct {a['max_cross_track'][0, 0].item():.4f} ft, worst of 8 {a['worst'][0].item():.4f} ft")
+    assert a["max_cross_track"][0, 0].item() > 0.25
+
+
+# ---- K sweep: layouts, shared records, short counts, empty routes, invalid records, two calls ----------------------------
+@pytest.mark.parametrize("K,B,ncmp", [(1, 300, 8), (3, 100, 6), (16, 20, 5), (64, 6, 3), (300, 3, 2)])
+def test_rollout_counts_and_layouts(torch_mod, K, B, ncmp):
+    torch = torch_mod
+    tk = trk()
+    rng = np.random.default_rng(200 + K)
+    cap = 110
+    rows = synth_rows(rng, B, cap)
+    counts = rng.integers(30, cap + 1, B).astype(np.int32)
+    counts[B // 2] = 0                                          # a route without rows
+    counts[0], counts[B - 1] = cap + 500, cap                   # clamped to capacity
+    if B > 4:
+        counts[1] = -3                                          # clamped to 0
+    for b in range(B):                                          # rows past counts are never read
+        rows[b, max(min(int(counts[b]), cap), 0):] = np.nan
+    follower = tk.Pursuit(settle_rows=25, n_substeps=3, tolerance=0.1, lookahead=0.5)
+    P = tk.sample_perturbations(B, K, seed=K, tau=0.03)
+    if K >= 3:
+        P[:, K // 2, 3] = 0.0                                   # invalid: gain_left <= 0
+        P[0, K - 1, 0] = np.nan                                 # invalid: non-finite
+        P[B - 1, 1, 7] = -0.25                                  # invalid: slot 7 < 0
+        P[B - 1, 2, 7] = 0.9                                    # a lookahead of its own
+    else:
+        P[3, 0, 4] = -1.0                                       # a route whose only rollout is invalid
+    d_rows, d_counts = torch.tensor(rows, device="cuda:0"), torch.tensor(counts, device="cuda:0")
+    res = tk.rollouts(d_rows, d_counts, follower, P, time_step=DT, executed=True)
+    again = tk.rollouts(d_rows, d_counts, follower, torch.tensor(P, device="cuda:0"), time_step=DT, executed=True)
+    torch.cuda.synchronize()
+    pick = sorted({0, B - 1, B // 2, 3 % B} | set(rng.choice(B, ncmp, replace=False).tolist()))
+    tally = Tally()
+    compare(res, rows, counts, follower, P, executed=True, tally=tally, routes=pick)
+    print(f"K = {K}, B = {B}: routes {pick}: {tally}")
+    tally.check()
+    # every route, whether compared or not: a result where there are rows and a valid record, and only there
+    n_eff = np.clip(counts, 0, cap)
+    valid = pr.record_valid(P.reshape(-1, 8)).reshape(B, K) & (n_eff > 0)[:, None]
+    np.testing.assert_array_equal((res["max_row"].cpu().numpy() >= 0), valid)
+    np.testing.assert_array_equal(res["counts"][:, 0].cpu().numpy().reshape(B, K), np.where(valid, (n_eff + 25)[:, None], 0))
+    assert (res["route_status"] == 0).all()
+    # two calls: the same bits (executed rows over the rows that exist)
+    same_bits(res, again)
+    ec = res["counts"][:, 0].cpu().numpy()
+    ra, rb = res["rows"].cpu().numpy(), again["rows"].cpu().numpy()
+    for i in np.nonzero(ec)[0][:40]:
+        np.testing.assert_array_equal(ra[i, :ec[i]].view(np.int64), rb[i, :ec[i]].view(np.int64))
+    # shared records: (K, 8) for every route equals the same records repeated per route
+    Ps = P[B - 1].copy()
+    shared = tk.rollouts(d_rows, d_counts, follower, Ps, time_step=DT)
+    repeated = tk.rollouts(d_rows, d_counts, follower, np.repeat(Ps[None], B, axis=0), time_step=DT)
+    torch.cuda.synchronize()
+    same_bits(shared, repeated)
+    np.testing.assert_array_equal(bits(shared)["stats"][B - 1], bits(res)["stats"][B - 1])
+    # explicit edge outputs
+    e = B // 2
+    assert torch.isnan(res["stats"][e]).all() and (res["stat_rows"][e] == -1).all() and (res["counts"][e * K:(e + 1) * K] == 0).all()
+    assert torch.isnan(res["worst"][e]) and torch.isnan(res["mean"][e])
+    assert [int(res[k][e]) for k in ("worst_rollout", "worst_row", "n_exceeding", "n_unfinished")] == [-1, -1, 0, 0]
+    if K >= 3:
+        assert (res["worst_rollout"] != K // 2).all()
+        assert res["lookahead"][B - 1, 2].item() == 0.9 and res["lookahead"][B - 1, 0].item() == 0.5
+    else:
+        assert torch.isnan(res["worst"][3]) and int(res["worst_rollout"][3]) == -1 and int(res["n_unfinished"][3]) == 0
+
+
+def test_one_workgroup_with_routes_of_every_length(torch_mod):
+    """K = 16: a workgroup holds 16 routes; these have 0, 1, 2, 37 and capacity rows (and lengths between), so lanes of one
+    wave run for very different numbers of steps."""
+    torch = torch_mod
+    tk = trk()
+    rng = np.random.default_rng(7)
+    B, K, cap = 16, 16, 96
+    rows = synth_rows(rng, B, cap)
+    counts = rng.integers(3, cap, B).astype(np.int32)
+    counts[:5] = [0, 1, 2, 37, cap]
+    follower = tk.Pursuit(settle_rows=12)
+    P = tk.sample_perturbations(B, K, seed=9)
+    res = tk.rollouts(torch.tensor(rows, device="cuda:0"), torch.tensor(counts, device="cuda:0"), follower, P, time_step=DT, executed=True)
+    torch.cuda.synchronize()
+    tally = Tally()
+    compare(res, rows, counts, follower, P, executed=True, tally=tally, routes=[0, 1, 2, 3, 4, 9])
+    print(f"routes of 0, 1, 2, 37, {cap} rows in one workgroup: {tally}")
+    tally.check()
+    assert (res["arrived_row"][1] == 0).all() and (res["closest_segment"][1] == 0).all()       # one row: arrived at step 0
+    assert (res["counts"][K:2 * K, 0] == 13).all() and (res["counts"][:K, 0] == 0).all()
+
+
+def test_lookahead_far_ahead_of_the_closest_point(torch_mod):
+    """700 rows at 0.2 ft/s: segments of 0.002 ft.  With L = 1.5 ft the lookahead pointer runs hundreds of rows ahead of
+    the closest one (to the route's end, and then the goal leaves along the last tangent); with L = 0.3 ft it stays about
+    150 rows ahead.  No staging window could hold both ends: every point a lane needs comes from wherever it is."""
+    torch = torch_mod
+    tk = trk()
+    n = 700
+    t = np.arange(n) * DT
+    th = 0.4 * np.sin(2.0 * t / t[-1])
+    rows = np.zeros((1, n, 8))
+    rows[0, :, 0], rows[0, :, 2], rows[0, :, 4] = t, 0.2, -th
+    rows[0, 1:, 6] = np.cumsum(0.2 * DT * np.cos(th[:-1]))
+    rows[0, 1:, 7] = np.cumsum(0.2 * DT * np.sin(th[:-1]))
+    follower = tk.Pursuit(lookahead=1.5, settle_rows=60)
+    P = tk.lookahead_sweep(tk.sample_perturbations(1, 2, seed=5, pos_sigma=0.02)[0], [0.0, 0.3])[None]
+    counts = np.array([n], dtype=np.int32)
+    res = tk.rollouts(torch.tensor(rows, device="cuda:0"), torch.tensor(counts, device="cuda:0"), follower, P, time_step=DT, executed=True)
+    torch.cuda.synchronize()
+    tally = Tally()
+    compare(res, rows, counts, follower, P, executed=True, tally=tally)
+    print(f"n = 700 at 0.2 ft/s, L = 1.5 / 0.3 ft: {tally}; arrived at steps {res['arrived_row'][0].tolist()}")
+    tally.check()
+    assert res["lookahead"][0].tolist() == [1.5, 0.3, 1.5, 0.3] and tally.n == 4
+
+
+def test_lookahead_sweep_through_slot_7(torch_mod):
+    torch = torch_mod
+    tk = trk()
+    rng = np.random.default_rng(3)
+    B, cap = 3, 100
+    rows = synth_rows(rng, B, cap)
+    counts = np.array([100, 64, 81], dtype=np.int32)
+    follower = tk.Pursuit(settle_rows=30)
+    las = [0.5, 0.0, 1.0, 1.5]
+    S = tk.lookahead_sweep(tk.sample_perturbations(1, 4, seed=2)[0], las)                # (16, 8), shared by every route
+    d_rows, d_counts = torch.tensor(rows, device="cuda:0"), torch.tensor(counts, device="cuda:0")
+    shared = tk.rollouts(d_rows, d_counts, follower, S, time_step=DT)
+    per_route = tk.rollouts(d_rows, d_counts, follower, np.repeat(S[None], B, axis=0), time_step=DT)
+    torch.cuda.synchronize()
+    same_bits(shared, per_route)                                                         # shared_perturb 1 and 0
+    tally = Tally()
+    compare(shared, rows, counts, follower, np.repeat(S[None], B, axis=0), tally=tally)
+    print(f"lookahead sweep {las}: {tally}; undisturbed max e_ct per lookahead {shared['max_cross_track'][0, :4].tolist()}")
+    tally.check()
+    assert shared["lookahead"][0, :4].tolist() == [0.5, 0.75, 1.0, 1.5]
+    # slot 7 = L is a follower with lookahead L and slot 7 = 0
+    Z = S.copy()
+    Z[:, 7] = 0.0
+    for m, L in enumerate((0.5, 0.75, 1.0, 1.5)):
+        one = tk.rollouts(d_rows, d_counts, tk.Pursuit(settle_rows=30, lookahead=L), Z[m::4], time_step=DT)
+        np.testing.assert_array_equal(bits(one, ("stats", "stat_rows"))["stats"], bits(shared, ("stats",))["stats"][:, m::4])
+
+
+def test_a_route_with_a_status_bit_among_good_ones(torch_mod):
+    torch = torch_mod
+    tk = trk()
+    rng = np.random.default_rng(12)
+    B, K, cap = 5, 4, 80
+    rows = synth_rows(rng, B, cap)
+    counts = np.full(B, cap, dtype=np.int32)
+    rows[1, 40, 2] = -0.3                                        # a reverse row: bit 0
+    rows[3, 11, 6] = np.inf                                      # a non-finite x: bit 1
+    rows[3, 70, 2] = -1.0                                        # and a reverse row: both bits
+    rows[4, 60, 7] = np.nan                                      # past the count: not seen
+    counts[4] = 60
+    follower = tk.Pursuit(settle_rows=20)
+    P = tk.sample_perturbations(B, K, seed=1)
+    res = tk.rollouts(torch.tensor(rows, device="cuda:0"), torch.tensor(counts, device="cuda:0"), follower, P, time_step=DT, executed=True)
+    torch.cuda.synchronize()
+    assert res["route_status"].tolist() == [0, 1, 0, 3, 0]
+    for b in (1, 3):
+        assert torch.isnan(res["stats"][b]).all() and (res["stat_rows"][b] == -1).all() and (res["counts"][b * K:(b + 1) * K] == 0).all()
+        assert torch.isnan(res["worst"][b]) and int(res["worst_rollout"][b]) == -1 and int(res["n_unfinished"][b]) == 0
+    tally = Tally()
+    compare(res, rows, counts, follower, P, executed=True, tally=tally)
+    print(f"status bits among good routes: {tally}")
+    tally.check()
+    assert tally.n == 3 * K
+
+
+def test_saturating_drive(torch_mod):
+    """A straight line at 8 ft/s against a 6 ft/s wheel limit, started on it: the command is (8, 8) at every step before
+    arrival, so each of them is saturated, and (0, 0) from arrival on, so none is: saturated rows = arrived step.  The
+    robot runs at 6 ft/s and arrives in the settle rows."""
+    torch = torch_mod
+    tk = trk()
+    n, K = 150, 4
+    rows = np.zeros((1, n, 8))
+    t = np.arange(n) * DT
+    rows[0, :, 0], rows[0, :, 1], rows[0, :, 2], rows[0, :, 6], rows[0, :, 7] = t, 8.0 * t, 8.0, 1.0 + 8.0 * t, -2.0
+    follower = tk.Pursuit(settle_rows=80)
+    P = tk.sample_perturbations(1, K, seed=21, tau=0.0)
+    counts = np.array([n], dtype=np.int32)
+    res = tk.rollouts(torch.tensor(rows, device="cuda:0"), torch.tensor(counts, device="cuda:0"), follower, P, time_step=DT)
+    torch.cuda.synchronize()
+    tally = Tally()
+    refs = compare(res, rows, counts, follower, P, tally=tally)
+    sat, arr = res["saturated_rows"][0].tolist(), res["arrived_row"][0].tolist()
+    print(f"saturating drive: saturated rows {sat}, arrived steps {arr}; {tally}")
+    tally.check()
+    assert refs[0]["stat_rows"][0, 1] == refs[0]["stat_rows"][0, 2] and sat[0] == arr[0] and n < arr[0] < n + 80
+    assert abs(arr[0] - (8.0 * (n - 1) * DT - 0.05) / (6.0 * DT)) <= 2
+
+
+# ---- the C-ABI with a live context ---------------------------------------------------------------------------------------
+def test_null_outputs_and_abi_checks(torch_mod):
+    from vexautonomousplanner_amd import _lib
+    torch = torch_mod
+    tk = trk()
+    L = _lib.lib()
+    ctx = _lib.Context(0)
+    rng = np.random.default_rng(5)
+    for K, B in ((5, 9), (260, 2)):
+        cap, settle = 70, 10
+        rows = torch.tensor(synth_rows(rng, B, cap), device="cuda:0")
+        counts = torch.tensor(np.stack([rng.integers(20, cap + 1, B), np.zeros(B)], axis=1).astype(np.int32), device="cuda:0")
+        P = torch.tensor(tk.sample_perturbations(B, K, seed=K), device="cuda:0")
+        fs = tk.Pursuit(settle_rows=settle).as_struct()
+        cap_exec = cap + settle
+
+        def fresh():
+            i32 = lambda *s: torch.full(s, -7, dtype=torch.int32, device="cuda:0")
+            f64 = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device="cuda:0")
+            return [f64(B, K, 6), i32(B, K, 4), f64(B), f64(B), i32(B), i32(B), i32(B), i32(B), i32(B), f64(B * K, cap_exec, 8), i32(B * K, 2)]
+
+        def call(outs, skip=None, cap_exec=cap_exec, K=K, fs=fs, dt=DT, rows_ptr=None, shift=None):
+            p = [C.c_void_p(t.data_ptr() + (8 if shift == i else 0)) if i != skip else None for i, t in enumerate(outs)]
+            st = L.vap_pursuit_rollouts(ctx.handle, B, cap, C.c_void_p(rows_ptr or rows.data_ptr()), C.c_void_p(counts.data_ptr()), 2, dt,
+                                        C.byref(fs), K, 0, C.c_void_p(P.data_ptr()), *p[:9], cap_exec, p[9], p[10])
+            ctx.synchronize()
+            return st
+
+        full = fresh()
+        assert call(full) == _lib.VAP_OK
+        assert not (full[0][..., :2] == -7.0).any() and not any((full[i] == -7).any() for i in (4, 5, 6, 7, 8, 10))
+        for skip in range(11):
+            outs = fresh()
+            assert call(outs, skip=skip) == _lib.VAP_OK, skip
+            for i, (a, b) in enumerate(zip(outs, full)):
+                if i == skip:
+                    assert (a == -7).all(), (skip, "a skipped output was written")
+                else:
+                    assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (skip, i)
+        assert L.vap_pursuit_rollouts(ctx.handle, B, cap, C.c_void_p(rows.data_ptr()), C.c_void_p(counts.data_ptr()), 2, DT, C.byref(fs), K, 0,
+                                      C.c_void_p(P.data_ptr()), *[None] * 9, 0, None, None) == _lib.VAP_OK
+        ctx.synchronize()
+        # rows past a rollout's count are left as they were
+        ec = full[10][:, 0].cpu().numpy()
+        ex = full[9].cpu().numpy()
+        assert all((ex[i, ec[i]:] == -7.0).all() for i in range(0, B * K, 7))
+        INV = _lib.VAP_ERR_INVALID
+        assert call(fresh(), cap_exec=cap + settle - 1) == INV and b"cap_exec" in L.vap_last_error()
+        assert call(fresh(), rows_ptr=rows.data_ptr() + 8) == INV and b"16-byte aligned" in L.vap_last_error()
+        assert call(fresh(), shift=0) == INV and b"16-byte aligned" in L.vap_last_error()       # stats
+        assert call(fresh(), shift=9) == INV and b"16-byte aligned" in L.vap_last_error()       # executed rows
+        assert call(fresh(), K=0) == INV and call(fresh(), K=4097) == INV and call(fresh(), dt=0.0) == INV
+        bad = tk.Pursuit(settle_rows=settle).as_struct()
+        bad.lookahead = 0.0
+        assert call(fresh(), fs=bad) == INV
+        bad.lookahead, bad.min_speed = 0.75, -1.0
+        assert call(fresh(), fs=bad) == INV
+    # B = 0 is a no-op
+    assert L.vap_pursuit_rollouts(ctx.handle, 0, 0, None, None, 2, DT, C.byref(fs), 4, 0, None, *[None] * 9, 0, None, None) == _lib.VAP_OK
+    e = tk.rollouts(torch.zeros((0, 16, 8), dtype=torch.float64, device="cuda:0"), torch.zeros((0, 2), dtype=torch.int32, device="cuda:0"),
+                    tk.Pursuit(), tk.sample_perturbations(0, 4))
+    assert e["stats"].shape == (0, 4, 6) and e["stat_rows"].shape == (0, 4, 4) and e["n_unfinished"].shape == (0,)
+    ctx.close()
+
+
+def test_host_input_single_trajectory_and_out(torch_mod):
+    torch = torch_mod
+    tk = trk()
+    rng = np.random.default_rng(8)
+    rows = synth_rows(rng, 3, 90)
+    counts = np.array([90, 60, 80], dtype=np.int32)
+    follower = tk.Pursuit(settle_rows=5)
+    P = tk.sample_perturbations(3, 4, seed=2)
+    dev = tk.rollouts(torch.tensor(rows, device="cuda:0"), torch.tensor(counts, device="cuda:0"), follower, P)
+    bufs = {}
+    host = tk.rollouts(rows, counts, follower, P, out=bufs)
+    torch.cuda.synchronize()
+    same_bits(dev, host)
+    keep = bufs["stats"].data_ptr()
+    tk.rollouts(rows, counts, follower, P, out=bufs)
+    assert bufs["stats"].data_ptr() == keep
+    sb = {}
+    one = tk.rollouts(rows[1, :60], None, follower, P[1], executed=True, out=sb)
+    torch.cuda.synchronize()
+    assert set(sb) == {"stats", "stat_rows", "worst", "mean", "worst_rollout", "worst_row", "n_exceeding", "n_unfinished", "route_status",
+                       "rows", "counts"}
+    assert one["stats"].shape == (4, 6) and one["worst"].dim() == 0 and one["rows"].shape == (4, 65, 8) and one["arrived_row"].shape == (4,)
+    np.testing.assert_array_equal(bits(one, ("stats",))["stats"], bits(dev, ("stats",))["stats"][1])
+    assert (one["counts"][:, 0] == 65).all() and one["n_unfinished"].dim() == 0
+    # a RAMSETE call through the same function is what it was
+    r = tk.rollouts(rows, counts, tk.Follower(), P)
+    assert r["stat_rows"].shape == (3, 4, 2) and "n_unfinished" not in r and "max_heading_error" in r
+
+
+# ---- search.refine with a Pursuit ----------------------------------------------------------------------------------------
+def test_refine_with_a_pursuit_follower(torch_mod):
+    from vexautonomousplanner_amd import footprint as fp, search
+    from vexautonomousplanner_amd.batch import BatchedTrajectoryGenerator
+    torch = torch_mod
+    tk = trk()
+    gen = BatchedTrajectoryGenerator(0, "f32")
+    seed = np.array([[-4, 0], [-2, 1], [0, -1], [2, 1], [4, 0]], dtype=np.float64)
+    scene = fp.Scene(field=(-6.0, -6.0, 6.0, 6.0))
+    cfg = search.SearchConfig(candidates=64, elites=8, iterations=3, alpha=0.7)
+    P = tk.sample_perturbations(1, 4, seed=6)[0]
+
+    def run(follower, records):
+        return gen.refine(seed, 0.5, fp.rectangle(18, 18), scene, dd=0.005, dt=DT, capacity=4096, capacity_rows=1024, config=cfg,
+                          follower=follower, perturbations=records)
+
+    a, b = run(tk.Pursuit(), P), run(tk.Pursuit(), P)
+    torch.cuda.synchronize()
+    h = a["history"].cpu().numpy()
+    cost, unf = a["cost"].cpu().numpy(), a["n_unfinished"].cpu().numpy()
+    print(f"refine with Pursuit: history {h[0].tolist()}, {int((unf > 0).sum())} of 64 candidates with an unfinished rollout")
+    assert h.shape == (1, 3) and not np.isnan(h).any() and (np.diff(h, axis=1) <= 0).all() and np.isfinite(h[0, -1])
+    assert np.isinf(cost[unf > 0]).all() and cost.shape == unf.shape == (1, 64)
+    for k in a:
+        x, y = a[k].cpu().numpy(), b[k].cpu().numpy()
+        assert x.dtype == y.dtype and np.array_equal(x.view(np.uint8), y.view(np.uint8)), k
+    # a drive at half gain never arrives without settle rows: every candidate costs +inf, and nothing becomes the best
+    slow = np.array([tk.NOMINAL, tk.NOMINAL])
+    slow[1, 3:5] = 0.5
+    c = run(tk.Pursuit(settle_rows=0), slow)
+    torch.cuda.synchronize()
+    assert (c["n_unfinished"] > 0).all() and torch.isinf(c["cost"]).all() and torch.isinf(c["best_cost"]).all()
+    assert torch.isinf(c["history"]).all() and not bool(c["feasible"].any())

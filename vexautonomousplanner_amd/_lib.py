@@ -70,7 +70,7 @@ EXPORTS = (
     "vap_grid_distances", "vap_route_limits", "vap_velocity_pass_limits", "vap_time_insert_waits", "vap_fit_ex",
     "vap_profile_routes", "vap_time_profile_routes", "vap_time_insert_events", "vap_limit_rows_dtype",
     "vap_closest_points", "vap_route_closest", "vap_footprint_clearance", "vap_footprint_conflicts",
-    "vap_tracking_rollouts", "vap_search_sample", "vap_search_update", "vap_plan_grid", "vap_plan_seeds",
+    "vap_tracking_rollouts", "vap_pursuit_rollouts", "vap_search_sample", "vap_search_update", "vap_plan_grid", "vap_plan_seeds",
     "vap_plan_occupancy", "vap_plan_seeds_occupied", "vap_plan_travel", "vap_plan_order",
     "vap_routine_timeline", "vap_plan_order_timed", "vap_velocity_conditioning",
 )
@@ -86,6 +86,12 @@ class FollowerStruct(C.Structure):
     """vap_follower (include/vap.h)."""
     _fields_ = [("track_width", C.c_double), ("b", C.c_double), ("zeta", C.c_double), ("wheel_speed_max", C.c_double),
                 ("tolerance", C.c_double), ("n_substeps", C.c_int), ("settle_rows", C.c_int)]
+
+
+class PursuitStruct(C.Structure):
+    """vap_pursuit (include/vap.h)."""
+    _fields_ = [("track_width", C.c_double), ("lookahead", C.c_double), ("min_speed", C.c_double), ("arrive_tolerance", C.c_double),
+                ("wheel_speed_max", C.c_double), ("tolerance", C.c_double), ("n_substeps", C.c_int), ("settle_rows", C.c_int)]
 
 
 class SearchWeights(C.Structure):
@@ -195,6 +201,8 @@ def lib():
     L.vap_footprint_conflicts.argtypes = [vp, C.c_int, C.c_int, C.c_double] + side + side + [vp] * 8
     L.vap_tracking_rollouts.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_double, C.POINTER(FollowerStruct), C.c_int,
                                         C.c_int, vp] + [vp] * 7 + [C.c_long, vp, vp]
+    L.vap_pursuit_rollouts.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_double, C.POINTER(PursuitStruct), C.c_int,
+                                       C.c_int, vp] + [vp] * 9 + [C.c_long, vp, vp]
     L.vap_search_sample.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]
     L.vap_search_update.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double] + [vp] * 5 + \
         [C.POINTER(SearchWeights), C.c_int, C.c_double, C.c_double, C.c_double] + [vp] * 10 + [C.c_int, C.c_uint32]

@@ -488,7 +488,9 @@ class BatchedTrajectoryGenerator:
     def tracking_rollouts(self, tp, follower, perturbations, **kw):
         """Closed-loop tracking rollouts along the rows of ``tp`` — the dict ``time_profile`` or ``insert_waits``
         returned — under ``perturbations`` (vap_tracking_rollouts on this generator's context and torch's current stream;
-        see tracking.rollouts for time_step, executed, out and the returned dict).  ``follower``: a tracking.Follower."""
+        see tracking.rollouts for time_step, executed, out and the returned dict).  ``follower``: a tracking.Follower
+        (RAMSETE, vap_tracking_rollouts) or a tracking.Pursuit (pure pursuit, vap_pursuit_rollouts; slot 7 of a record is
+        then the rollout's lookahead)."""
         from . import tracking
         if tp["rows"].device != self.device:
             raise ValueError(f"rows must be on {self.device}")

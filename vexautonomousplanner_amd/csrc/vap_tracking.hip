@@ -27,13 +27,12 @@
 #include <cstdint>
 
 #include "vap_internal.h"
+#include "vap_track_common.h"
 
 namespace vap {
 
-constexpr int kTrackThreads = 256;
 constexpr int kTrackRows = 512;        // staged rows per LDS buffer, over all routes of the workgroup
 constexpr int kTrackTileMax = 64;      // rows of one route per tile, at most
-constexpr double kPi = 3.14159265358979323846;
 
 struct TrackArgs {
     const double *rows;       // [B][cap][8]
@@ -53,42 +52,6 @@ struct TrackArgs {
     double *part_e;           // K > 256: [B][K] max e_pos (row < 0: takes no part)
     int *part_row;
     int R, tile, wpr;         // routes per workgroup, rows per tile, workgroups per route
-};
-
-// ((a + pi) mod 2 pi) - pi with the floored mod (MPG:560-562); fmod is exact
-__device__ __forceinline__ double track_wrap(double a)
-{
-    double m = fmod(a + kPi, 2.0 * kPi);
-    if (m < 0.0) m += 2.0 * kPi;
-    return m - kPi;
-}
-
-__device__ __forceinline__ double track_sinc(double x, double sin_x)
-{
-    return fabs(x) < 1e-4 ? 1.0 - x * x / 6.0 : sin_x / x;
-}
-
-// a route's rollouts in ascending k: worst (a strictly larger error replaces: the smallest k stays), running sum, count
-// above the tolerance
-struct TrackSummary {
-    double worst = -INFINITY, sum = 0.0;
-    int k = -1, row = -1, cnt = 0, nex = 0;
-    __device__ void take(double e, int r, int kk, double tol)
-    {
-        if (r < 0) return;
-        if (e > worst) { worst = e; k = kk; row = r; }
-        sum += e;
-        cnt++;
-        nex += e > tol ? 1 : 0;
-    }
-    __device__ void store(const TrackArgs &g, int b) const
-    {
-        if (g.worst) g.worst[b] = cnt ? worst : NAN;
-        if (g.mean) g.mean[b] = cnt ? sum / (double)cnt : NAN;
-        if (g.worst_rollout) g.worst_rollout[b] = k;
-        if (g.worst_row) g.worst_row[b] = row;
-        if (g.n_exceeding) g.n_exceeding[b] = nex;
-    }
 };
 
 template <bool EXEC>
@@ -122,8 +85,7 @@ __global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g
     const size_t gi = (size_t)b * g.K + k;            // flattened (b, k)
 
     // the rollout's constants and start state
-    double gl = 1.0, gr = 1.0, tts = 1.0, a = 1.0;
-    double x = 0.0, y = 0.0, phi = 0.0, wl = 0.0, wr = 0.0;
+    TrackPlant pl;
     bool valid = false;
     if (inside && n > 0) {
         const double *p = g.perturb + (g.shared ? (size_t)k : gi) * 8;
@@ -135,19 +97,19 @@ __global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g
         if (valid) {
             const double *row0 = g.rows + (size_t)b * (size_t)g.cap * 8;
             const double v0 = row0[2], w0 = -row0[5];
-            x = row0[6] + p01.x;
-            y = row0[7] + p01.y;
-            phi = -row0[4] + p23.x;
-            wl = v0 - w0 * g.T / 2.0;
-            wr = v0 + w0 * g.T / 2.0;
-            gl = p23.y;
-            gr = p45.x;
-            tts = g.T * p45.y;
-            a = tau == 0.0 ? 1.0 : 1.0 - exp(-g.h / tau);
+            pl.x = row0[6] + p01.x;
+            pl.y = row0[7] + p01.y;
+            pl.phi = -row0[4] + p23.x;
+            pl.wl = v0 - w0 * g.T / 2.0;
+            pl.wr = v0 + w0 * g.T / 2.0;
+            pl.gl = p23.y;
+            pl.gr = p45.x;
+            pl.tts = g.T * p45.y;
+            pl.a = tau == 0.0 ? 1.0 : 1.0 - exp(-g.h / tau);
         }
     }
     const int my_total = valid ? n + g.settle : 0;
-    double maxe = -INFINITY, maxey = -INFINITY, maxeph = -INFINITY, dist = 0.0, vprev = 0.0;
+    double maxe = -INFINITY, maxey = -INFINITY, maxeph = -INFINITY;
     int mrow = -1, nsat = 0;
     double *erow = EXEC && valid ? g.exec_rows + gi * (size_t)g.cap_exec * 8 : nullptr;
 
@@ -211,26 +173,17 @@ __global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g
             const double vr = q[0], phr = -q[R], wref = -q[2 * R], xr = q[3 * R], yr = q[4 * R];
             // 1. errors in the body frame
             double sp, cp;
-            sincos(phi, &sp, &cp);
-            const double dx = xr - x, dy = yr - y;
+            sincos(pl.phi, &sp, &cp);
+            const double dx = xr - pl.x, dy = yr - pl.y;
             const double ex = cp * dx + sp * dy, ey = cp * dy - sp * dx;
-            const double eph = track_wrap(phr - phi);
+            const double eph = track_wrap(phr - pl.phi);
             const double epos = hypot(ex, ey);
             // 2. statistics
             if (epos > maxe) { maxe = epos; mrow = r; }
             if (fabs(ey) > maxey) maxey = fabs(ey);
             if (fabs(eph) > maxeph) maxeph = fabs(eph);
             // 3. the executed row
-            if (EXEC) {
-                const double v = (gl * wl + gr * wr) / 2.0;
-                const double om = (gr * wr - gl * wl) / tts;
-                double2 *o = (double2 *)(erow + (size_t)r * 8);
-                o[0] = make_double2((double)r * g.dt, dist);
-                o[1] = make_double2(v, r > 0 ? (v - vprev) / g.dt : 0.0);
-                o[2] = make_double2(-track_wrap(phi), -om);
-                o[3] = make_double2(x, y);
-                vprev = v;
-            }
+            if (EXEC) pl.write_row(erow, r, g.dt);
             // 4. RAMSETE
             double se, ce;
             sincos(eph, &se, &ce);
@@ -239,29 +192,9 @@ __global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g
             const double wc = wref + kk * eph + g.b * vr * track_sinc(eph, se) * ey;
             double cl = vc - wc * g.T / 2.0, cr = vc + wc * g.T / 2.0;
             // 5. saturation, keeping c_L : c_R
-            const double mx = fmax(fabs(cl), fabs(cr));
-            if (mx > g.wmax) {
-                const double scale = g.wmax / mx;
-                cl *= scale;
-                cr *= scale;
-                nsat++;
-            }
+            if (track_saturate(cl, cr, g.wmax)) nsat++;
             // 6. substeps: first-order wheel lag, then the exact arc
-#pragma unroll 1
-            for (int s = 0; s < g.nsub; s++) {
-                wl += (cl - wl) * a;
-                wr += (cr - wr) * a;
-                const double v = (gl * wl + gr * wr) / 2.0;
-                const double om = (gr * wr - gl * wl) / tts;
-                const double u = om * g.h / 2.0;
-                double sa, ca;
-                sincos(phi + u, &sa, &ca);
-                const double d = v * g.h * track_sinc(u, sin(u));
-                x += d * ca;
-                y += d * sa;
-                phi += om * g.h;
-                dist += fabs(d);
-            }
+            pl.advance(cl, cr, g.nsub, g.h);
         }
         if (more) store((ti + 1) & 1);
         __syncthreads();
@@ -273,8 +206,8 @@ __global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g
         double fpos = NAN, fphi = NAN;
         if (have) {
             const double *ql = g.rows + ((size_t)b * (size_t)g.cap + (size_t)(n - 1)) * 8;
-            fpos = hypot(ql[6] - x, ql[7] - y);
-            fphi = fabs(track_wrap(-ql[4] - phi));
+            fpos = hypot(ql[6] - pl.x, ql[7] - pl.y);
+            fphi = fabs(track_wrap(-ql[4] - pl.phi));
         }
         if (g.stats) {
             double2 *o = (double2 *)(g.stats + gi * 6);

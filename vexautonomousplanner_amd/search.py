@@ -252,8 +252,9 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
       others         the dict ``time_profile`` / ``insert_waits`` returned for the partner's routines (same dt): every
                      candidate is checked against all of them (``footprint.conflicts``; ``others_footprint`` default the
                      same robot); the margin is config.weights.conflict_margin
-      follower, perturbations   a tracking.Follower and (K, 8) or (R * N, K, 8) records: the worst tracking error of every
-                     candidate's rollouts enters the cost above config.weights.tracking_tolerance
+      follower, perturbations   a tracking.Follower or tracking.Pursuit and (K, 8) or (R * N, K, 8) records: the worst
+                     tracking error of every candidate's rollouts enters the cost above config.weights.tracking_tolerance;
+                     with a Pursuit a candidate with a rollout that never arrives (n_unfinished > 0) has the term +inf
       config         a SearchConfig
       first_problem  the number of problem 0 in the random stream: R = 1 with first_problem = r draws what problem r of a
                      larger call draws
@@ -262,7 +263,7 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
     device tensors: best_waypoints (R, W, 2), best_cost (R,) (+inf: no candidate ever had a finite cost), best_terms (R, 4)
     = duration, length, violation, candidate index of the best, feasible (R,) bool, history (R, iterations) (the best cost
     after each iteration, non-increasing), n_feasible (R, iterations), mean, sigma (R, W, 2), and the last iteration's cost
-    (R, N) and order (R, N).
+    (R, N) and order (R, N); with a tracking.Pursuit also the last iteration's n_unfinished (R, N).
 
     Plain-node paths only: routes with reverse or turn nodes are out of this search's scope."""
     from . import footprint as fp
@@ -292,6 +293,8 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
     if perturbations is not None and not isinstance(perturbations, torch.Tensor):
         perturbations = torch.as_tensor(np.ascontiguousarray(perturbations, dtype=np.float64), device=dev)
     prof, tp, clr, conf, trk, upd = None, {}, {}, {}, {}, {}
+    pursuit = isinstance(follower, tracking.Pursuit)
+    inf = torch.full((), float("inf"), dtype=torch.float64, device=dev)
     kw = {"samples": samples} if samples is not None else {"dd": dd, "capacity": capacity}
     for it in range(iters):
         sample(mean, sigma, N, seed=cfg.seed, iteration=it, first_problem=first_problem, best_waypoints=best_wp,
@@ -306,11 +309,15 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
             terms["conflict_clearance"] = conf["min_clearance"]
         if follower is not None:
             tracking.rollouts(tp["rows"], tp["counts"], follower, perturbations, time_step=dt, out=trk, ctx=gen.ctx)
-            terms["tracking_worst"] = trk["worst"]
+            # a pure-pursuit candidate whose rollouts do not all arrive is never an elite: its tracking term is +inf
+            terms["tracking_worst"] = torch.where(trk["n_unfinished"] > 0, inf, trk["worst"]) if pursuit else trk["worst"]
         update(wp, R, weights=wts, counts=tp["counts"], time_step=dt, meta=prof["meta"], flags=prof["flags"], mean=mean,
                sigma=sigma, elites=cfg.elites, alpha=cfg.alpha, sigma_min=cfg.sigma_min, sigma_max=cfg.sigma_max,
                best_cost=best_cost, best_waypoints=best_wp, best_terms=best_terms, history=history, iteration=it,
                n_feasible=n_feas[it], out=upd, ctx=gen.ctx, **terms)
-    return {"best_waypoints": best_wp, "best_cost": best_cost, "best_terms": best_terms,
-            "feasible": torch.isfinite(best_cost) & (best_terms[:, 2] == 0), "history": history, "n_feasible": n_feas.t(),
-            "mean": mean, "sigma": sigma, "cost": upd["cost"].view(R, N), "order": upd["order"]}
+    out = {"best_waypoints": best_wp, "best_cost": best_cost, "best_terms": best_terms,
+           "feasible": torch.isfinite(best_cost) & (best_terms[:, 2] == 0), "history": history, "n_feasible": n_feas.t(),
+           "mean": mean, "sigma": sigma, "cost": upd["cost"].view(R, N), "order": upd["order"]}
+    if pursuit:
+        out["n_unfinished"] = trk["n_unfinished"].view(R, N)
+    return out

@@ -10,6 +10,11 @@ and, with ``executed=True``, the executed rows in the time-profile layout, which
 The model, step by step, is the header's: reference pose (x, y) = columns 6, 7, phi = -heading, v = column 2,
 omega = -angular velocity; errors in the body frame; RAMSETE; wheel-speed saturation that keeps the curvature; a
 first-order wheel lag and the exact arc per substep.  Units: feet, seconds, radians.
+
+A second follower, pure pursuit (``Pursuit``, vap_pursuit_rollouts), goes through the same ``rollouts``: it is indexed by
+where the robot is on the path, reads only the polyline (columns 6, 7) and the speeds (column 2), and takes a record's
+slot 7 as that rollout's lookahead, so one call sweeps perturbations x lookaheads (``lookahead_sweep``).  It does not
+execute reverse legs (``route_status`` bit 0), in-place turns or dwells.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -55,6 +60,45 @@ class Follower:
                                    float(self.tolerance), int(self.n_substeps), int(self.settle_rows))
 
 
+@dataclass
+class Pursuit:
+    """vap_pursuit: the robot's track width (ft), the lookahead along the path's chord length (ft; a record's slot 7
+    overrides it per rollout), the speed the command never falls below before arrival (ft/s), the distance to the last
+    point at which the robot has arrived (ft), the wheel speed limit (ft/s), the cross-track error (ft) above which a
+    rollout counts in ``n_exceeding``, the integration substeps per row and the rows past the plan's end the robot is
+    given to arrive (a lagging drive arrives later than the plan)."""
+    track_width: float = 1.0
+    lookahead: float = 0.75
+    min_speed: float = 0.1
+    arrive_tolerance: float = 0.05
+    wheel_speed_max: float = 6.0
+    tolerance: float = 0.25
+    n_substeps: int = 2
+    settle_rows: int = 150
+
+    def validate(self):
+        for name in ("track_width", "lookahead", "wheel_speed_max"):
+            v = float(getattr(self, name))
+            if not (v > 0 and np.isfinite(v)):
+                raise ValueError(f"Pursuit.{name} must be positive and finite (got {v!r})")
+        for name in ("min_speed", "arrive_tolerance"):
+            v = float(getattr(self, name))
+            if not (v >= 0 and np.isfinite(v)):
+                raise ValueError(f"Pursuit.{name} must be >= 0 and finite (got {v!r})")
+        if np.isnan(float(self.tolerance)):
+            raise ValueError("Pursuit.tolerance is NaN")
+        if int(self.n_substeps) != self.n_substeps or not 1 <= int(self.n_substeps) <= 16:
+            raise ValueError(f"Pursuit.n_substeps must be 1..16 (got {self.n_substeps!r})")
+        if int(self.settle_rows) != self.settle_rows or not 0 <= int(self.settle_rows) <= 10000:
+            raise ValueError(f"Pursuit.settle_rows must be 0..10000 (got {self.settle_rows!r})")
+        return self
+
+    def as_struct(self):
+        return _lib.PursuitStruct(float(self.track_width), float(self.lookahead), float(self.min_speed),
+                                  float(self.arrive_tolerance), float(self.wheel_speed_max), float(self.tolerance),
+                                  int(self.n_substeps), int(self.settle_rows))
+
+
 def sample_perturbations(B, K, pos_sigma=0.1, heading_sigma=0.05, gain_sigma=0.03, track_sigma=0.05, tau=0.05, seed=0,
                          nominal_first=True):
     """(B, K, 8) fp64 perturbation records drawn on the host with ``np.random.default_rng(seed)``: dx, dy ~ N(0,
@@ -82,7 +126,28 @@ def sample_perturbations(B, K, pos_sigma=0.1, heading_sigma=0.05, gain_sigma=0.0
     return p
 
 
+def lookahead_sweep(perturbations, lookaheads):
+    """The records of every perturbation x lookahead pair for a ``Pursuit`` call: ``perturbations`` (K, 8) or (B, K, 8)
+    and ``lookaheads`` (M,) feet (0: the follower's own) give (K * M, 8) or (B, K * M, 8) fp64 records, pair (k, m) at
+    k * M + m, slot 7 = lookaheads[m] and the other slots those of record k."""
+    p = np.asarray(perturbations, dtype=np.float64)
+    la = np.asarray(lookaheads, dtype=np.float64).reshape(-1)
+    if p.ndim not in (2, 3) or p.shape[-1] != 8:
+        raise ValueError(f"perturbations must be (K, 8) or (B, K, 8), got {p.shape}")
+    if la.size < 1 or not (np.isfinite(la).all() and (la >= 0).all()):
+        raise ValueError("lookaheads must be finite and >= 0")
+    if p.shape[-2] * la.size > MAX_ROLLOUTS:
+        raise ValueError(f"{p.shape[-2]} records x {la.size} lookaheads exceed {MAX_ROLLOUTS} rollouts per route")
+    out = np.repeat(p, la.size, axis=-2)
+    out[..., 7] = np.tile(la, p.shape[-2])
+    return out
+
+
 STAT_COLUMNS = ("max_error", "max_cross_track", "max_heading_error", "final_error", "final_heading_error")
+
+
+PURSUIT_STAT_COLUMNS = ("max_cross_track", "final_error", "arrival_time", "lookahead")
+PURSUIT_ROW_COLUMNS = ("max_row", "saturated_rows", "arrived_row", "closest_segment")
 
 
 def rollouts(rows, counts, follower, perturbations, time_step=0.01, executed=False, out=None, device=0, ctx=None):
@@ -91,7 +156,7 @@ def rollouts(rows, counts, follower, perturbations, time_step=0.01, executed=Fal
       rows           (B, capacity, 8) fp64 rows of time_profile / insert_waits — a device tensor (used in place) or a
                      host array (uploaded once); (n, 8) for a single trajectory
       counts         (B, k) int counts of that call (column 0 = rows), or (B,); None for a single trajectory
-      follower       a Follower
+      follower       a Follower (RAMSETE) or a Pursuit (pure pursuit; see below)
       perturbations  (B, K, 8) records per route, or (K, 8) shared by every route (``sample_perturbations``); a device
                      tensor or a host array
       time_step      the rows' time step in seconds (time_profile's dt)
@@ -105,9 +170,19 @@ def rollouts(rows, counts, follower, perturbations, time_step=0.01, executed=Fal
     Returns a dict of tensors: stats (B, K, 6) and its columns as views max_error, max_cross_track, max_heading_error,
     final_error, final_heading_error (B, K); stat_rows (B, K, 2) with views max_row and saturated_rows; per route (B,)
     worst, mean, worst_rollout, worst_row, n_exceeding.  A route without rows and an invalid record give NaN / -1 / 0.
-    A single trajectory gives (K, ...) and 0-d tensors.  Work runs on torch's current stream and is not synchronised."""
-    if not isinstance(follower, Follower):
-        raise TypeError("follower must be a tracking.Follower")
+    A single trajectory gives (K, ...) and 0-d tensors.  Work runs on torch's current stream and is not synchronised.
+
+    With a ``Pursuit`` (vap_pursuit_rollouts) slot 7 of a record is that rollout's lookahead (``lookahead_sweep``) and
+    the dict has: stats (B, K, 6) with views max_cross_track, final_error, arrival_time (NaN: never arrived), lookahead;
+    stat_rows (B, K, 4) with views max_row, saturated_rows, arrived_row (-1: never), closest_segment; per route worst,
+    mean, worst_rollout, worst_row, n_exceeding (over the cross-track error), n_unfinished (valid rollouts that never
+    arrived) and route_status (bit 0: a negative speed, bit 1: a non-finite x, y or v; such a route gives NaN / -1 / 0)."""
+    if isinstance(follower, Pursuit):
+        pursuit = True
+    elif isinstance(follower, Follower):
+        pursuit = False
+    else:
+        raise TypeError("follower must be a tracking.Follower or a tracking.Pursuit")
     follower.validate()
     time_step = float(time_step)
     if not (time_step > 0 and np.isfinite(time_step)):
@@ -122,9 +197,12 @@ def rollouts(rows, counts, follower, perturbations, time_step=0.01, executed=Fal
     if not 1 <= K <= MAX_ROLLOUTS:
         raise ValueError(f"K = {K} rollouts per route (1..{MAX_ROLLOUTS})")
     cap_exec = cap + int(follower.settle_rows)
-    shapes = {"stats": ((B, K, 6), torch.float64), "stat_rows": ((B, K, 2), torch.int32), "worst": ((B,), torch.float64),
+    shapes = {"stats": ((B, K, 6), torch.float64), "stat_rows": ((B, K, 4 if pursuit else 2), torch.int32), "worst": ((B,), torch.float64),
               "mean": ((B,), torch.float64), "worst_rollout": ((B,), torch.int32), "worst_row": ((B,), torch.int32),
               "n_exceeding": ((B,), torch.int32)}
+    if pursuit:
+        shapes["n_unfinished"] = ((B,), torch.int32)
+        shapes["route_status"] = ((B,), torch.int32)
     if executed:
         shapes["rows"] = ((B * K, cap_exec, 8), torch.float64)
         shapes["counts"] = ((B * K, 2), torch.int32)
@@ -132,6 +210,17 @@ def rollouts(rows, counts, follower, perturbations, time_step=0.01, executed=Fal
     res = {k: bufs[k] for k in shapes}
     ctx = context_for(dev, ctx)
     fs = follower.as_struct()
+    if pursuit:
+        _lib.check(ctx._L.vap_pursuit_rollouts(
+            ctx.handle, B, cap, ptr(rows), ptr(counts), int(counts.shape[1]), time_step, C.byref(fs), K, int(shared), ptr(pert),
+            ptr(res["stats"]), ptr(res["stat_rows"]), ptr(res["worst"]), ptr(res["mean"]), ptr(res["worst_rollout"]),
+            ptr(res["worst_row"]), ptr(res["n_exceeding"]), ptr(res["n_unfinished"]), ptr(res["route_status"]), cap_exec,
+            ptr(res.get("rows") if executed else None), ptr(res.get("counts") if executed else None)), "vap_pursuit_rollouts")
+        for i, name in enumerate(PURSUIT_STAT_COLUMNS):
+            res[name] = res["stats"][..., i]
+        for i, name in enumerate(PURSUIT_ROW_COLUMNS):
+            res[name] = res["stat_rows"][..., i]
+        return _single(res) if single else res
     _lib.check(ctx._L.vap_tracking_rollouts(
         ctx.handle, B, cap, ptr(rows), ptr(counts), int(counts.shape[1]), time_step, C.byref(fs), K, int(shared), ptr(pert),
         ptr(res["stats"]), ptr(res["stat_rows"]), ptr(res["worst"]), ptr(res["mean"]), ptr(res["worst_rollout"]),
@@ -141,8 +230,11 @@ def rollouts(rows, counts, follower, perturbations, time_step=0.01, executed=Fal
         res[name] = res["stats"][..., i]
     res["max_row"] = res["stat_rows"][..., 0]
     res["saturated_rows"] = res["stat_rows"][..., 1]
-    if single:
-        for k in list(res):
-            if k not in ("rows", "counts"):
-                res[k] = res[k][0]
+    return _single(res) if single else res
+
+
+def _single(res):
+    for k in list(res):
+        if k not in ("rows", "counts"):
+            res[k] = res[k][0]
     return res
