@@ -625,6 +625,57 @@ int vap_footprint_conflicts(vap_ctx *ctx, int pairing, int shift_rows, double ma
                             double *d_pair_clearance, int *d_pair_row, int *d_pair_first_row,
                             double *d_min_clearance, int *d_min_other, int *d_min_row, int *d_n_conflicts, int *d_first_row);
 
+/* ---- robot-to-robot clearance over a window of start shifts -------------------------------------------------------
+ * How long must I wait at this site, or how late must my partner start, for the two of us not to meet?  The call above
+ * answers for ONE shift_rows; this one returns, for every pair of routes, the clearance as a function of the start shift
+ * over a whole window, in one pass over rows that are packed once, and the first shift at which a route clears every other
+ * robot for a run of consecutive shifts.
+ *
+ *   sides, rows, counts, strides, footprints, pose (phi = -heading, columns 4, 6, 7), the polygon clearance, pairing
+ *             (VAP_CONFLICT_ALL_PAIRS: P = Bo; VAP_CONFLICT_MATCHED: P = 1) and footprint validation are
+ *             vap_footprint_conflicts' own.
+ *   shifts    window entry k = 0 .. n_shifts - 1 of A route a stands for the shift
+ *               s = shift_lo + base[a] + k * shift_step,   computed in 64 bits;
+ *             d_shift_base is a device int32 [Ba], or NULL for 0; shift_step >= 1.  As above, s is how many rows later
+ *             side O starts; a negative s means that A starts |s| rows after O.
+ *   instants  a valid pair (n_a > 0 and n_o > 0) at shift s is examined at t = min(0, s) .. max(n_a, n_o + s) - 1.  At
+ *             instant t, A's row is i = t and O's row is j = t - s.  An index outside its side's rows is treated by the
+ *             four bits of hold:
+ *               VAP_HOLD_A_FIRST (1)  i < 0 becomes 0          VAP_HOLD_A_LAST (2)  i >= n_a becomes n_a - 1
+ *               VAP_HOLD_O_FIRST (4)  j < 0 becomes 0          VAP_HOLD_O_LAST (8)  j >= n_o becomes n_o - 1
+ *             With a bit clear, an instant that needs it is not examined.  hold = 14 is exactly vap_footprint_conflicts'
+ *             horizon and parking: the table entry is then that call's d_pair_clearance at shift_rows = s, the same number.
+ *   table     d_table [Ba][P][n_shifts]: the smallest clearance over the examined instants.  A NaN clearance takes part
+ *             in nothing; the entry is NaN when no finite clearance was examined, and for an invalid pair.
+ *   blocked   shift k of a pair is blocked iff table < margin (NaN never blocks).
+ *             d_pair_safe [Ba][P]: the number of unblocked k; 0 for an invalid pair.
+ *             d_pair_first [Ba][P]: scan = +1: the smallest k such that k .. k + min_run - 1 all lie in the window and
+ *             are unblocked; scan = -1: the largest k such that k - min_run + 1 .. k do; -1 when there is none, and for
+ *             an invalid pair.  min_run >= 1.
+ *   per route shift k of route a is blocked iff any valid pair of a is blocked at k.  d_route_table [Ba][n_shifts]: the
+ *             minimum over its valid pairs' table entries (NaN ignored; NaN if there is none); d_route_first [Ba] and
+ *             d_route_safe [Ba] follow the pair rules.  A route with n_a = 0 gets NaN, -1, 0.  A route with rows but no
+ *             valid pair is blocked nowhere: first = 0 (scan +1) or n_shifts - 1 (scan -1) when min_run <= n_shifts, and
+ *             safe = n_shifts.
+ * Every output pointer may be NULL.  n_shifts < 1, shift_step < 1, min_run < 1, scan not +-1, hold outside 0..15, MATCHED
+ * with Ba != Bo, null rows or counts with B > 0, a negative capacity, a bad footprint: VAP_ERR_INVALID.  n_shifts above
+ * VAP_CONFLICT_SHIFTS_MAX, a capacity above INT_MAX: VAP_ERR_UNSUPPORTED.  Arguments are checked before the context is
+ * touched.  Ba = 0 or Bo = 0 is a no-op.  Works on the context's stream and does not synchronise.  Context scratch grows
+ * with (Ba cap_a + Bo cap_o) x 32 B (capacities rounded up to 64 rows) and with Ba (P + 1) n_shifts bits, never with pairs
+ * x rows or pairs x blocks x shifts.  Two calls on the same inputs give the same bits.  VAP_OPT_FOOTPRINT_CULL governs culling
+ * (block and row bounding circles before the exact pair); outputs are the same numbers either way.  Discrete at the rows'
+ * dt like the call above.  The row at which a minimum falls is not returned: call vap_footprint_conflicts at that shift. */
+enum { VAP_HOLD_A_FIRST = 1, VAP_HOLD_A_LAST = 2, VAP_HOLD_O_FIRST = 4, VAP_HOLD_O_LAST = 8 };
+#define VAP_CONFLICT_SHIFTS_MAX 4096
+int vap_conflict_shifts(vap_ctx *ctx, int pairing, int hold, double margin, int shift_lo, int shift_step, int n_shifts,
+                        const int *d_shift_base, int min_run, int scan,
+                        int Ba, long cap_a, const double *d_rows_a, const int *d_counts_a, int stride_a, int n_foot_a,
+                        const double *h_foot_a,
+                        int Bo, long cap_o, const double *d_rows_o, const int *d_counts_o, int stride_o, int n_foot_o,
+                        const double *h_foot_o,
+                        double *d_table, int *d_pair_first, int *d_pair_safe,
+                        double *d_route_table, int *d_route_first, int *d_route_safe);
+
 /* ---- closed-loop tracking rollouts of time-domain rows -----------------------------------------------------------
  * How far does the robot stray from a route when it DRIVES it?  The two clearance calls judge the nominal rows; the robot
  * feeds those rows (t, x, y, heading, v, omega: the columns trajectory_io.py writes into routes.h) to a path follower.

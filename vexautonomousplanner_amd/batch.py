@@ -485,6 +485,28 @@ class BatchedTrajectoryGenerator:
         return fp.conflicts(tp["rows"], tp["counts"], footprint, others["rows"], others["counts"], others_footprint,
                             ctx=self.ctx, **kw)
 
+    def conflict_shifts(self, tp, footprint, others, others_footprint=None, **kw):
+        """Robot-to-robot clearance of the rows of ``tp`` against the rows of ``others`` over a window of start shifts, and
+        the first shift at which each route of ``tp`` clears every other robot (vap_conflict_shifts on this generator's
+        context and torch's current stream; see footprint.shifts for margin, shift_lo, n_shifts, shift_step, base, hold,
+        pairing, min_run, scan, table, pairs, out, cull and the returned dict)."""
+        from . import footprint as fp
+        for d in (tp, others):
+            if d["rows"].device != self.device:
+                raise ValueError(f"rows must be on {self.device}")
+        return fp.shifts(tp["rows"], tp["counts"], footprint, others["rows"], others["counts"], others_footprint,
+                         ctx=self.ctx, **kw)
+
+    def earliest_start(self, tp, footprint, others, others_footprint=None, **kw):
+        """The fewest rows either side has to wait for the routes of ``tp`` to clear ``others`` (see footprint.
+        earliest_start for margin, max_delay_rows, who, min_run and the returned dict), on this generator's context."""
+        from . import footprint as fp
+        for d in (tp, others):
+            if d["rows"].device != self.device:
+                raise ValueError(f"rows must be on {self.device}")
+        return fp.earliest_start(tp["rows"], tp["counts"], footprint, others["rows"], others["counts"], others_footprint,
+                                 ctx=self.ctx, **kw)
+
     def tracking_rollouts(self, tp, follower, perturbations, **kw):
         """Closed-loop tracking rollouts along the rows of ``tp`` — the dict ``time_profile`` or ``insert_waits``
         returned — under ``perturbations`` (vap_tracking_rollouts on this generator's context and torch's current stream;

@@ -1,5 +1,6 @@
 """Robot-footprint clearance of time-domain rows (vap_footprint_clearance, include/vap.h), and robot-to-robot clearance
-between two batches of them (vap_footprint_conflicts, ``conflicts`` below).
+between two batches of them (vap_footprint_conflicts, ``conflicts`` below), also over a window of start shifts
+(vap_conflict_shifts: ``shifts`` and ``earliest_start``).
 
 Which candidate trajectories are drivable: does the robot's body stay on the field and off the field elements at every
 row?  The reference only previews the footprint (gui/path.py:764-809 PathWidget.draw_rect: the robot rectangle rotated to
@@ -20,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._call import buffers, context_for, dptr, ptr, time_rows
+from ._call import buffers, context_for, device_array, dptr, ptr, time_rows
 
 # gui/path.py:366-367: the 2000 px field image spans 12.1090395251 ft
 FIELD_FT = 12.1090395251
@@ -255,6 +256,113 @@ def conflicts(rows_a, counts_a, footprint_a, rows_o, counts_o, footprint_o=None,
         for k in list(res):
             res[k] = res[k][0]
     return res
+
+
+HOLD_ALL = _lib.HOLD_A_FIRST | _lib.HOLD_A_LAST | _lib.HOLD_O_FIRST | _lib.HOLD_O_LAST
+HOLD_CONFLICTS = _lib.HOLD_A_LAST | _lib.HOLD_O_FIRST | _lib.HOLD_O_LAST      # what ``conflicts`` does: 14
+SCANS = {"up": 1, "down": -1}
+
+
+def shifts(rows_a, counts_a, footprint_a, rows_o, counts_o, footprint_o=None, margin=0.0, shift_lo=0, n_shifts=1, shift_step=1,
+           base=None, hold=HOLD_CONFLICTS, pairing="all", min_run=1, scan="up", table=False, pairs=False, out=None, device=0,
+           ctx=None, cull=True):
+    """Robot-to-robot clearance as a function of the start shift (vap_conflict_shifts): ``conflicts`` for a whole window
+    of ``shift_rows`` in one pass over rows that are packed once, and the first shift at which a route of side A clears
+    every route of side O it is paired with.
+
+      rows_a .. footprint_o, margin, pairing, out, ctx, cull   as in ``conflicts``
+      shift_lo, n_shifts, shift_step   window entry k = 0 .. n_shifts - 1 stands for side O starting
+                         s = shift_lo + base[a] + k * shift_step rows later (negative: side A starts |s| rows later);
+                         n_shifts <= 4096
+      base               (Ba,) int, device or host: a per-route offset of the window; None = 0
+      hold               which side stays on the field outside its own rows: a mask of _lib.HOLD_A_FIRST (1), HOLD_A_LAST
+                         (2), HOLD_O_FIRST (4), HOLD_O_LAST (8).  14 (the default) is ``conflicts``' parking: the table is
+                         then its pair_clearance at shift_rows = s, the same numbers.  15 also keeps side A at its first
+                         pose while it waits to start
+      min_run, scan      "up": ``first`` is the smallest k with k .. k + min_run - 1 inside the window and unblocked (the
+                         clearance of every pair >= margin, or NaN); "down": the largest k with k - min_run + 1 .. k so
+      table              also return route_table (Ba, n_shifts): the smallest clearance over the route's pairs per shift
+      pairs              also return pair_table (Ba, P, n_shifts), pair_first and pair_safe (Ba, P)
+    Returns a dict of (Ba,) tensors: first (int32, -1: none), first_shift (int64: the shift s of ``first``; 0 where there is
+    none), n_safe (unblocked shifts of the window) and first_time (first_shift x the rows' time step; NaN where there is
+    none).  A route without rows gets -1 / 0; one with rows and no valid pair is blocked nowhere.  A single side-A
+    trajectory gives 0-d tensors.  Work runs on torch's current stream and is not synchronised."""
+    foot_a = _ccw_polygon(footprint_a, "footprint_a")
+    foot_o = foot_a if footprint_o is None else _ccw_polygon(footprint_o, "footprint_o")
+    if not isinstance(pairing, str) or pairing not in PAIRINGS:
+        raise ValueError(f"pairing must be 'all' or 'matched' (got {pairing!r})")
+    if not isinstance(scan, str) or scan not in SCANS:
+        raise ValueError(f"scan must be 'up' or 'down' (got {scan!r})")
+    shift_lo, n_shifts, shift_step, hold, min_run = int(shift_lo), int(n_shifts), int(shift_step), int(hold), int(min_run)
+    given = [r.device for r in (rows_a, rows_o) if isinstance(r, torch.Tensor)]
+    rows_a, counts_a, single, dev = time_rows(rows_a, counts_a, given[0] if given else None, device, "side A")
+    rows_o, counts_o, _, _ = time_rows(rows_o, counts_o, dev, device, "side O")
+    Ba, cap_a, Bo, cap_o = int(rows_a.shape[0]), int(rows_a.shape[1]), int(rows_o.shape[0]), int(rows_o.shape[1])
+    if pairing == "matched" and Ba != Bo:
+        raise ValueError(f"matched pairing needs as many routes on both sides (got {Ba} and {Bo})")
+    if isinstance(base, torch.Tensor) and base.device != dev:
+        raise ValueError(f"base is on {base.device}, the rows on {dev}")
+    base = device_array(base, dev, torch.int32)
+    if base is not None and tuple(base.shape) != (Ba,):
+        raise ValueError(f"base must be ({Ba},), got {tuple(base.shape)}")
+    P = 1 if pairing == "matched" else Bo
+    n = max(n_shifts, 0)
+    shapes = {"first": ((Ba,), torch.int32), "n_safe": ((Ba,), torch.int32)}
+    if table:
+        shapes["route_table"] = ((Ba, n), torch.float64)
+    if pairs:
+        shapes.update(pair_table=((Ba, P, n), torch.float64), pair_first=((Ba, P), torch.int32), pair_safe=((Ba, P), torch.int32))
+    res = buffers(out, shapes, dev)
+    ctx = context_for(dev, ctx)
+    ctx.set_option(_lib.OPT_FOOTPRINT_CULL, 1 if cull else 0)
+    want = lambda k: ptr(res[k]) if k in shapes else None
+    _lib.check(ctx._L.vap_conflict_shifts(
+        ctx.handle, PAIRINGS[pairing], hold, float(margin), shift_lo, shift_step, n_shifts, ptr(base), min_run, SCANS[scan],
+        Ba, cap_a, ptr(rows_a), ptr(counts_a), int(counts_a.shape[1]), len(foot_a), dptr(foot_a),
+        Bo, cap_o, ptr(rows_o), ptr(counts_o), int(counts_o.shape[1]), len(foot_o), dptr(foot_o),
+        want("pair_table"), want("pair_first"), want("pair_safe"), want("route_table"), ptr(res["first"]), ptr(res["n_safe"])),
+        "vap_conflict_shifts")
+    if Bo == 0:                                   # nothing to meet: the C-ABI call is a no-op
+        has = counts_a[:, 0] > 0
+        k = (0 if scan == "up" else n_shifts - 1) if min_run <= n_shifts else -1
+        res["first"].copy_(torch.where(has, k, -1))
+        res["n_safe"].copy_(torch.where(has, n_shifts, 0))
+        if table:
+            res["route_table"].fill_(float("nan"))
+    first = res["first"].to(torch.int64)
+    s = shift_lo + first * shift_step
+    if base is not None:
+        s = s + base.to(torch.int64)
+    res["first_shift"] = torch.where(first >= 0, s, torch.zeros_like(s))
+    t = res["first_shift"].to(torch.float64) * _time_step((rows_a, counts_a), (rows_o, counts_o))
+    res["first_time"] = torch.where(first >= 0, t, torch.full_like(t, float("nan")))
+    if single:
+        for k in list(res):
+            res[k] = res[k][0]
+    return res
+
+
+def earliest_start(rows_a, counts_a, footprint_a, rows_o, counts_o, footprint_o=None, margin=0.0, max_delay_rows=256, who="a",
+                   min_run=1, pairing="all", device=0, ctx=None, cull=True):
+    """How long must one side wait for the two not to meet?  Per route of side A the fewest rows of delay d in
+    0 .. max_delay_rows such that d .. d + min_run - 1 all keep every pair of the route at ``margin`` or more (``shifts``
+    with hold = 15: whoever waits stands at its first pose, whoever has finished at its last).
+
+      who   "o": side O starts d rows later (shifts 0 .. max_delay_rows, scanned up);
+            "a": side A waits d rows at its first pose (shifts -max_delay_rows .. 0, scanned down)
+    Returns a dict of (Ba,) tensors: delay_rows (int32, -1 where no such delay exists in the window) and delay_time
+    (delay_rows x the rows' time step, NaN where none).  max_delay_rows + 1 <= 4096."""
+    if who not in ("a", "o"):
+        raise ValueError(f"who must be 'a' or 'o' (got {who!r})")
+    D = int(max_delay_rows)
+    if D < 0:
+        raise ValueError(f"max_delay_rows must be >= 0 (got {max_delay_rows!r})")
+    r = shifts(rows_a, counts_a, footprint_a, rows_o, counts_o, footprint_o, margin=margin, shift_lo=0 if who == "o" else -D,
+               n_shifts=D + 1, hold=HOLD_ALL, pairing=pairing, min_run=min_run, scan="up" if who == "o" else "down",
+               device=device, ctx=ctx, cull=cull)
+    first = r["first"]
+    delay = first if who == "o" else torch.where(first >= 0, D - first, torch.full_like(first, -1))
+    return {"delay_rows": delay, "delay_time": r["first_time"].abs()}
 
 
 def _time_step(*sides):

@@ -6,7 +6,8 @@ routine the turn on the spot from the heading the robot arrives with to the head
 reference's own turn, MPG:319-346 and 487-507), the leg's rows at their place in time and distance, and the rows of the
 dwell at the site.  The result has the rows and counts of ``time_profile``, so it goes where those go: ``footprint.
 clearance`` (does the turning robot clear the post beside the site?), ``footprint.conflicts`` (a later leg against the
-partner at its real start time), ``tracking.rollouts`` and ``plan.occupancy``.
+partner at its real start time), ``tracking.rollouts`` and ``plan.occupancy``.  ``dwell_to_clear`` asks the question a
+crossing partner raises: how much longer must the robot stay at the previous site for the rest of the routine to clear it.
 
 Nothing here reads the device: the visiting order may stay a device tensor from ``plan.order`` to the chained rows.
 """
@@ -119,3 +120,51 @@ def chain(rows, counts, legs, dwell=None, start_heading=None, n_legs=None, const
     bad = (res["flags"] & _lib.FLAG_BAD_ROUTE) != 0
     res["duration"] = torch.where(bad, nan, res["counts"][:, 0].to(torch.float64) * dt)
     return res
+
+
+def dwell_to_clear(tl, slot, footprint, others_rows, others_counts, others_footprint=None, margin=0.0, max_delay_rows=256,
+                   min_run=1, device=0, ctx=None):
+    """The extra dwell that lets the rest of a routine clear the other robots (``footprint.earliest_start`` on the tails).
+
+      tl             what ``chain`` returned
+      slot           0 <= slot < M.  Everything from slot's turn block on, output row b = map[r, slot, 0], is delayed: the
+                     dwell goes to slot - 1 (for slot = 0 the routine starts that much later)
+      others_rows, others_counts, others_footprint   the other robots' rows on the timeline's clock and time step, as
+                     ``footprint.conflicts`` takes its side O; footprint None = the same as ``footprint``
+      margin, max_delay_rows, min_run   as in ``footprint.earliest_start``
+    Per routine the tail of its own rows from b, waiting at its first pose, is swept against every other robot's rows from
+    b on (one that has ended by b stands at its last row).  Returns (R,) seconds: (d + 0.5) dt for the fewest rows d that
+    clear every other robot, so that ``chain`` turns it into exactly d rows; NaN where no delay up to max_delay_rows does,
+    and for a routine that does not use the slot.  One routine at a time, all on the device: nothing is read on the host."""
+    from . import footprint as fp
+    rows, counts, at = tl["rows"], tl["counts"], tl["map"]
+    R, cap = int(rows.shape[0]), int(rows.shape[1])
+    slot = int(slot)
+    if not 0 <= slot < int(at.shape[1]):
+        raise ValueError(f"slot must be in [0, {int(at.shape[1])}) (got {slot})")
+    o_rows, o_counts, _, dev = time_rows(others_rows, others_counts, rows.device, device, "others")
+    Bo, cap_o = int(o_rows.shape[0]), int(o_rows.shape[1])
+    dt = fp._time_step((rows, counts), (o_rows, o_counts))
+    out = torch.full((R,), float("nan"), dtype=torch.float64, device=dev)
+    if cap == 0:
+        return out
+    ar_a = torch.arange(cap, device=dev)
+    ar_o = torch.arange(max(cap_o, 1), device=dev)
+    n_o = o_counts[:, 0].clamp(0, cap_o).to(torch.int64)
+    for r in range(R):
+        b = at[r, slot, 0].to(torch.int64)
+        used = b >= 0
+        b = b.clamp(min=0)
+        tail = rows[r].index_select(0, (b + ar_a).clamp(max=cap - 1)).unsqueeze(0)
+        n_tail = torch.where(used, (counts[r, 0].to(torch.int64) - b).clamp(min=0), torch.zeros_like(b)).to(torch.int32).reshape(1, 1)
+        if Bo and cap_o:
+            j = torch.minimum(b + ar_o[None, :], (n_o - 1).clamp(min=0)[:, None])
+            o_tail = torch.gather(o_rows, 1, j[:, :, None].expand(Bo, cap_o, 8))
+            o_n = torch.where(n_o > 0, (n_o - b).clamp(min=1), torch.zeros_like(n_o)).to(torch.int32)
+        else:
+            o_tail, o_n = o_rows, o_counts[:, 0]
+        e = fp.earliest_start(tail, n_tail, footprint, o_tail, o_n, others_footprint, margin=margin, max_delay_rows=max_delay_rows,
+                              who="a", min_run=min_run, device=device, ctx=ctx)
+        d = e["delay_rows"][0]
+        out[r] = torch.where(d >= 0, (d.to(torch.float64) + 0.5) * dt, torch.full_like(dt, float("nan")))
+    return out
