@@ -1161,6 +1161,76 @@ int vap_plan_order_timed(vap_ctx *ctx, int R, int P, int L, int capacity, double
                          const int *d_budget_rows, int end, const uint32_t *d_before, int *d_order, int *d_n_visited,
                          int *d_rows_total, int *d_arrival_rows, double *d_value_total, uint32_t *d_flags);
 
+/* ---- drive limits: curve caps for the velocity pass, and an audit of time-domain rows -------------------------------------------
+ * vap_constraints carries friction_coef and max_jerk, and forward_backward_pass reads neither; the reference also computes
+ * curvature_derivs (MPG:178-186) for a curvature-rate cap, limit_velocity_by_ang_accel (MPG:41-50), that it comments out of
+ * both sweeps (MPG:215-220, 276-281), and the wheel speeds (MPG:594-599) and wheel accelerations (MPG:612-616) of every
+ * time-domain row, which it drops on return.  The two calls below use them; no other entry point changes.
+ *
+ * vap_curve_caps writes, per sample, min(incoming cap, lateral cap, curvature-rate cap) into a row that
+ * vap_velocity_pass_limits takes as d_vcap.
+ *   rows      N = meta[b][3] (taken as 0 below 0 and as S above S), dd = meta[b][2], as vap_velocity_conditioning.
+ *             d_curvature [B][S] in `dt`, or NULL for VAP_F32 with VAP_RECURRENCE_F64: the fp64 rows the last sampling call
+ *             of this shape left on the context (VAP_ERR_INVALID where it holds none).  d_vcap_in / d_vcap_out [B][S] of type
+ *             vap_limit_rows_dtype(ctx, dt); d_vcap_in NULL = c->max_vel everywhere; the two may be the same row (in place,
+ *             e.g. behind vap_route_limits).  Row addresses that are not 16-byte aligned are moved element by element.
+ *   arithmetic  fp64 on widened inputs, IEEE divisions and square roots, no contraction; an fp32 result is rounded to nearest.
+ *   lateral   cap_lat = sqrt(A / |k|) where |k| > 0, else +inf; A = lateral_acc_max (ft/s^2; friction_coef * g).
+ *   rate      dk_0 = (k_1 + k_0) / dd, dk_(N-1) = (k_(N-1) + k_(N-2)) / dd, dk_i = (k_(i+1) - k_(i-1)) / (2 dd) between.  The
+ *             two PLUS signs are the reference's own (MPG:180, 182; a quirk: the ends hold a mean curvature over dd / 2, not
+ *             a difference) and are kept.  cap_ang = max_vel if |dk| < 1e-9, else min(sqrt(alpha / |dk|), max_vel), the left
+ *             operand unless the right is strictly smaller (MPG:45-50); alpha = angular_acc_max (rad/s^2; the reference's
+ *             max_angular_accel is 2 max_acc / track_width, MPG:82).  N < 2, or alpha = +inf, gives no cap (+inf).
+ *   output    out_i = min(in_i, cap_lat, cap_ang) for i < N in Python's order: in_i, unless cap_lat is strictly smaller, then
+ *             that, unless cap_ang is strictly smaller.  A NaN curvature gives out_i = NaN (the velocity pass flags such a
+ *             path).  Samples i >= N receive in_i.  The velocity pass takes entry 0 and the end sample from start_vel / end_vel.
+ *   count     d_n_bound [B][2] int32, optional: the samples i < N with cap_lat < in_i, and with cap_ang < in_i (integer
+ *             atomics: deterministic).
+ * VAP_ERR_INVALID, before the context is touched: a limit that is NaN or <= 0 (+inf switches a cap off), a non-finite max_vel or
+ * track_width, a null meta, limits, constraints or output pointer with B > 0.  B = 0 is a no-op.  Works on the context's stream
+ * and does not synchronise. */
+typedef struct {
+    double lateral_acc_max; /* ft/s^2;  +inf = off */
+    double angular_acc_max; /* rad/s^2; +inf = off */
+} vap_curve_limits;
+int vap_curve_caps(vap_ctx *ctx, vap_dtype dt, int B, int S, const vap_constraints *c, const vap_curve_limits *lim,
+                   const double *d_meta, const void *d_curvature, const void *d_vcap_in, void *d_vcap_out, int *d_n_bound);
+
+/* vap_drive_audit: what the drivetrain has to do to follow time-domain rows.  d_rows [B][capacity][8] in the layout of
+ * vap_time_profile (any producer of it: vap_time_profile[_routes], vap_time_insert_waits / _events, vap_routine_timeline, the
+ * rollouts' executed rows); n = d_counts[b * counts_stride] clamped to [0, capacity].  Only column 2 (v) and column 5 (omega)
+ * are read.  With T = track_width and h = time_step, for row r < n, every operation fp64 and IEEE, in this order:
+ *   wL = v - (omega T) / 2, wR = v + (omega T) / 2            MPG:594-599, get_wheel_trajectory (MPG:641-642)
+ *   aL = (wL_r - wL_(r-1)) / h, aR likewise                   MPG:612-616 — but a wheel before row 0 stands still (0.0): the
+ *                                                             reference's i = 0 wraps to index -1, the LAST row; not kept
+ *   b = (v_r - v_(r-1)) / h, j = (b_r - b_(r-1)) / h          v_(-1) = b_(-1) = 0
+ *   l = v omega,  g = (omega_r - omega_(r-1)) / h             omega_(-1) = 0
+ * and the audited quantities q0 = max(|wL|, |wR|), q1 = max(|aL|, |aR|), q2 = |j|, q3 = |l|, q4 = |g|, with the limits
+ * wheel_speed_max, wheel_acc_max, jerk_max, lateral_acc_max, angular_acc_max in that order.
+ *   outputs (any may be NULL)
+ *     d_peak [B][5] fp64         the maximum of each q over the route's rows
+ *     d_peak_row [B][5] int32    the first row attaining it
+ *     d_n_over [B][5] int32      the rows with q strictly above its limit (+inf: never)
+ *     d_first_over [B][5] int32  the first such row, or -1
+ *     d_route_status [B] int32   bit 1 (value 2): a non-finite v or omega among rows 0 .. n - 1 (vap_pursuit_rollouts'
+ *                                convention); such a route is treated as a route with n = 0
+ *     d_wheel_rows [B][capacity][8] fp64  {wL, wR, aL, aR, b, j, l, g}, signed, for rows below n; nothing is written at or
+ *                                above n
+ *   n = 0 gives NaN peaks, -1 rows and 0 counts.  A q that is NaN (finite inputs can only give one by overflow) neither becomes
+ *   a peak nor counts.
+ * d_rows and d_wheel_rows must be 16-byte aligned.  The peaks are reduced as (value, row) pairs under one total order (the
+ * larger value, then the lower row) and the counts as integers, so the result does not depend on how the rows are tiled; no
+ * float atomics: two calls give the same bits.
+ * VAP_ERR_INVALID, before the context is touched: a track_width or time_step that is not positive and finite, a limit that is
+ * NaN or negative, a null rows, counts or limits pointer with B > 0, a misaligned pointer, B < 0, capacity < 0,
+ * counts_stride < 1.  B = 0 is a no-op.  Works on the context's stream and does not synchronise. */
+typedef struct {
+    double track_width, wheel_speed_max, wheel_acc_max, jerk_max, lateral_acc_max, angular_acc_max;
+} vap_drive_limits;
+int vap_drive_audit(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride,
+                    double time_step, const vap_drive_limits *lim, double *d_peak, int *d_peak_row, int *d_n_over,
+                    int *d_first_over, int *d_route_status, double *d_wheel_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,7 @@ EXPORTS = (
     "vap_tracking_rollouts", "vap_pursuit_rollouts", "vap_search_sample", "vap_search_update", "vap_plan_grid", "vap_plan_seeds",
     "vap_plan_occupancy", "vap_plan_seeds_occupied", "vap_plan_travel", "vap_plan_order",
     "vap_routine_timeline", "vap_plan_order_timed", "vap_velocity_conditioning",
+    "vap_curve_caps", "vap_drive_audit",
 )
 
 
@@ -101,6 +102,17 @@ class SearchWeights(C.Structure):
     """vap_search_weights (include/vap.h)."""
     _fields_ = [("w_time", C.c_double), ("w_length", C.c_double), ("w_violation", C.c_double), ("infeasible_base", C.c_double),
                 ("clearance_margin", C.c_double), ("conflict_margin", C.c_double), ("tracking_tolerance", C.c_double)]
+
+
+class CurveLimitsStruct(C.Structure):
+    """vap_curve_limits (include/vap.h)."""
+    _fields_ = [("lateral_acc_max", C.c_double), ("angular_acc_max", C.c_double)]
+
+
+class DriveLimitsStruct(C.Structure):
+    """vap_drive_limits (include/vap.h)."""
+    _fields_ = [("track_width", C.c_double), ("wheel_speed_max", C.c_double), ("wheel_acc_max", C.c_double),
+                ("jerk_max", C.c_double), ("lateral_acc_max", C.c_double), ("angular_acc_max", C.c_double)]
 
 
 ip = C.POINTER(C.c_int)
@@ -225,6 +237,8 @@ def lib():
                                        vp, vp, C.c_int] + [vp] * 6 + [C.c_int] + [vp] * 7
     L.vap_velocity_conditioning.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(Constraints), C.c_double, C.c_double] + [vp] * 7 + \
         [C.c_int, C.c_double, C.c_uint64, C.c_uint32, C.c_double] + [vp] * 6
+    L.vap_curve_caps.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(Constraints), C.POINTER(CurveLimitsStruct)] + [vp] * 5
+    L.vap_drive_audit.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_double, C.POINTER(DriveLimitsStruct)] + [vp] * 6
     _lib = L
     return L
 

@@ -338,9 +338,70 @@ class BatchedTrajectoryGenerator:
                                                     ptr(acc_b), ptr(dec_b), ptr(vel), ptr(result["flags"])),
                    "vap_velocity_pass_limits")
         result["vcap"] = vcap
+        # the acceleration rows stay with the result for apply_curve_caps (absent without max_acceleration limits)
+        for k, t in (("acc_forward", acc_f), ("acc_backward", acc_b), ("dec_backward", dec_b)):
+            if t is not None:
+                result[k] = t
+            else:
+                result.pop(k, None)
+        result.node_limits = (result.generation, vcap)
         result["node_sample"] = node_k
         result["action_sample"] = ap_k[:, :M]
         return result
+
+    def apply_curve_caps(self, result, caps, constraints=DEFAULT_CONSTRAINTS, start_vel=START_VEL, end_vel=END_VEL):
+        """Recompute the velocity rows of the batch ``profile`` has just produced with this generator under curve caps
+        (vap_curve_caps + vap_velocity_pass_limits): ``caps`` is a drive.CurveCaps — the lateral-acceleration cap
+        sqrt(A / |curvature|), which is what friction_coef is for, and / or the reference's dormant curvature-rate cap
+        (MPG:41-50 on MPG:178-186).  Same contract and checks as ``apply_node_limits``; if that ran on ``result`` before, its
+        "vcap" row is the incoming row and its acceleration rows are passed on.  Returns ``result`` with "velocity" replaced,
+        plus "vcap" (the capped row) and "n_bound" (B, 2) int32: the samples at which the lateral / the curvature-rate cap
+        lies below the incoming row.  A cap that binds nowhere changes no bit of the velocity row."""
+        from . import drive
+        if not isinstance(caps, drive.CurveCaps):
+            raise TypeError("caps must be a drive.CurveCaps")
+        caps.validate()
+        vel, meta = result["velocity"], result["meta"]
+        B, S = vel.shape
+        last = getattr(self, "_last_shape", None)
+        if last is None or (last[0], last[2]) != (B, S):
+            raise ValueError("apply_curve_caps needs the result of this generator's last profile() call")
+        self._check_current(result, "apply_curve_caps")
+        curv = result.get("curvature")
+        ctx_rows = self.vdtype == _lib.VAP_F32 and self.recurrence == "f64"   # the context holds the fp64 rows itself
+        if curv is None and not ctx_rows:
+            raise ValueError("apply_curve_caps needs the curvature rows (profile(want=...) must include 'curvature')")
+        dev = self.device
+        ldt = torch.float64 if self._L.vap_limit_rows_dtype(self.ctx.handle, self.vdtype) == _lib.VAP_F64 else torch.float32
+        node = getattr(result, "node_limits", None)
+        vin = node[1] if node is not None and node[0] == result.generation else None     # apply_node_limits ran on this batch
+        acc = [result.get(k) for k in ("acc_forward", "acc_backward", "dec_backward")] if vin is not None else [None] * 3
+        if any(a is None for a in acc):
+            acc = [None] * 3
+        # the capped row: a buffer of an earlier call on this dict where there is one (search.refine), never the incoming row
+        vcap = result.get("curve_vcap")
+        if vcap is None or vcap.shape != (B, S) or vcap.dtype != ldt or vcap.device != dev or vcap is vin:
+            vcap = None
+        c = _lib.make_constraints(constraints)
+        vcap, n_bound = drive.curve_caps(meta, None if ctx_rows else curv, caps, c, samples=S, dtype=self.tdtype, vcap_in=vin,
+                                         vcap_out=vcap, n_bound=result.get("n_bound"), ctx=self.ctx)
+        result["n_bound"] = n_bound
+        _lib.check(self._L.vap_velocity_pass_limits(self.ctx.handle, self.vdtype, B, S, C.byref(c), float(start_vel),
+                                                    float(end_vel), ptr(meta), ptr(curv), None, ptr(vcap), ptr(acc[0]),
+                                                    ptr(acc[1]), ptr(acc[2]), ptr(vel), ptr(result["flags"])),
+                   "vap_velocity_pass_limits")
+        result["vcap"] = result["curve_vcap"] = vcap
+        return result
+
+    def drive_audit(self, tp, limits, **kw):
+        """What the drivetrain has to do to follow the rows of ``tp`` — the dict ``time_profile``, ``insert_waits``,
+        ``routine_timeline`` or ``tracking_rollouts`` returned: peak wheel speed, wheel acceleration, jerk, lateral and angular
+        acceleration per route against ``limits`` (a drive.Limits; vap_drive_audit on this generator's context and torch's
+        current stream; see drive.audit for time_step, per_row, out and the returned dict)."""
+        from . import drive
+        if tp["rows"].device != self.device:
+            raise ValueError(f"rows must be on {self.device}")
+        return drive.audit(tp["rows"], tp["counts"], limits, ctx=self.ctx, **kw)
 
     def conditioning(self, result, constraints=DEFAULT_CONSTRAINTS, start_vel=START_VEL, end_vel=END_VEL, limits=None, probes=3,
                      delta=2.0 ** -40, seed=0, *, limit, per_sample=False):

@@ -97,6 +97,8 @@ struct vap_ctx {
     // vap_velocity_conditioning: the probes' squared velocities of one launch, at most cond_scratch_mb MiB of them
     VapBuffer cond_u;
     int cond_scratch_mb = 512;        // VAP_OPT_CONDITIONING_SCRATCH_MB
+    // vap_drive_audit: the routes' status words and the per-tile partial peaks and counts
+    VapBuffer drive_part;
 
     int ensure(VapBuffer &b, size_t bytes)
     {

@@ -238,7 +238,7 @@ def _sigma0(sigma0, R, W, pinned, pin_ends):
 
 def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS, samples=None, dd=None, dt=0.01,
            capacity_rows=None, others=None, others_footprint=None, follower=None, perturbations=None, config=None,
-           pinned=None, pin_ends=True, capacity=None, first_problem=0):
+           pinned=None, pin_ends=True, capacity=None, first_problem=0, curve_caps=None):
     """Refine R routes by cross-entropy search on ``gen``'s device (a BatchedTrajectoryGenerator; its dtype is the
     waypoints').
 
@@ -256,6 +256,8 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
                      tracking error of every candidate's rollouts enters the cost above config.weights.tracking_tolerance;
                      with a Pursuit a candidate with a rollout that never arrives (n_unfinished > 0) has the term +inf
       config         a SearchConfig
+      curve_caps     a drive.CurveCaps: every iteration's velocity rows are recomputed under these caps
+                     (``gen.apply_curve_caps``) between ``profile`` and ``time_profile``; None: the sequence without it
       first_problem  the number of problem 0 in the random stream: R = 1 with first_problem = r draws what problem r of a
                      larger call draws
     Per iteration it enqueues sample, profile, time_profile, footprint clearance, conflicts (with ``others``), rollouts
@@ -300,6 +302,8 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
         sample(mean, sigma, N, seed=cfg.seed, iteration=it, first_problem=first_problem, best_waypoints=best_wp,
                best_cost=best_cost, out=wp, ctx=gen.ctx)
         prof = gen.profile(wp, constraints, out=prof, **kw)
+        if curve_caps is not None:
+            gen.apply_curve_caps(prof, curve_caps, constraints)
         gen.time_profile(prof, constraints, dt=dt, capacity_rows=capacity_rows, out=tp)
         fp.clearance(tp["rows"], tp["counts"], footprint, scene, margin=wts.clearance_margin, out=clr, ctx=gen.ctx)
         terms = {"clearance": clr["min_clearance"]}
