@@ -807,6 +807,60 @@ int vap_pursuit_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_row
                          int *d_worst_row, int *d_n_exceeding, int *d_n_unfinished, int *d_route_status, long cap_exec,
                          double *d_exec_rows, int *d_exec_counts);
 
+/* ---- scene clearance of the disturbed rollouts ---------------------------------------------------------------------
+ * Does the robot still miss the post when it starts an inch off, one side runs 3 % weak and the drive lags?  The rollout
+ * calls above can write every executed row (d_exec_rows) and vap_footprint_clearance can read them back: B x K x rows x
+ * 64 bytes through memory for five numbers per rollout.  This call runs the K rollouts per route of either follower and
+ * takes the scene clearance of every executed row while it is still on the chip.  No executed rows are written.
+ *
+ *   follower  follower_kind = VAP_FOLLOWER_RAMSETE with `follower` a const vap_follower *, or VAP_FOLLOWER_PURSUIT with a
+ *             const vap_pursuit *.
+ *   rollouts  d_rows, d_counts, counts_stride, time_step, K, shared_perturb, d_perturb and the follower outputs d_stats,
+ *             d_stat_rows ([B][K][2] for RAMSETE, [B][K][4] for pure pursuit), d_worst, d_mean, d_worst_rollout, d_worst_row,
+ *             d_n_exceeding, and for pure pursuit d_n_unfinished and d_route_status: exactly as vap_tracking_rollouts /
+ *             vap_pursuit_rollouts take and write them for the same inputs, bit for bit.  d_n_unfinished and d_route_status
+ *             must be NULL with VAP_FOLLOWER_RAMSETE (VAP_ERR_INVALID).
+ *   scene     n_foot, h_footprint, h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles and margin exactly as
+ *             vap_footprint_clearance takes them: the same validation, limits and errors, the same element ids.
+ *   pose      of executed row r: what step 3 of vap_tracking_rollouts would store, heading = -wrap(phi), x, y.  The
+ *             footprint is posed at the body angle -heading = wrap(phi), not at the unwrapped phi (the two differ in
+ *             the last bits of sin and cos once |phi| > pi).
+ *   outputs   any pointer may be NULL.
+ *             per rollout: d_clearance [B][K]; d_clear_rows [B][K][4] = {the first row at the minimum, the element at it,
+ *             the first row with clearance < margin or -1, the rows with clearance < margin}.  DEFINITION: the five
+ *             numbers vap_footprint_clearance returns (d_min_clearance, d_min_row, d_min_element, d_first_row, d_n_below)
+ *             for route b * K + k of that follower's d_exec_rows / d_exec_counts with the same scene, footprint and margin
+ *             and counts_stride = 2 — over executed rows 0 .. n + settle_rows - 1, bit for bit.  The reduction over a
+ *             rollout's rows is that call's: a strictly smaller clearance replaces (the first row stays on a tie), a NaN
+ *             clearance never replaces.  A rollout without executed rows (n = 0, an invalid record, a non-zero pursuit
+ *             status) gets NaN, -1, -1, -1, 0.
+ *             per route [B], over the route's valid rollouts (those with a minimum row >= 0) in ascending k:
+ *             d_worst_clearance (the smallest per-rollout clearance; the smallest k on a tie), d_worst_clear_rollout,
+ *             d_worst_clear_row, d_worst_clear_element (that k, its row and its element), d_mean_clearance (one running
+ *             sum divided by the count), d_n_colliding (valid rollouts with clearance < margin), d_n_clear_valid (the valid
+ *             rollouts: n_colliding / n_clear_valid is the collision share).  A route without a valid rollout gets NaN,
+ *             -1, -1, -1, NaN, 0, 0.
+ *   alignment d_rows, d_perturb and d_stats 16-byte aligned as in the rollout calls, else VAP_ERR_INVALID.
+ * The check is discrete at time_step, as vap_footprint_clearance is: motion between two rows is not swept.
+ * VAP_OPT_FOOTPRINT_CULL governs culling; on and off give the same bits.  Every reduction has a fixed order and there are
+ * no float atomics: two calls on the same inputs give the same bits.
+ * VAP_ERR_INVALID: a follower_kind other than the two; a null follower; every follower, time_step, K (outside 1..4096),
+ * shape, stride and null-pointer error of the follower's own call; a non-finite margin; a null, clockwise, non-convex or
+ * degenerate footprint; every scene error of vap_footprint_clearance.  VAP_ERR_UNSUPPORTED: that call's scene limits (256
+ * polygons, 4096 polygon vertices, 256 circles); capacity + settle_rows above INT_MAX; too many workgroups for one launch.
+ * The host arguments are checked before the context is touched.  B = 0 is a no-op.  Works on the context's stream and does
+ * not synchronise.  Context scratch: the packed scene, pure pursuit's status words, and for K > 256 the B x K partials of
+ * the summaries; it never grows with rows x K. */
+enum { VAP_FOLLOWER_RAMSETE = 0, VAP_FOLLOWER_PURSUIT = 1 };
+int vap_rollout_clearance(vap_ctx *ctx, int follower_kind, const void *follower, int B, long capacity, const double *d_rows,
+                          const int *d_counts, int counts_stride, double time_step, int K, int shared_perturb,
+                          const double *d_perturb, int n_foot, const double *h_footprint, const double *h_field, int n_poly,
+                          const int *h_poly_start, const double *h_poly_xy, int n_circle, const double *h_circles, double margin,
+                          double *d_stats, int *d_stat_rows, double *d_worst, double *d_mean, int *d_worst_rollout,
+                          int *d_worst_row, int *d_n_exceeding, int *d_n_unfinished, int *d_route_status, double *d_clearance,
+                          int *d_clear_rows, double *d_worst_clearance, int *d_worst_clear_rollout, int *d_worst_clear_row,
+                          int *d_worst_clear_element, double *d_mean_clearance, int *d_n_colliding, int *d_n_clear_valid);
+
 /* ---- cross-entropy route search over batches of candidate trajectories --------------------------------------------
  * The calls above judge candidate routes; these two make the candidates and act on the verdicts, so that a search
  *   sample -> vap_profile_batch -> vap_time_profile -> vap_footprint_clearance [-> conflicts, rollouts] -> update

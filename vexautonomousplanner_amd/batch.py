@@ -579,6 +579,17 @@ class BatchedTrajectoryGenerator:
             raise ValueError(f"rows must be on {self.device}")
         return tracking.rollouts(tp["rows"], tp["counts"], follower, perturbations, ctx=self.ctx, **kw)
 
+    def rollout_clearance(self, tp, follower, perturbations, footprint, scene, **kw):
+        """Scene clearance of the disturbed rollouts along the rows of ``tp`` — the dict ``time_profile`` or
+        ``insert_waits`` returned — under ``perturbations``, without executed rows in memory (vap_rollout_clearance on this
+        generator's context and torch's current stream; see tracking.rollout_clearance for margin, time_step, out, cull and
+        the returned dict).  ``follower``: a tracking.Follower or a tracking.Pursuit; ``footprint``, ``scene``: as in
+        ``footprint_clearance``."""
+        from . import tracking
+        if tp["rows"].device != self.device:
+            raise ValueError(f"rows must be on {self.device}")
+        return tracking.rollout_clearance(tp["rows"], tp["counts"], follower, perturbations, footprint, scene, ctx=self.ctx, **kw)
+
     def refine(self, seeds, sigma0, footprint, scene, **kw):
         """Cross-entropy search for faster routes that still clear ``scene`` (and a partner's routines, and a follower's
         tracking error), starting from ``seeds``: sample, profile, time_profile, clearance checks and the refit run on this

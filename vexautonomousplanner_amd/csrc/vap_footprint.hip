@@ -14,7 +14,8 @@
 // the route's outputs.  No reduction across workgroups.
 //
 // The scene (a few KB) lives in one device block read at wave-uniform addresses; rows are read with 8-byte loads of
-// columns 4, 6 and 7 (the only columns the check needs).
+// columns 4, 6 and 7 (the only columns the check needs).  The scene's layout and the per-row device functions are in
+// vap_footprint.h: the rollout kernels take the clearance of their executed rows with them (vap_rollout_clearance.hip).
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -26,176 +27,6 @@ namespace vap {
 
 constexpr int kFootThreads = 256;
 constexpr int kFootWaves = kFootThreads / 64;
-
-// Packed scene (fp64):
-//   foot  [n_foot][8]  body vertex x, y; outward unit normal of the edge to the next vertex nx, ny; that edge ex, ey;
-//                      1 / |e|^2; 0
-//   poly  [n_poly][4]  centre x, y; bounding radius; first vertex * 32 + vertex count (as a double)
-//   pv    [nv][8]      the polygons' vertices, same layout as foot, in world coordinates
-//   circ  [n_circle][4] cx, cy, r, 0
-struct FootScene {
-    const double *__restrict__ foot;
-    const double *__restrict__ poly;
-    const double *__restrict__ pv;
-    const double *__restrict__ circ;
-    double fcx, fcy, fR;                  // footprint centre (body frame) and bounding radius
-    double xmin, ymin, xmax, ymax;
-    double slack;                         // kCullSlack * (1 + scene coordinate scale)
-    int has_field, n_foot, n_poly, n_circle, cull;
-};
-
-// the footprint's vertex i at the row's pose
-__device__ __forceinline__ void foot_vertex(const FootScene &s, int i, double x, double y, double c, double sn, double &wx,
-                                            double &wy)
-{
-    const double bx = s.foot[i * 8 + 0], by = s.foot[i * 8 + 1];
-    wx = x + (c * bx - sn * by);
-    wy = y + (sn * bx + c * by);
-}
-
-// Polygon element [p0, p0 + m): separated -> distance, overlapping -> minus the smallest overlap over the edge normals
-// of both polygons.
-__device__ double poly_clearance(const FootScene &s, int p0, int m, double x, double y, double c, double sn)
-{
-    const int n = s.n_foot;
-    double sep = INFINITY;
-    bool separated = false;
-    // axes of the footprint's edges (rotated body normals)
-#pragma unroll 1
-    for (int i = 0; i < n && !separated; i++) {
-        const double bnx = s.foot[i * 8 + 2], bny = s.foot[i * 8 + 3];
-        const double nx = c * bnx - sn * bny, ny = sn * bnx + c * bny;
-        double f0 = INFINITY, f1 = -INFINITY, q0 = INFINITY, q1 = -INFINITY;
-#pragma unroll 1
-        for (int j = 0; j < n; j++) {
-            double wx, wy;
-            foot_vertex(s, j, x, y, c, sn, wx, wy);
-            const double d = nx * wx + ny * wy;
-            f0 = fmin(f0, d);
-            f1 = fmax(f1, d);
-        }
-#pragma unroll 1
-        for (int k = 0; k < m; k++) {
-            const double *v = s.pv + (size_t)(p0 + k) * 8;
-            const double d = nx * v[0] + ny * v[1];
-            q0 = fmin(q0, d);
-            q1 = fmax(q1, d);
-        }
-        const double ov = fmin(f1, q1) - fmax(f0, q0);
-        sep = fmin(sep, ov);
-        separated = !(ov > 0.0);
-    }
-    // axes of the polygon's edges
-#pragma unroll 1
-    for (int k = 0; k < m && !separated; k++) {
-        const double *vk = s.pv + (size_t)(p0 + k) * 8;
-        const double nx = vk[2], ny = vk[3];
-        double f0 = INFINITY, f1 = -INFINITY, q0 = INFINITY, q1 = -INFINITY;
-#pragma unroll 1
-        for (int j = 0; j < n; j++) {
-            double wx, wy;
-            foot_vertex(s, j, x, y, c, sn, wx, wy);
-            const double d = nx * wx + ny * wy;
-            f0 = fmin(f0, d);
-            f1 = fmax(f1, d);
-        }
-#pragma unroll 1
-        for (int j = 0; j < m; j++) {
-            const double *v = s.pv + (size_t)(p0 + j) * 8;
-            const double d = nx * v[0] + ny * v[1];
-            q0 = fmin(q0, d);
-            q1 = fmax(q1, d);
-        }
-        const double ov = fmin(f1, q1) - fmax(f0, q0);
-        sep = fmin(sep, ov);
-        separated = !(ov > 0.0);
-    }
-    if (!separated) return -sep;
-    // separated or touching: the distance is attained between a vertex of one and an edge of the other
-    double d2 = INFINITY;
-#pragma unroll 1
-    for (int i = 0; i < n; i++) {
-        double ax, ay;
-        foot_vertex(s, i, x, y, c, sn, ax, ay);
-        const double bex = s.foot[i * 8 + 4], bey = s.foot[i * 8 + 5], il2 = s.foot[i * 8 + 6];
-        const double ex = c * bex - sn * bey, ey = sn * bex + c * bey;
-#pragma unroll 1
-        for (int k = 0; k < m; k++) {
-            const double *v = s.pv + (size_t)(p0 + k) * 8;
-            d2 = fmin(d2, seg_dist2(ax, ay, v[0], v[1], v[4], v[5], v[6]));    // footprint vertex i, polygon edge k
-            d2 = fmin(d2, seg_dist2(v[0], v[1], ax, ay, ex, ey, il2));         // polygon vertex k, footprint edge i
-        }
-    }
-    return sqrt(d2);
-}
-
-// Circle element: signed distance from the centre to the footprint (positive outside) minus r.
-__device__ double circle_clearance(const FootScene &s, double qx, double qy, double r, double x, double y, double c, double sn)
-{
-    double smax = -INFINITY, d2 = INFINITY;
-#pragma unroll 1
-    for (int i = 0; i < s.n_foot; i++) {
-        double ax, ay;
-        foot_vertex(s, i, x, y, c, sn, ax, ay);
-        const double bnx = s.foot[i * 8 + 2], bny = s.foot[i * 8 + 3];
-        const double bex = s.foot[i * 8 + 4], bey = s.foot[i * 8 + 5], il2 = s.foot[i * 8 + 6];
-        const double nx = c * bnx - sn * bny, ny = sn * bnx + c * bny;
-        const double ex = c * bex - sn * bey, ey = sn * bex + c * bey;
-        smax = fmax(smax, nx * (qx - ax) + ny * (qy - ay));
-        d2 = fmin(d2, seg_dist2(qx, qy, ax, ay, ex, ey, il2));
-    }
-    return (smax > 0.0 ? sqrt(d2) : smax) - r;
-}
-
-// true when an element of centre (ox, oy) and bounding radius orad cannot go below best at this row
-__device__ __forceinline__ bool culled(const FootScene &s, double best, double slack, double fx, double fy, double ox, double oy,
-                                       double orad)
-{
-    if (!s.cull) return false;
-    const double reach = best + slack + orad + s.fR;   // skip when |o - f| > reach
-    if (reach < 0.0) return true;
-    const double dx = ox - fx, dy = oy - fy;
-    return dx * dx + dy * dy > reach * reach;          // false for best = +inf or NaN
-}
-
-// The clearance of one row and the element that gives it.
-__device__ double row_clearance(const FootScene &s, double heading, double x, double y, int &elem)
-{
-    const double phi = -heading;
-    double sn, c;
-    sincos(phi, &sn, &c);
-    double best = INFINITY;
-    elem = INT_MAX;
-    if (s.has_field) {
-        double w = INFINITY;
-#pragma unroll 1
-        for (int i = 0; i < s.n_foot; i++) {
-            double px, py;
-            foot_vertex(s, i, x, y, c, sn, px, py);
-            w = fmin(w, fmin(fmin(px - s.xmin, s.xmax - px), fmin(py - s.ymin, s.ymax - py)));
-        }
-        best = w;
-        elem = -1;
-    }
-    const double fx = x + (c * s.fcx - sn * s.fcy), fy = y + (sn * s.fcx + c * s.fcy);
-    const double slack = s.slack + kCullSlack * (fabs(x) + fabs(y));
-#pragma unroll 1
-    for (int k = 0; k < s.n_poly; k++) {
-        const double *pk = s.poly + (size_t)k * 4;
-        if (culled(s, best, slack, fx, fy, pk[0], pk[1], pk[2])) continue;
-        const int code = (int)pk[3];
-        const double v = poly_clearance(s, code >> 5, code & 31, x, y, c, sn);
-        if (v < best) { best = v; elem = k; }
-    }
-#pragma unroll 1
-    for (int k = 0; k < s.n_circle; k++) {
-        const double *ck = s.circ + (size_t)k * 4;
-        if (culled(s, best, slack, fx, fy, ck[0], ck[1], ck[2])) continue;
-        const double v = circle_clearance(s, ck[0], ck[1], ck[2], x, y, c, sn);
-        if (v < best) { best = v; elem = s.n_poly + k; }
-    }
-    return best;
-}
 
 __global__ __launch_bounds__(kFootThreads) void k_footprint_clearance(FootScene s, long capacity, const double *__restrict__ rows,
                                                                       const int *__restrict__ counts, int counts_stride, double margin,
@@ -390,38 +221,16 @@ int scene_upload(vap_ctx *ctx, size_t bytes)
     return VAP_OK;
 }
 
-}  // namespace vap
-
-extern "C" {
-
-int vap_footprint_clearance(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride,
-                            int n_foot, const double *h_footprint, const double *h_field, int n_poly, const int *h_poly_start,
-                            const double *h_poly_xy, int n_circle, const double *h_circles, double margin,
-                            double *d_row_clearance, double *d_min_clearance, int *d_min_row, int *d_min_element,
-                            int *d_first_row, int *d_n_below)
+// The packed scene of a validated footprint and scene on the device, and `s` filled for a kernel on the context's stream.
+int scene_pack(vap_ctx *ctx, int n_foot, const double *h_footprint, const double *h_field, int n_poly, const int *h_poly_start,
+               const double *h_poly_xy, int n_circle, const double *h_circles, double scale, int nv, FootScene &s)
 {
-    using namespace vap;
-    VAP_TRY(vap_set_device(ctx));
-    if (B < 0 || capacity < 0) return vap_fail(VAP_ERR_INVALID, "bad shape B=%d capacity=%ld", B, capacity);
-    if (capacity > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "capacity %ld above %d rows", capacity, INT_MAX);
-    if (counts_stride < 1) return vap_fail(VAP_ERR_INVALID, "counts_stride must be >= 1 (got %d)", counts_stride);
-    if (B > 0 && (!d_counts || (capacity > 0 && !d_rows))) return vap_fail(VAP_ERR_INVALID, "null rows / counts");
-    if (!std::isfinite(margin)) return vap_fail(VAP_ERR_INVALID, "margin must be finite");
-    // the scene
-    if (!h_footprint) return vap_fail(VAP_ERR_INVALID, "null footprint");
-    VAP_TRY(check_convex(h_footprint, n_foot, "footprint", 0));
-    double scale = 0.0;
-    int nv = 0;
-    VAP_TRY(check_scene(h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, scale, nv));
-    if (B == 0) return VAP_OK;
-
     // pack: foot [n_foot][8] | poly [n_poly][4] | pv [nv][8] | circ [n_circle][4]
     const size_t o_poly = (size_t)n_foot * 8, o_pv = o_poly + (size_t)n_poly * 4, o_circ = o_pv + (size_t)nv * 8;
     const size_t n_dbl = o_circ + (size_t)n_circle * 4;
     const size_t bytes = n_dbl * sizeof(double);
     double *h = nullptr;
     VAP_TRY(scene_stage(ctx, bytes, &h));
-    FootScene s;
     pack_polygon(h_footprint, n_foot, h);
     bound_polygon(h_footprint, n_foot, s.fcx, s.fcy, s.fR);
     for (int k = 0; k < n_poly; k++) {
@@ -450,6 +259,36 @@ int vap_footprint_clearance(vap_ctx *ctx, int B, long capacity, const double *d_
     s.n_poly = n_poly;
     s.n_circle = n_circle;
     s.cull = ctx->footprint_cull;
+    return VAP_OK;
+}
+
+}  // namespace vap
+
+extern "C" {
+
+int vap_footprint_clearance(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride,
+                            int n_foot, const double *h_footprint, const double *h_field, int n_poly, const int *h_poly_start,
+                            const double *h_poly_xy, int n_circle, const double *h_circles, double margin,
+                            double *d_row_clearance, double *d_min_clearance, int *d_min_row, int *d_min_element,
+                            int *d_first_row, int *d_n_below)
+{
+    using namespace vap;
+    VAP_TRY(vap_set_device(ctx));
+    if (B < 0 || capacity < 0) return vap_fail(VAP_ERR_INVALID, "bad shape B=%d capacity=%ld", B, capacity);
+    if (capacity > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "capacity %ld above %d rows", capacity, INT_MAX);
+    if (counts_stride < 1) return vap_fail(VAP_ERR_INVALID, "counts_stride must be >= 1 (got %d)", counts_stride);
+    if (B > 0 && (!d_counts || (capacity > 0 && !d_rows))) return vap_fail(VAP_ERR_INVALID, "null rows / counts");
+    if (!std::isfinite(margin)) return vap_fail(VAP_ERR_INVALID, "margin must be finite");
+    // the scene
+    if (!h_footprint) return vap_fail(VAP_ERR_INVALID, "null footprint");
+    VAP_TRY(check_convex(h_footprint, n_foot, "footprint", 0));
+    double scale = 0.0;
+    int nv = 0;
+    VAP_TRY(check_scene(h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, scale, nv));
+    if (B == 0) return VAP_OK;
+
+    FootScene s;
+    VAP_TRY(scene_pack(ctx, n_foot, h_footprint, h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, scale, nv, s));
     hipLaunchKernelGGL(k_footprint_clearance, dim3(B), dim3(kFootThreads), 0, ctx->stream, s, capacity, d_rows, d_counts,
                        counts_stride, margin, d_row_clearance, d_min_clearance, d_min_row, d_min_element, d_first_row, d_n_below);
     HIP_TRY(hipGetLastError());

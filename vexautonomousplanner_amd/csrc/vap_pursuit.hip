@@ -21,6 +21,9 @@
 //   summary  as vap_tracking.hip: K <= 256 the first lane of each route walks its K rollouts in LDS in ascending k;
 //            K > 256 the partials go to context scratch and k_pursuit_reduce walks them, a lane per route.  No float
 //            atomics, so two calls give the same bits.
+//   modes    as vap_tracking.hip: pursuit_rollouts<MODE> is the march; k_pursuit_rollouts<false / true>,
+//            k_pursuit_clearance and k_pursuit_clearance_split (vap_rollout_clearance.hip, through pursuit_setup /
+//            pursuit_launch) instantiate it.  Only the split cuts the row loop into tiles with a barrier each.
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -31,28 +34,6 @@
 namespace vap {
 
 constexpr int kCheckThreads = 256;
-
-struct PursuitArgs {
-    const double *rows;       // [B][cap][8]
-    const int *counts;
-    long cap;
-    int stride, B, K, shared;
-    const double *perturb;    // [B][K][8] or [K][8]
-    double T, L, vmin, atol, wmax, tol, dt, h;
-    int nsub, settle;
-    double *stats;            // [B][K][6]
-    int *stat_rows;           // [B][K][4]
-    double *worst, *mean;     // [B]
-    int *worst_rollout, *worst_row, *n_exceeding, *n_unfinished;
-    int *status;              // [B] context scratch: the check kernel's mask
-    int *route_status;        // [B] the caller's, or NULL
-    long cap_exec;
-    double *exec_rows;        // [B*K][cap_exec][8]
-    int *exec_counts;         // [B*K][2]
-    double *part_e;           // K > 256: [B][K] max e_ct (row < 0: takes no part)
-    int *part_row, *part_arr;
-    int R, wpr;               // routes per workgroup, workgroups per route
-};
 
 __global__ __launch_bounds__(kCheckThreads) void k_pursuit_check(PursuitArgs g)
 {
@@ -122,19 +103,28 @@ struct PursuitSummary : TrackSummary {
     }
 };
 
-template <bool EXEC>
-__global__ __launch_bounds__(kTrackThreads) void k_pursuit_rollouts(PursuitArgs g)
+// The rollouts of one workgroup.  MODE: what becomes of the executed row (kTrackPlain, kTrackExec, kTrackClear,
+// kTrackSplit); `c` is read with the last two only.
+template <int MODE>
+__device__ __forceinline__ void pursuit_rollouts(const PursuitArgs &g, const TrackClear *c)
 {
+    constexpr bool EXEC = MODE == kTrackExec, SPLIT = MODE == kTrackSplit;
     __shared__ double s_e[kTrackThreads];
     __shared__ int s_r[kTrackThreads], s_a[kTrackThreads];
     const int tid = threadIdx.x;
     const int R = g.R;
+    const bool producer = !SPLIT || tid < kTrackThreads;     // SPLIT: the threads behind the rollout lanes take clearances
+    double *s_pose = nullptr, *s_cap = nullptr;
+    if constexpr (SPLIT) {
+        s_pose = lds_doubles<2 * kSplitTile, 0>();
+        s_cap = lds_doubles<2 * kTrackThreads, 1>();
+    }
     // which rollout this lane walks
     const int b0 = g.wpr > 1 ? (int)(blockIdx.x / g.wpr) : (int)blockIdx.x * R;
     const int lr = g.wpr > 1 ? 0 : tid / g.K;                                  // route within the workgroup
     const int k = g.wpr > 1 ? (int)(blockIdx.x % g.wpr) * kTrackThreads + tid : tid % g.K;
     const int b = b0 + lr;
-    const bool inside = lr < R && b < g.B && k < g.K;
+    const bool inside = producer && lr < R && b < g.B && k < g.K;
     const size_t gi = (size_t)b * g.K + k;            // flattened (b, k)
     int n = 0;
     if (inside && g.status[b] == 0) {
@@ -173,6 +163,7 @@ __global__ __launch_bounds__(kTrackThreads) void k_pursuit_rollouts(PursuitArgs 
     double maxe = -INFINITY;
     int mrow = -1, nsat = 0, arrived = -1;
     double *erow = EXEC && valid ? g.exec_rows + gi * (size_t)g.cap_exec * 8 : nullptr;
+    ClearAcc acc;
 
     // the two pointers: the closest segment ic with P_ic, P_ic+1, P_ic+2 (A, Bp, Cn), its chord length and length; the
     // lookahead segment il with P_il, P_il+1 (Lp, Lq).  Both start on segment 0.
@@ -196,116 +187,154 @@ __global__ __launch_bounds__(kTrackThreads) void k_pursuit_rollouts(PursuitArgs 
         }
     }
 
+    // SPLIT: in iteration ti tile ti is marched, tile ti - 1 cleared, tile ti - 2 folded; the steps of the longest rollout
+    // of the workgroup set the number of tiles for every thread
+    int wg_total = my_total;
+    if constexpr (SPLIT) {
+        __shared__ int s_total;
+        if (tid == 0) s_total = 0;
+        __syncthreads();
+        if (my_total > 0) atomicMax(&s_total, my_total);
+        __syncthreads();
+        wg_total = s_total;
+    }
+    const int ntiles = (wg_total + kSplitRows - 1) / kSplitRows;
+    const int nit = SPLIT ? ntiles + 2 : 1;
 #pragma unroll 1
-    for (int r = 0; r < my_total; r++) {
-        // 1. the closest point: ic advances while the next segment is no farther
-        double t = 1.0, D, ect, vt, sc = 0.0;
-        bool at_end = true;
-        if (n >= 2) {
-            pursuit_project(A.x, A.y, Bp.x, Bp.y, pl.x, pl.y, t, D);
-#pragma unroll 1
-            while (ic < n - 2) {
-                double t1, D1;
-                pursuit_project(Bp.x, Bp.y, Cn.x, Cn.y, pl.x, pl.y, t1, D1);
-                if (!(D1 <= D)) break;
-                c_ic += len_ic;
-                A = Bp;
-                Bp = Cn;
-                ic++;
-                len_ic = pursuit_len(A.x, A.y, Bp.x, Bp.y);
-                if (ic + 2 < n) Cn = pursuit_point(route, ic + 2);
-                t = t1;
-                D = D1;
+    for (int ti = 0; ti < nit; ti++) {
+        int rbeg = 0, rstop = my_total;
+        if (SPLIT) {
+            rbeg = rstop = ti * kSplitRows;
+            if (!producer) {
+                if (ti >= 1 && ti <= ntiles)
+                    split_clear(*c, s_pose, s_cap, ti - 1, min(kSplitRows, wg_total - (ti - 1) * kSplitRows), tid - kTrackThreads,
+                                (int)blockDim.x - kTrackThreads);
+            } else {
+                if (ti >= 2)
+                    split_fold(acc, s_pose, ti - 2, (ti - 2) * kSplitRows, min(kSplitRows, wg_total - (ti - 2) * kSplitRows), my_total,
+                               tid, c->margin);
+                s_cap[(size_t)(ti & 1) * kTrackThreads + tid] = acc.best;
+                if (ti < ntiles) rstop = min(rbeg + kSplitRows, wg_total);
             }
-            ect = sqrt(D);
-            vt = A.v + t * (Bp.v - A.v);
-            sc = c_ic + t * len_ic;
-            at_end = ic == n - 2 && t == 1.0;
-        } else {
-            const double ex = pl.x - A.x, ey = pl.y - A.y;
-            ect = sqrt(ex * ex + ey * ey);
-            vt = A.v;
         }
-        // 2. statistics
-        if (ect > maxe) { maxe = ect; mrow = r; }
-        // 3. the executed row
-        if (EXEC) pl.write_row(erow, r, g.dt);
-        // 4. arrival
-        if (arrived < 0) {
-            const double ex = lastx - pl.x, ey = lasty - pl.y;
-            if (at_end || sqrt(ex * ex + ey * ey) <= g.atol) arrived = r;
-        }
-        // 5. the goal one lookahead further along the chord length, and the command (n >= 2: one row has arrived)
-        double cl = 0.0, cr = 0.0;
-        if (arrived < 0) {
-            const double star = sc + L;
-            if (il < ic) {
-                il = ic;
-                lpx = A.x, lpy = A.y, lqx = Bp.x, lqy = Bp.y;
-                c_il = c_ic;
-                len_il = len_ic;
-            }
 #pragma unroll 1
-            while (il < n - 2 && c_il + len_il < star) {
-                c_il += len_il;
-                lpx = lqx, lpy = lqy;
-                il++;
-                const double2 q = *(const double2 *)(route + (size_t)(il + 1) * 8 + 6);
-                lqx = q.x, lqy = q.y;
-                len_il = pursuit_len(lpx, lpy, lqx, lqy);
+        for (int r = rbeg; r < rstop; r++) {
+            if (SPLIT && r >= my_total) {
+                split_put(s_pose, ti & 1, r - rbeg, tid, NAN, 0.0, 0.0);
+                continue;
             }
-            // star >= c_(n-1)?  c_(il+1) >= star here unless il is the last segment, so short of it the two can only be
-            // equal, with every later segment adding nothing
-            const double cnext = c_il + len_il;
-            bool beyond = il == n - 2 ? star >= cnext : cnext == star;
-            if (beyond && il < n - 2) {
-                double px = lqx, py = lqy;
+            // 1. the closest point: ic advances while the next segment is no farther
+            double t = 1.0, D, ect, vt, sc = 0.0;
+            bool at_end = true;
+            if (n >= 2) {
+                pursuit_project(A.x, A.y, Bp.x, Bp.y, pl.x, pl.y, t, D);
 #pragma unroll 1
-                for (int j = il + 1; j < n - 1; j++) {
-                    const double2 q = *(const double2 *)(route + (size_t)(j + 1) * 8 + 6);
-                    if (cnext + pursuit_len(px, py, q.x, q.y) != cnext) { beyond = false; break; }
-                    px = q.x, py = q.y;
+                while (ic < n - 2) {
+                    double t1, D1;
+                    pursuit_project(Bp.x, Bp.y, Cn.x, Cn.y, pl.x, pl.y, t1, D1);
+                    if (!(D1 <= D)) break;
+                    c_ic += len_ic;
+                    A = Bp;
+                    Bp = Cn;
+                    ic++;
+                    len_ic = pursuit_len(A.x, A.y, Bp.x, Bp.y);
+                    if (ic + 2 < n) Cn = pursuit_point(route, ic + 2);
+                    t = t1;
+                    D = D1;
                 }
+                ect = sqrt(D);
+                vt = A.v + t * (Bp.v - A.v);
+                sc = c_ic + t * len_ic;
+                at_end = ic == n - 2 && t == 1.0;
+            } else {
+                const double ex = pl.x - A.x, ey = pl.y - A.y;
+                ect = sqrt(ex * ex + ey * ey);
+                vt = A.v;
             }
-            double gx, gy;
-            if (beyond) {
-                if (!have_u) {                       // the direction of the last segment with a length
-                    have_u = true;
-                    double qx = lastx, qy = lasty;
+            // 2. statistics
+            if (ect > maxe) { maxe = ect; mrow = r; }
+            // 3. the executed row
+            if (EXEC) pl.write_row(erow, r, g.dt);
+            if (MODE == kTrackClear) acc.take(c->s, c->margin, pl, r);
+            if (SPLIT) split_put(s_pose, ti & 1, r - rbeg, tid, -track_wrap(pl.phi), pl.x, pl.y);
+            // 4. arrival
+            if (arrived < 0) {
+                const double ex = lastx - pl.x, ey = lasty - pl.y;
+                if (at_end || sqrt(ex * ex + ey * ey) <= g.atol) arrived = r;
+            }
+            // 5. the goal one lookahead further along the chord length, and the command (n >= 2: one row has arrived)
+            double cl = 0.0, cr = 0.0;
+            if (arrived < 0) {
+                const double star = sc + L;
+                if (il < ic) {
+                    il = ic;
+                    lpx = A.x, lpy = A.y, lqx = Bp.x, lqy = Bp.y;
+                    c_il = c_ic;
+                    len_il = len_ic;
+                }
 #pragma unroll 1
-                    for (int j = n - 2; j >= 0; j--) {
-                        const double2 q = *(const double2 *)(route + (size_t)j * 8 + 6);
-                        const double l = pursuit_len(q.x, q.y, qx, qy);
-                        if (l > 0.0) {
-                            ux = (qx - q.x) / l;
-                            uy = (qy - q.y) / l;
-                            break;
-                        }
-                        qx = q.x, qy = q.y;
+                while (il < n - 2 && c_il + len_il < star) {
+                    c_il += len_il;
+                    lpx = lqx, lpy = lqy;
+                    il++;
+                    const double2 q = *(const double2 *)(route + (size_t)(il + 1) * 8 + 6);
+                    lqx = q.x, lqy = q.y;
+                    len_il = pursuit_len(lpx, lpy, lqx, lqy);
+                }
+                // star >= c_(n-1)?  c_(il+1) >= star here unless il is the last segment, so short of it the two can only be
+                // equal, with every later segment adding nothing
+                const double cnext = c_il + len_il;
+                bool beyond = il == n - 2 ? star >= cnext : cnext == star;
+                if (beyond && il < n - 2) {
+                    double px = lqx, py = lqy;
+#pragma unroll 1
+                    for (int j = il + 1; j < n - 1; j++) {
+                        const double2 q = *(const double2 *)(route + (size_t)(j + 1) * 8 + 6);
+                        if (cnext + pursuit_len(px, py, q.x, q.y) != cnext) { beyond = false; break; }
+                        px = q.x, py = q.y;
                     }
                 }
-                gx = lastx + (star - cnext) * ux;
-                gy = lasty + (star - cnext) * uy;
-            } else {
-                double f = 0.0;
-                if (len_il != 0.0) f = fmin(fmax((star - c_il) / len_il, 0.0), 1.0);
-                gx = lpx + f * (lqx - lpx);
-                gy = lpy + f * (lqy - lpy);
+                double gx, gy;
+                if (beyond) {
+                    if (!have_u) {                       // the direction of the last segment with a length
+                        have_u = true;
+                        double qx = lastx, qy = lasty;
+#pragma unroll 1
+                        for (int j = n - 2; j >= 0; j--) {
+                            const double2 q = *(const double2 *)(route + (size_t)j * 8 + 6);
+                            const double l = pursuit_len(q.x, q.y, qx, qy);
+                            if (l > 0.0) {
+                                ux = (qx - q.x) / l;
+                                uy = (qy - q.y) / l;
+                                break;
+                            }
+                            qx = q.x, qy = q.y;
+                        }
+                    }
+                    gx = lastx + (star - cnext) * ux;
+                    gy = lasty + (star - cnext) * uy;
+                } else {
+                    double f = 0.0;
+                    if (len_il != 0.0) f = fmin(fmax((star - c_il) / len_il, 0.0), 1.0);
+                    gx = lpx + f * (lqx - lpx);
+                    gy = lpy + f * (lqy - lpy);
+                }
+                double sp, cp;
+                sincos(pl.phi, &sp, &cp);
+                const double dx = gx - pl.x, dy = gy - pl.y;
+                const double ly = cp * dy - sp * dx;
+                const double a2 = dx * dx + dy * dy;
+                const double kap = a2 == 0.0 ? 0.0 : 2.0 * ly / a2;
+                const double spd = fmax(vt, g.vmin);
+                cl = spd - spd * kap * g.T / 2.0;
+                cr = spd + spd * kap * g.T / 2.0;
             }
-            double sp, cp;
-            sincos(pl.phi, &sp, &cp);
-            const double dx = gx - pl.x, dy = gy - pl.y;
-            const double ly = cp * dy - sp * dx;
-            const double a2 = dx * dx + dy * dy;
-            const double kap = a2 == 0.0 ? 0.0 : 2.0 * ly / a2;
-            const double spd = fmax(vt, g.vmin);
-            cl = spd - spd * kap * g.T / 2.0;
-            cr = spd + spd * kap * g.T / 2.0;
+            // 6. saturation, keeping c_L : c_R
+            if (track_saturate(cl, cr, g.wmax)) nsat++;
+            // 7. substeps: first-order wheel lag, then the exact arc
+            pl.advance(cl, cr, g.nsub, g.h);
         }
-        // 6. saturation, keeping c_L : c_R
-        if (track_saturate(cl, cr, g.wmax)) nsat++;
-        // 7. substeps: first-order wheel lag, then the exact arc
-        pl.advance(cl, cr, g.nsub, g.h);
+        if (SPLIT) __syncthreads();
     }
 
     // the final position error against the last point, and the rollout's outputs
@@ -338,11 +367,14 @@ __global__ __launch_bounds__(kTrackThreads) void k_pursuit_rollouts(PursuitArgs 
             g.part_row[gi] = mrow;
             g.part_arr[gi] = arrived;
         }
+        if (MODE == kTrackClear || SPLIT) acc.store(*c, gi);
     }
     if (g.wpr > 1) return;                              // the route's summary: k_pursuit_reduce
-    s_e[tid] = maxe;
-    s_r[tid] = inside ? mrow : -1;
-    s_a[tid] = arrived;
+    if (producer) {
+        s_e[tid] = maxe;
+        s_r[tid] = inside ? mrow : -1;
+        s_a[tid] = arrived;
+    }
     __syncthreads();
     if (inside && k == 0) {
         PursuitSummary sum;
@@ -350,6 +382,39 @@ __global__ __launch_bounds__(kTrackThreads) void k_pursuit_rollouts(PursuitArgs 
         for (int kk = 0; kk < g.K; kk++) sum.take(s_e[tid + kk], s_r[tid + kk], s_a[tid + kk], kk, g.tol);
         sum.store(g, b);
     }
+    if (MODE == kTrackClear || SPLIT) {                 // the clearance summary, over the same three columns
+        __syncthreads();
+        if (producer) {
+            s_e[tid] = acc.best;
+            s_r[tid] = inside ? acc.row : -1;
+            s_a[tid] = acc.el;
+        }
+        __syncthreads();
+        if (inside && k == 0 && c->summary()) {
+            ClearSummary cs;
+#pragma unroll 1
+            for (int kk = 0; kk < g.K; kk++) cs.take(s_e[tid + kk], s_r[tid + kk], s_a[tid + kk], kk, c->margin);
+            cs.store(*c, b);
+        }
+    }
+}
+
+template <bool EXEC>
+__global__ __launch_bounds__(kTrackThreads) void k_pursuit_rollouts(PursuitArgs g)
+{
+    pursuit_rollouts<EXEC ? kTrackExec : kTrackPlain>(g, nullptr);
+}
+
+// vap_rollout_clearance: the same march, the clearance of every executed row taken in the lane that made it
+__global__ __launch_bounds__(kTrackThreads) void k_pursuit_clearance(PursuitArgs g, TrackClear c)
+{
+    pursuit_rollouts<kTrackClear>(g, &c);
+}
+
+// the same with the clearance split off the rollout lanes (vap_track_common.h)
+__global__ __launch_bounds__(kSplitThreads) void k_pursuit_clearance_split(PursuitArgs g, TrackClear c)
+{
+    pursuit_rollouts<kTrackSplit>(g, &c);
 }
 
 // K > 256: per route, its rollouts' partials in ascending k
@@ -366,17 +431,11 @@ __global__ __launch_bounds__(64) void k_pursuit_reduce(PursuitArgs g)
     sum.store(g, b);
 }
 
-}  // namespace vap
-
-extern "C" {
-
-int vap_pursuit_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride,
-                         double time_step, const vap_pursuit *f, int K, int shared_perturb, const double *d_perturb,
-                         double *d_stats, int *d_stat_rows, double *d_worst, double *d_mean, int *d_worst_rollout,
-                         int *d_worst_row, int *d_n_exceeding, int *d_n_unfinished, int *d_route_status, long cap_exec,
-                         double *d_exec_rows, int *d_exec_counts)
+int pursuit_setup(int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride, double time_step,
+                  const vap_pursuit *f, int K, int shared_perturb, const double *d_perturb, double *d_stats, int *d_stat_rows,
+                  double *d_worst, double *d_mean, int *d_worst_rollout, int *d_worst_row, int *d_n_exceeding, int *d_n_unfinished,
+                  int *d_route_status, long cap_exec, double *d_exec_rows, int *d_exec_counts, PursuitArgs &g)
 {
-    using namespace vap;
     // host validation first: it needs no device
     if (!f) return vap_fail(VAP_ERR_INVALID, "null follower");
     if (!(f->track_width > 0.0) || !(f->lookahead > 0.0) || !(f->wheel_speed_max > 0.0) || !std::isfinite(f->track_width) ||
@@ -400,10 +459,6 @@ int vap_pursuit_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_row
         return vap_fail(VAP_ERR_INVALID, "cap_exec %ld below capacity + settle_rows = %ld", cap_exec, capacity + f->settle_rows);
     if ((((uintptr_t)d_rows | (uintptr_t)d_perturb | (uintptr_t)d_stats | (uintptr_t)d_exec_rows) & 15) != 0)
         return vap_fail(VAP_ERR_INVALID, "rows, perturbation records, stats and executed rows must be 16-byte aligned");
-    VAP_TRY(vap_set_device(ctx));
-    if (B == 0) return VAP_OK;
-
-    PursuitArgs g{};
     g.rows = d_rows;
     g.counts = d_counts;
     g.cap = capacity;
@@ -434,10 +489,18 @@ int vap_pursuit_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_row
     g.cap_exec = cap_exec;
     g.exec_rows = d_exec_rows;
     g.exec_counts = d_exec_counts;
-    const bool summary = d_worst || d_mean || d_worst_rollout || d_worst_row || d_n_exceeding || d_n_unfinished;
-    // context scratch: the routes' status words, then (K > 256 with a summary) the rollouts' partials
+    return VAP_OK;
+}
+
+int pursuit_launch(vap_ctx *ctx, PursuitArgs &g, TrackClear *clear)
+{
+    const int B = g.B, K = g.K;
+    const bool summary = g.worst || g.mean || g.worst_rollout || g.worst_row || g.n_exceeding || g.n_unfinished;
+    // context scratch: the routes' status words, then (K > 256 with a summary) the rollouts' partials, then those of the
+    // clearance summary
     const size_t status_bytes = (((size_t)B * sizeof(int)) + 15) & ~(size_t)15;
     size_t part_bytes = 0;
+    const size_t clear_bytes = clear_part_bytes(clear, B, K);
     long grid;
     if (K <= kTrackThreads) {
         g.R = kTrackThreads / K;
@@ -450,7 +513,7 @@ int vap_pursuit_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_row
         if (summary) part_bytes = (size_t)B * (size_t)K * (sizeof(double) + 2 * sizeof(int));
     }
     if (grid > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "%d routes x %d rollouts: too many workgroups for one launch", B, K);
-    VAP_TRY(ctx->ensure(ctx->track_part, status_bytes + part_bytes));
+    VAP_TRY(ctx->ensure(ctx->track_part, status_bytes + part_bytes + clear_bytes));
     g.status = (int *)ctx->track_part.ptr;
     if (part_bytes) {
         const size_t np = (size_t)B * (size_t)K;
@@ -458,9 +521,18 @@ int vap_pursuit_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_row
         g.part_row = (int *)(g.part_e + np);
         g.part_arr = g.part_row + np;
     }
+    if (clear_bytes) clear_part_place(clear, (char *)ctx->track_part.ptr + status_bytes + part_bytes, B, K);
 
     hipLaunchKernelGGL(k_pursuit_check, dim3((unsigned)B), dim3(kCheckThreads), 0, ctx->stream, g);
-    if (d_exec_rows)
+    // the clearance split off the rollout lanes where every workgroup gets a CU of its own (K = 16 at config 3: one rollout
+    // wave per SIMD, which cannot hide the clearance's loads); with more workgroups than CUs the lanes' own clearance,
+    // several workgroups to a CU, measured faster
+    const bool split = clear && grid <= track_cus(ctx->device);
+    if (split)
+        hipLaunchKernelGGL(k_pursuit_clearance_split, dim3((unsigned)grid), dim3(kSplitThreads), 0, ctx->stream, g, *clear);
+    else if (clear)
+        hipLaunchKernelGGL(k_pursuit_clearance, dim3((unsigned)grid), dim3(kTrackThreads), 0, ctx->stream, g, *clear);
+    else if (g.exec_rows)
         hipLaunchKernelGGL(k_pursuit_rollouts<true>, dim3((unsigned)grid), dim3(kTrackThreads), 0, ctx->stream, g);
     else
         hipLaunchKernelGGL(k_pursuit_rollouts<false>, dim3((unsigned)grid), dim3(kTrackThreads), 0, ctx->stream, g);
@@ -468,6 +540,26 @@ int vap_pursuit_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_row
         hipLaunchKernelGGL(k_pursuit_reduce, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, g);
     HIP_TRY(hipGetLastError());
     return VAP_OK;
+}
+
+}  // namespace vap
+
+extern "C" {
+
+int vap_pursuit_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride,
+                         double time_step, const vap_pursuit *f, int K, int shared_perturb, const double *d_perturb,
+                         double *d_stats, int *d_stat_rows, double *d_worst, double *d_mean, int *d_worst_rollout,
+                         int *d_worst_row, int *d_n_exceeding, int *d_n_unfinished, int *d_route_status, long cap_exec,
+                         double *d_exec_rows, int *d_exec_counts)
+{
+    using namespace vap;
+    PursuitArgs g{};
+    VAP_TRY(pursuit_setup(B, capacity, d_rows, d_counts, counts_stride, time_step, f, K, shared_perturb, d_perturb, d_stats,
+                          d_stat_rows, d_worst, d_mean, d_worst_rollout, d_worst_row, d_n_exceeding, d_n_unfinished, d_route_status,
+                          cap_exec, d_exec_rows, d_exec_counts, g));
+    VAP_TRY(vap_set_device(ctx));
+    if (B == 0) return VAP_OK;
+    return pursuit_launch(ctx, g, nullptr);
 }
 
 }  // extern "C"

@@ -22,6 +22,10 @@
 //            worst keeps the smallest k on a tie, the mean is one running sum).  K > 256: the rollouts' (max e_pos,
 //            row) go to context scratch and k_tracking_reduce walks them the same way, a lane per route.  No float
 //            atomics anywhere, so two calls give the same bits.
+//   modes    the march is one function template, tracking_rollouts<MODE>: plain, with the executed rows written
+//            (k_tracking_rollouts<false / true>), or with the scene clearance of every executed row taken where it would
+//            be written (k_tracking_clearance) or by further lanes of the workgroup a tile later
+//            (k_tracking_clearance_split); the last two for vap_rollout_clearance.hip, through tracking_setup / tracking_launch.
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -34,40 +38,29 @@ namespace vap {
 constexpr int kTrackRows = 512;        // staged rows per LDS buffer, over all routes of the workgroup
 constexpr int kTrackTileMax = 64;      // rows of one route per tile, at most
 
-struct TrackArgs {
-    const double *rows;       // [B][cap][8]
-    const int *counts;
-    long cap;
-    int stride, B, K, shared;
-    const double *perturb;    // [B][K][8] or [K][8]
-    double T, b, two_zeta, wmax, tol, dt, h;
-    int nsub, settle;
-    double *stats;            // [B][K][6]
-    int *stat_rows;           // [B][K][2]
-    double *worst, *mean;     // [B]
-    int *worst_rollout, *worst_row, *n_exceeding;
-    long cap_exec;
-    double *exec_rows;        // [B*K][cap_exec][8]
-    int *exec_counts;         // [B*K][2]
-    double *part_e;           // K > 256: [B][K] max e_pos (row < 0: takes no part)
-    int *part_row;
-    int R, tile, wpr;         // routes per workgroup, rows per tile, workgroups per route
-};
-
-template <bool EXEC>
-__global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g)
+// The rollouts of one workgroup.  MODE: what becomes of the executed row (kTrackPlain, kTrackExec, kTrackClear,
+// kTrackSplit); `c` is read with the last two only.
+template <int MODE>
+__device__ __forceinline__ void tracking_rollouts(const TrackArgs &g, const TrackClear *c)
 {
+    constexpr bool EXEC = MODE == kTrackExec, SPLIT = MODE == kTrackSplit;
     __shared__ __attribute__((aligned(16))) double stage[2][kTrackRows * 5];
     __shared__ int s_n[kTrackThreads];
     __shared__ int s_total;
     const int tid = threadIdx.x;
     const int R = g.R, tile = g.tile;
+    const bool producer = !SPLIT || tid < kTrackThreads;     // SPLIT: the threads behind the rollout lanes take clearances
+    double *s_pose = nullptr, *s_cap = nullptr;
+    if constexpr (SPLIT) {
+        s_pose = lds_doubles<2 * kSplitTile, 0>();
+        s_cap = lds_doubles<2 * kTrackThreads, 1>();
+    }
     // which rollout this lane walks
     const int b0 = g.wpr > 1 ? (int)(blockIdx.x / g.wpr) : (int)blockIdx.x * R;
     const int lr = g.wpr > 1 ? 0 : tid / g.K;                                  // route within the workgroup
     const int k = g.wpr > 1 ? (int)(blockIdx.x % g.wpr) * kTrackThreads + tid : tid % g.K;
     const int b = b0 + lr;
-    const bool inside = lr < R && b < g.B && k < g.K;
+    const bool inside = producer && lr < R && b < g.B && k < g.K;
     if (tid == 0) s_total = 0;
     if (tid < R) {
         int n = 0;
@@ -112,6 +105,7 @@ __global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g
     double maxe = -INFINITY, maxey = -INFINITY, maxeph = -INFINITY;
     int mrow = -1, nsat = 0;
     double *erow = EXEC && valid ? g.exec_rows + gi * (size_t)g.cap_exec * 8 : nullptr;
+    ClearAcc acc;
 
     // the loader: item j < R * tile is row j % tile of route j / tile of the tile (consecutive threads on consecutive
     // rows of a route); at most two items per thread
@@ -122,7 +116,7 @@ __global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g
         for (int i = 0; i < 2; i++) {
             const int j = tid + i * kTrackThreads;
             lv[i] = lh[i] = lw[i] = lx[i] = ly[i] = 0.0;
-            if (j < items) {
+            if (producer && j < items) {
                 const int route = j / tile, r = ti * tile + j % tile, nr = s_n[route];
                 if (nr > 0 && r < nr + g.settle) {
                     const int src = r < nr ? r : nr - 1;
@@ -141,7 +135,7 @@ __global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g
 #pragma unroll
         for (int i = 0; i < 2; i++) {
             const int j = tid + i * kTrackThreads;
-            if (j < items) {
+            if (producer && j < items) {
                 double *d = stage[buf] + (size_t)(j % tile) * 5 * R + j / tile;
                 d[0] = lv[i];
                 d[R] = lh[i];
@@ -158,8 +152,18 @@ __global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g
         store(0);
     }
     __syncthreads();
+    const int nit = SPLIT ? ntiles + 2 : ntiles;       // SPLIT: tile ti is marched, tile ti - 1 cleared, tile ti - 2 folded
 #pragma unroll 1
-    for (int ti = 0; ti < ntiles; ti++) {
+    for (int ti = 0; ti < nit; ti++) {
+        if (SPLIT && !producer) {
+            if (ti >= 1 && ti <= ntiles)
+                split_clear(*c, s_pose, s_cap, ti - 1, min(tile, wg_total - (ti - 1) * tile), tid - kTrackThreads,
+                            (int)blockDim.x - kTrackThreads);
+        } else {
+            if (SPLIT && ti >= 2)
+                split_fold(acc, s_pose, ti - 2, (ti - 2) * tile, min(tile, wg_total - (ti - 2) * tile), my_total, tid, c->margin);
+            if (SPLIT) s_cap[(size_t)(ti & 1) * kTrackThreads + tid] = acc.best;
+            if (!SPLIT || ti < ntiles) {
         const bool more = ti + 1 < ntiles;
         if (more) load(ti + 1);                        // in flight while this tile is marched
         const double *cur = stage[ti & 1] + (lr < R ? lr : 0);
@@ -168,7 +172,10 @@ __global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g
 #pragma unroll 1
         for (int t = 0; t < rend; t++) {
             const int r = r0 + t;
-            if (r >= my_total) continue;
+            if (r >= my_total) {
+                if (SPLIT) split_put(s_pose, ti & 1, t, tid, NAN, 0.0, 0.0);
+                continue;
+            }
             const double *q = cur + (size_t)t * 5 * R;
             const double vr = q[0], phr = -q[R], wref = -q[2 * R], xr = q[3 * R], yr = q[4 * R];
             // 1. errors in the body frame
@@ -184,6 +191,8 @@ __global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g
             if (fabs(eph) > maxeph) maxeph = fabs(eph);
             // 3. the executed row
             if (EXEC) pl.write_row(erow, r, g.dt);
+            if (MODE == kTrackClear) acc.take(c->s, c->margin, pl, r);
+            if (SPLIT) split_put(s_pose, ti & 1, t, tid, -track_wrap(pl.phi), pl.x, pl.y);
             // 4. RAMSETE
             double se, ce;
             sincos(eph, &se, &ce);
@@ -197,6 +206,8 @@ __global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g
             pl.advance(cl, cr, g.nsub, g.h);
         }
         if (more) store((ti + 1) & 1);
+            }
+        }
         __syncthreads();
     }
 
@@ -227,21 +238,57 @@ __global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g
             g.part_e[gi] = maxe;
             g.part_row[gi] = mrow;
         }
+        if (MODE == kTrackClear || SPLIT) acc.store(*c, gi);
     }
     if (g.wpr > 1) return;                              // the route's summary: k_tracking_reduce
     // the route's summary inside the workgroup: the stage buffers are free (the last barrier is behind every thread)
     double *s_e = stage[0];
     int *s_r = s_n;
     __syncthreads();                                    // s_n was read above
-    s_e[tid] = maxe;
-    s_r[tid] = inside ? mrow : -1;
+    if (producer) {
+        s_e[tid] = maxe;
+        s_r[tid] = inside ? mrow : -1;
+    }
+    // the clearance summary's columns lie in the other stage buffer
+    double *s_c = stage[1];
+    int *s_cr = (int *)(stage[1] + kTrackThreads), *s_ce = s_cr + kTrackThreads;
+    if ((MODE == kTrackClear || SPLIT) && producer) {
+        s_c[tid] = acc.best;
+        s_cr[tid] = inside ? acc.row : -1;
+        s_ce[tid] = acc.el;
+    }
     __syncthreads();
     if (inside && k == 0) {
         TrackSummary sum;
 #pragma unroll 1
         for (int kk = 0; kk < g.K; kk++) sum.take(s_e[tid + kk], s_r[tid + kk], kk, g.tol);
         sum.store(g, b);
+        if ((MODE == kTrackClear || SPLIT) && c->summary()) {
+            ClearSummary cs;
+#pragma unroll 1
+            for (int kk = 0; kk < g.K; kk++) cs.take(s_c[tid + kk], s_cr[tid + kk], s_ce[tid + kk], kk, c->margin);
+            cs.store(*c, b);
+        }
     }
+}
+
+template <bool EXEC>
+__global__ __launch_bounds__(kTrackThreads) void k_tracking_rollouts(TrackArgs g)
+{
+    tracking_rollouts<EXEC ? kTrackExec : kTrackPlain>(g, nullptr);
+}
+
+// vap_rollout_clearance: the same march, the clearance of every executed row taken in the lane that made it
+__global__ __launch_bounds__(kTrackThreads) void k_tracking_clearance(TrackArgs g, TrackClear c)
+{
+    tracking_rollouts<kTrackClear>(g, &c);
+}
+
+// the same with the clearance split off: kTrackThreads rollout lanes and, behind them, lanes that take the clearance of the
+// tile the rollout lanes marched before
+__global__ __launch_bounds__(kSplitThreads) void k_tracking_clearance_split(TrackArgs g, TrackClear c)
+{
+    tracking_rollouts<kTrackSplit>(g, &c);
 }
 
 // K > 256: per route, its rollouts' partials in ascending k
@@ -258,16 +305,11 @@ __global__ __launch_bounds__(64) void k_tracking_reduce(TrackArgs g)
     sum.store(g, b);
 }
 
-}  // namespace vap
-
-extern "C" {
-
-int vap_tracking_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride,
-                          double time_step, const vap_follower *f, int K, int shared_perturb, const double *d_perturb,
-                          double *d_stats, int *d_stat_rows, double *d_worst, double *d_mean, int *d_worst_rollout,
-                          int *d_worst_row, int *d_n_exceeding, long cap_exec, double *d_exec_rows, int *d_exec_counts)
+int tracking_setup(int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride, double time_step,
+                   const vap_follower *f, int K, int shared_perturb, const double *d_perturb, double *d_stats, int *d_stat_rows,
+                   double *d_worst, double *d_mean, int *d_worst_rollout, int *d_worst_row, int *d_n_exceeding, long cap_exec,
+                   double *d_exec_rows, int *d_exec_counts, TrackArgs &g)
 {
-    using namespace vap;
     // host validation first: it needs no device
     if (!f) return vap_fail(VAP_ERR_INVALID, "null follower");
     if (!(f->track_width > 0.0) || !(f->b > 0.0) || !(f->zeta > 0.0) || !(f->wheel_speed_max > 0.0) ||
@@ -288,10 +330,6 @@ int vap_tracking_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_ro
         return vap_fail(VAP_ERR_INVALID, "cap_exec %ld below capacity + settle_rows = %ld", cap_exec, capacity + f->settle_rows);
     if ((((uintptr_t)d_rows | (uintptr_t)d_perturb | (uintptr_t)d_stats | (uintptr_t)d_exec_rows) & 15) != 0)
         return vap_fail(VAP_ERR_INVALID, "rows, perturbation records, stats and executed rows must be 16-byte aligned");
-    VAP_TRY(vap_set_device(ctx));
-    if (B == 0) return VAP_OK;
-
-    TrackArgs g{};
     g.rows = d_rows;
     g.counts = d_counts;
     g.cap = capacity;
@@ -319,7 +357,16 @@ int vap_tracking_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_ro
     g.cap_exec = cap_exec;
     g.exec_rows = d_exec_rows;
     g.exec_counts = d_exec_counts;
-    const bool summary = d_worst || d_mean || d_worst_rollout || d_worst_row || d_n_exceeding;
+    return VAP_OK;
+}
+
+int tracking_launch(vap_ctx *ctx, TrackArgs &g, TrackClear *clear)
+{
+    const int B = g.B, K = g.K;
+    const bool summary = g.worst || g.mean || g.worst_rollout || g.worst_row || g.n_exceeding;
+    // context scratch, K > 256 only: the rollouts' partials of the summary, then those of the clearance summary
+    size_t part_bytes = 0;
+    const size_t clear_bytes = clear_part_bytes(clear, B, K);
     long grid;
     if (K <= kTrackThreads) {
         g.R = kTrackThreads / K;
@@ -329,17 +376,28 @@ int vap_tracking_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_ro
         g.R = 1;
         g.wpr = (K + kTrackThreads - 1) / kTrackThreads;
         grid = (long)B * g.wpr;
-        if (summary) {
-            const size_t np = (size_t)B * (size_t)K;
-            VAP_TRY(ctx->ensure(ctx->track_part, np * (sizeof(double) + sizeof(int))));
-            g.part_e = (double *)ctx->track_part.ptr;
-            g.part_row = (int *)(g.part_e + np);
-        }
+        if (summary) part_bytes = (size_t)B * (size_t)K * (sizeof(double) + sizeof(int));
+        part_bytes = (part_bytes + 15) & ~(size_t)15;
     }
     if (grid > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "%d routes x %d rollouts: too many workgroups for one launch", B, K);
+    if (part_bytes + clear_bytes) VAP_TRY(ctx->ensure(ctx->track_part, part_bytes + clear_bytes));
+    if (g.wpr > 1 && summary) {
+        g.part_e = (double *)ctx->track_part.ptr;
+        g.part_row = (int *)(g.part_e + (size_t)B * (size_t)K);
+    }
+    if (clear_bytes) clear_part_place(clear, (char *)ctx->track_part.ptr + part_bytes, B, K);
     g.tile = kTrackRows / g.R < kTrackTileMax ? kTrackRows / g.R : kTrackTileMax;
+    // the clearance split off the rollout lanes where every workgroup gets a CU of its own (K = 16 at config 3: one rollout
+    // wave per SIMD, which cannot hide the clearance's loads); with more workgroups than CUs the lanes' own clearance,
+    // several workgroups to a CU, measured faster
+    const bool split = clear && grid <= track_cus(ctx->device);
+    if (split) g.tile = g.tile < kSplitRows ? g.tile : kSplitRows;
 
-    if (d_exec_rows)
+    if (split)
+        hipLaunchKernelGGL(k_tracking_clearance_split, dim3((unsigned)grid), dim3(kSplitThreads), 0, ctx->stream, g, *clear);
+    else if (clear)
+        hipLaunchKernelGGL(k_tracking_clearance, dim3((unsigned)grid), dim3(kTrackThreads), 0, ctx->stream, g, *clear);
+    else if (g.exec_rows)
         hipLaunchKernelGGL(k_tracking_rollouts<true>, dim3((unsigned)grid), dim3(kTrackThreads), 0, ctx->stream, g);
     else
         hipLaunchKernelGGL(k_tracking_rollouts<false>, dim3((unsigned)grid), dim3(kTrackThreads), 0, ctx->stream, g);
@@ -347,6 +405,25 @@ int vap_tracking_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_ro
         hipLaunchKernelGGL(k_tracking_reduce, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, g);
     HIP_TRY(hipGetLastError());
     return VAP_OK;
+}
+
+}  // namespace vap
+
+extern "C" {
+
+int vap_tracking_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride,
+                          double time_step, const vap_follower *f, int K, int shared_perturb, const double *d_perturb,
+                          double *d_stats, int *d_stat_rows, double *d_worst, double *d_mean, int *d_worst_rollout,
+                          int *d_worst_row, int *d_n_exceeding, long cap_exec, double *d_exec_rows, int *d_exec_counts)
+{
+    using namespace vap;
+    TrackArgs g{};
+    VAP_TRY(tracking_setup(B, capacity, d_rows, d_counts, counts_stride, time_step, f, K, shared_perturb, d_perturb, d_stats,
+                           d_stat_rows, d_worst, d_mean, d_worst_rollout, d_worst_row, d_n_exceeding, cap_exec, d_exec_rows,
+                           d_exec_counts, g));
+    VAP_TRY(vap_set_device(ctx));
+    if (B == 0) return VAP_OK;
+    return tracking_launch(ctx, g, nullptr);
 }
 
 }  // extern "C"

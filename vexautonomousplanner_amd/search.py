@@ -238,7 +238,7 @@ def _sigma0(sigma0, R, W, pinned, pin_ends):
 
 def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS, samples=None, dd=None, dt=0.01,
            capacity_rows=None, others=None, others_footprint=None, follower=None, perturbations=None, config=None,
-           pinned=None, pin_ends=True, capacity=None, first_problem=0, curve_caps=None):
+           pinned=None, pin_ends=True, capacity=None, first_problem=0, curve_caps=None, robust_clearance=False):
     """Refine R routes by cross-entropy search on ``gen``'s device (a BatchedTrajectoryGenerator; its dtype is the
     waypoints').
 
@@ -255,6 +255,11 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
       follower, perturbations   a tracking.Follower or tracking.Pursuit and (K, 8) or (R * N, K, 8) records: the worst
                      tracking error of every candidate's rollouts enters the cost above config.weights.tracking_tolerance;
                      with a Pursuit a candidate with a rollout that never arrives (n_unfinished > 0) has the term +inf
+      robust_clearance   needs ``follower``: every iteration runs ``tracking.rollout_clearance`` where it ran
+                     ``tracking.rollouts``, and a candidate's clearance term is the smaller of its planned rows' clearance
+                     and the worst clearance of its disturbed rollouts (the planned one alone where no rollout has rows),
+                     so a route that clears the scene only when driven perfectly is no longer feasible.  The tracking term
+                     is unchanged.  False: the sequence without it
       config         a SearchConfig
       curve_caps     a drive.CurveCaps: every iteration's velocity rows are recomputed under these caps
                      (``gen.apply_curve_caps``) between ``profile`` and ``time_profile``; None: the sequence without it
@@ -275,6 +280,8 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
         raise ValueError("give exactly one of samples= or dd=")
     if follower is not None and perturbations is None:
         raise ValueError("follower needs perturbations (tracking.sample_perturbations)")
+    if robust_clearance and follower is None:
+        raise ValueError("robust_clearance needs a follower (and perturbations): it scores the rollouts' clearance")
     dev = gen.device
     s = np.asarray(seeds.detach().cpu().numpy() if isinstance(seeds, torch.Tensor) else seeds, dtype=np.float64)
     if s.ndim == 2:
@@ -311,8 +318,14 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
             fp.conflicts(tp["rows"], tp["counts"], footprint, others["rows"], others["counts"], others_footprint,
                          margin=wts.conflict_margin, out=conf, ctx=gen.ctx)
             terms["conflict_clearance"] = conf["min_clearance"]
-        if follower is not None:
+        if robust_clearance:
+            tracking.rollout_clearance(tp["rows"], tp["counts"], follower, perturbations, footprint, scene,
+                                       margin=wts.clearance_margin, time_step=dt, out=trk, ctx=gen.ctx)
+            wc = trk["worst_clearance"]
+            terms["clearance"] = torch.where(torch.isnan(wc), clr["min_clearance"], torch.minimum(clr["min_clearance"], wc))
+        elif follower is not None:
             tracking.rollouts(tp["rows"], tp["counts"], follower, perturbations, time_step=dt, out=trk, ctx=gen.ctx)
+        if follower is not None:
             # a pure-pursuit candidate whose rollouts do not all arrive is never an elite: its tracking term is +inf
             terms["tracking_worst"] = torch.where(trk["n_unfinished"] > 0, inf, trk["worst"]) if pursuit else trk["worst"]
         update(wp, R, weights=wts, counts=tp["counts"], time_step=dt, meta=prof["meta"], flags=prof["flags"], mean=mean,
@@ -324,4 +337,6 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
            "mean": mean, "sigma": sigma, "cost": upd["cost"].view(R, N), "order": upd["order"]}
     if pursuit:
         out["n_unfinished"] = trk["n_unfinished"].view(R, N)
+    if robust_clearance:
+        out["n_colliding"] = trk["n_colliding"].view(R, N)
     return out

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._call import buffers, context_for, device_array, ptr, time_rows
+from ._call import buffers, context_for, device_array, dptr, ptr, time_rows
 
 MAX_ROLLOUTS = 4096
 NOMINAL = (0.0, 0.0, 0.0, 1.0, 1.0, 1.0, 0.0, 0.0)      # dx, dy, dphi, gain_left, gain_right, track_scale, tau, reserved
@@ -150,6 +150,52 @@ PURSUIT_STAT_COLUMNS = ("max_cross_track", "final_error", "arrival_time", "looka
 PURSUIT_ROW_COLUMNS = ("max_row", "saturated_rows", "arrived_row", "closest_segment")
 
 
+def _checked(follower, time_step):
+    """(is it a Pursuit, time_step as a float) of a validated follower and time step."""
+    if isinstance(follower, Pursuit):
+        pursuit = True
+    elif isinstance(follower, Follower):
+        pursuit = False
+    else:
+        raise TypeError("follower must be a tracking.Follower or a tracking.Pursuit")
+    follower.validate()
+    time_step = float(time_step)
+    if not (time_step > 0 and np.isfinite(time_step)):
+        raise ValueError(f"time_step must be positive and finite (got {time_step!r})")
+    return pursuit, time_step
+
+
+def _records(perturbations, B, dev):
+    """The records on ``dev`` as (tensor, shared, K): (B, K, 8), or (K, 8) shared by every route, K in 1..4096."""
+    pert = device_array(perturbations, dev, torch.float64)
+    shared = pert.dim() == 2
+    if pert.dim() not in (2, 3) or pert.shape[-1] != 8 or (not shared and pert.shape[0] != B):
+        raise ValueError(f"perturbations must be ({B}, K, 8) or (K, 8), got {tuple(pert.shape)}")
+    K = int(pert.shape[-2])
+    if not 1 <= K <= MAX_ROLLOUTS:
+        raise ValueError(f"K = {K} rollouts per route (1..{MAX_ROLLOUTS})")
+    return pert, shared, K
+
+
+def _follower_shapes(B, K, pursuit):
+    """The follower's own outputs: name -> (shape, dtype)."""
+    shapes = {"stats": ((B, K, 6), torch.float64), "stat_rows": ((B, K, 4 if pursuit else 2), torch.int32), "worst": ((B,), torch.float64),
+              "mean": ((B,), torch.float64), "worst_rollout": ((B,), torch.int32), "worst_row": ((B,), torch.int32),
+              "n_exceeding": ((B,), torch.int32)}
+    if pursuit:
+        shapes["n_unfinished"] = ((B,), torch.int32)
+        shapes["route_status"] = ((B,), torch.int32)
+    return shapes
+
+
+def _follower_views(res, pursuit):
+    """The named columns of stats and stat_rows, as views."""
+    for i, name in enumerate(PURSUIT_STAT_COLUMNS if pursuit else STAT_COLUMNS):
+        res[name] = res["stats"][..., i]
+    for i, name in enumerate(PURSUIT_ROW_COLUMNS if pursuit else ("max_row", "saturated_rows")):
+        res[name] = res["stat_rows"][..., i]
+
+
 def rollouts(rows, counts, follower, perturbations, time_step=0.01, executed=False, out=None, device=0, ctx=None):
     """Tracking rollouts of a batch of time-domain rows (vap_tracking_rollouts).
 
@@ -177,32 +223,12 @@ def rollouts(rows, counts, follower, perturbations, time_step=0.01, executed=Fal
     stat_rows (B, K, 4) with views max_row, saturated_rows, arrived_row (-1: never), closest_segment; per route worst,
     mean, worst_rollout, worst_row, n_exceeding (over the cross-track error), n_unfinished (valid rollouts that never
     arrived) and route_status (bit 0: a negative speed, bit 1: a non-finite x, y or v; such a route gives NaN / -1 / 0)."""
-    if isinstance(follower, Pursuit):
-        pursuit = True
-    elif isinstance(follower, Follower):
-        pursuit = False
-    else:
-        raise TypeError("follower must be a tracking.Follower or a tracking.Pursuit")
-    follower.validate()
-    time_step = float(time_step)
-    if not (time_step > 0 and np.isfinite(time_step)):
-        raise ValueError(f"time_step must be positive and finite (got {time_step!r})")
+    pursuit, time_step = _checked(follower, time_step)
     rows, counts, single, dev = time_rows(rows, counts, None, device)
     B, cap = int(rows.shape[0]), int(rows.shape[1])
-    pert = device_array(perturbations, dev, torch.float64)
-    shared = pert.dim() == 2
-    if pert.dim() not in (2, 3) or pert.shape[-1] != 8 or (not shared and pert.shape[0] != B):
-        raise ValueError(f"perturbations must be ({B}, K, 8) or (K, 8), got {tuple(pert.shape)}")
-    K = int(pert.shape[-2])
-    if not 1 <= K <= MAX_ROLLOUTS:
-        raise ValueError(f"K = {K} rollouts per route (1..{MAX_ROLLOUTS})")
+    pert, shared, K = _records(perturbations, B, dev)
     cap_exec = cap + int(follower.settle_rows)
-    shapes = {"stats": ((B, K, 6), torch.float64), "stat_rows": ((B, K, 4 if pursuit else 2), torch.int32), "worst": ((B,), torch.float64),
-              "mean": ((B,), torch.float64), "worst_rollout": ((B,), torch.int32), "worst_row": ((B,), torch.int32),
-              "n_exceeding": ((B,), torch.int32)}
-    if pursuit:
-        shapes["n_unfinished"] = ((B,), torch.int32)
-        shapes["route_status"] = ((B,), torch.int32)
+    shapes = _follower_shapes(B, K, pursuit)
     if executed:
         shapes["rows"] = ((B * K, cap_exec, 8), torch.float64)
         shapes["counts"] = ((B * K, 2), torch.int32)
@@ -216,20 +242,14 @@ def rollouts(rows, counts, follower, perturbations, time_step=0.01, executed=Fal
             ptr(res["stats"]), ptr(res["stat_rows"]), ptr(res["worst"]), ptr(res["mean"]), ptr(res["worst_rollout"]),
             ptr(res["worst_row"]), ptr(res["n_exceeding"]), ptr(res["n_unfinished"]), ptr(res["route_status"]), cap_exec,
             ptr(res.get("rows") if executed else None), ptr(res.get("counts") if executed else None)), "vap_pursuit_rollouts")
-        for i, name in enumerate(PURSUIT_STAT_COLUMNS):
-            res[name] = res["stats"][..., i]
-        for i, name in enumerate(PURSUIT_ROW_COLUMNS):
-            res[name] = res["stat_rows"][..., i]
+        _follower_views(res, True)
         return _single(res) if single else res
     _lib.check(ctx._L.vap_tracking_rollouts(
         ctx.handle, B, cap, ptr(rows), ptr(counts), int(counts.shape[1]), time_step, C.byref(fs), K, int(shared), ptr(pert),
         ptr(res["stats"]), ptr(res["stat_rows"]), ptr(res["worst"]), ptr(res["mean"]), ptr(res["worst_rollout"]),
         ptr(res["worst_row"]), ptr(res["n_exceeding"]), cap_exec, ptr(res.get("rows") if executed else None),
         ptr(res.get("counts") if executed else None)), "vap_tracking_rollouts")
-    for i, name in enumerate(STAT_COLUMNS):
-        res[name] = res["stats"][..., i]
-    res["max_row"] = res["stat_rows"][..., 0]
-    res["saturated_rows"] = res["stat_rows"][..., 1]
+    _follower_views(res, False)
     return _single(res) if single else res
 
 
@@ -238,3 +258,62 @@ def _single(res):
         if k not in ("rows", "counts"):
             res[k] = res[k][0]
     return res
+
+
+CLEAR_ROW_COLUMNS = ("clear_min_row", "clear_min_element", "clear_first_row", "clear_n_below")
+
+
+def rollout_clearance(rows, counts, follower, perturbations, footprint, scene, margin=0.0, time_step=0.01, out=None, device=0,
+                      ctx=None, cull=True):
+    """Scene clearance of the disturbed rollouts (vap_rollout_clearance): does the robot still miss the post when it
+    starts an inch off, one side runs weak and the drive lags?  ``rollouts(executed=True)`` followed by
+    ``footprint.clearance`` answers that through B * K * (capacity + settle_rows) executed rows in memory; this call runs
+    the same rollouts and takes the clearance of every executed row while it is on the chip.  No executed rows exist.
+
+      rows, counts, follower, perturbations, time_step   as in ``rollouts`` (a Follower or a Pursuit)
+      footprint, scene, margin, cull                     as in ``footprint.clearance``; a rollout whose clearance is below
+                                                         ``margin`` counts as colliding
+      out            optional dict that keeps the call's buffers between calls, as in ``rollouts``
+    Returns everything ``rollouts`` returns for that follower (the same bits), and: clearance (B, K), the smallest
+    clearance over the rollout's executed rows; clear_rows (B, K, 4) with views clear_min_row (the first row at it),
+    clear_min_element (footprint.Scene.element_name), clear_first_row (the first row below ``margin``, -1: none),
+    clear_n_below; per route (B,) worst_clearance (the smallest over k; the smallest k on a tie), worst_clear_rollout,
+    worst_clear_row, worst_clear_element, mean_clearance, n_colliding (rollouts below ``margin``) and n_clear_valid (the
+    rollouts that have rows: n_colliding / n_clear_valid is the collision share).  Per rollout these are the numbers
+    ``footprint.clearance`` gives for the executed rows of ``rollouts(executed=True)``, bit for bit.  A rollout without
+    rows gives NaN / -1 / 0, a route without one NaN / -1 / 0 / 0.  A single trajectory gives (K, ...) and 0-d tensors.
+    Work runs on torch's current stream and is not synchronised."""
+    from . import footprint as fp
+    pursuit, time_step = _checked(follower, time_step)
+    if not isinstance(scene, fp.Scene):
+        raise TypeError("scene must be a footprint.Scene")
+    foot = fp.convex_polygon(footprint, "footprint")
+    margin = float(margin)
+    if not np.isfinite(margin):
+        raise ValueError(f"margin must be finite (got {margin!r})")
+    rows, counts, single, dev = time_rows(rows, counts, None, device)
+    B, cap = int(rows.shape[0]), int(rows.shape[1])
+    pert, shared, K = _records(perturbations, B, dev)
+    shapes = _follower_shapes(B, K, pursuit)
+    shapes.update(clearance=((B, K), torch.float64), clear_rows=((B, K, 4), torch.int32), worst_clearance=((B,), torch.float64),
+                  worst_clear_rollout=((B,), torch.int32), worst_clear_row=((B,), torch.int32),
+                  worst_clear_element=((B,), torch.int32), mean_clearance=((B,), torch.float64), n_colliding=((B,), torch.int32),
+                  n_clear_valid=((B,), torch.int32))
+    bufs = buffers(out, shapes, dev)       # the call's buffers; the returned dict is built apart from it
+    res = {k: bufs[k] for k in shapes}
+    ctx = context_for(dev, ctx)
+    ctx.set_option(_lib.OPT_FOOTPRINT_CULL, 1 if cull else 0)
+    fs = follower.as_struct()
+    _lib.check(ctx._L.vap_rollout_clearance(
+        ctx.handle, _lib.FOLLOWER_PURSUIT if pursuit else _lib.FOLLOWER_RAMSETE, C.cast(C.pointer(fs), C.c_void_p), B, cap,
+        ptr(rows), ptr(counts), int(counts.shape[1]), time_step, K, int(shared), ptr(pert), len(foot), dptr(foot),
+        dptr(scene.field), scene.n_polygons, scene.poly_start.ctypes.data_as(_lib.ip), dptr(scene.poly_xy), scene.n_circles,
+        dptr(scene.circles), margin, ptr(res["stats"]), ptr(res["stat_rows"]), ptr(res["worst"]), ptr(res["mean"]),
+        ptr(res["worst_rollout"]), ptr(res["worst_row"]), ptr(res["n_exceeding"]), ptr(res.get("n_unfinished")),
+        ptr(res.get("route_status")), ptr(res["clearance"]), ptr(res["clear_rows"]), ptr(res["worst_clearance"]),
+        ptr(res["worst_clear_rollout"]), ptr(res["worst_clear_row"]), ptr(res["worst_clear_element"]), ptr(res["mean_clearance"]),
+        ptr(res["n_colliding"]), ptr(res["n_clear_valid"])), "vap_rollout_clearance")
+    _follower_views(res, pursuit)
+    for i, name in enumerate(CLEAR_ROW_COLUMNS):
+        res[name] = res["clear_rows"][..., i]
+    return _single(res) if single else res
