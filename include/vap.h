@@ -1285,6 +1285,68 @@ int vap_drive_audit(vap_ctx *ctx, int B, long capacity, const double *d_rows, co
                     double time_step, const vap_drive_limits *lim, double *d_peak, int *d_peak_row, int *d_n_over,
                     int *d_first_over, int *d_route_status, double *d_wheel_rows);
 
+/* ---- range-sensor readings of time-domain rows against the scene ---------------------------------------------------
+ * Everything above takes the pose for known.  On a robot it comes from dead reckoning, and the usual cure is a wall-facing
+ * distance sensor that resets one coordinate when it sees a wall it can trust.  This call says what such a sensor would read
+ * at every row, and where along a route a reset is possible at all.  Units: feet, the rows' own frame.  The whole call is fp64.
+ *
+ *   rows      d_rows [B][capacity][8], d_counts with counts_stride, exactly as vap_footprint_clearance takes them (counts
+ *             clamped to [0, capacity]; only columns 4, 6, 7 are read).  Pose p = (x, y), phi = -heading, a body point v sits
+ *             at p + R(phi) v.
+ *   scene     h_field (or NULL), polygons, circles: vap_footprint_clearance's, the same validation, limits and status codes.
+ *   sensors   h_sensors [n_sens][8] = {mx, my, ux, uy, r_min, r_max, min_cos, 0}, n_sens 1..8: the mount point in the body
+ *             frame (ft); the beam direction as a body-frame unit vector, |hypot(ux, uy) - 1| <= 1e-12 (the caller gives it,
+ *             nothing is renormalised); the valid window 0 <= r_min <= r_max (ft); min_cos in [0, 1], the smallest accepted
+ *             cosine of the incidence angle.
+ *   partners  optional (Bo = 0, cap_o = 0 or NULL rows: none): d_rows_o [Bo][cap_o][8], d_counts_o with stride_o, one footprint
+ *             h_foot_o [n_foot_o][2] (convex, counter-clockwise, 3..16 vertices), shift_rows.  Bo <= 16.  Every route of the call
+ *             sees every partner; partner o at row r stands at its own row clamp(r - shift_rows, 0, n_o - 1)
+ *             (vap_footprint_conflicts' parking); a partner without rows is absent.  Both sides are on the same time step (the
+ *             caller guarantees it).
+ *   reading   (row r, sensor s).  The beam is a single ray: it has no cone, the robot's own body is not seen, and motion
+ *             between rows is not swept.  With c, s = cos phi, sin phi taken once per row: origin o = p + R(phi)(mx, my),
+ *             direction u = (c ux - s uy, s ux + c uy).  Candidates in this order; a later one replaces the best only on a
+ *             strictly smaller t, so the first in this order wins a tie:
+ *             1. wall, element -1: only with a field and only if o lies inside or on the box.  For u.x > 0 t = (xmax - o.x) /
+ *                u.x, for u.x < 0 t = (xmin - o.x) / u.x, likewise in y; the smaller wins, on a tie the x side.  face = 0 xmin,
+ *                1 ymin, 2 xmax, 3 ymax; cos_inc = |u.x| or |u.y|.
+ *             2. polygons k = 0 .. n_poly - 1, element k, edges j ascending, face = j.  For the edge a -> a + e: den = u x e
+ *                (0: no candidate), t = ((a - o) x e) / den, w = ((a - o) x u) / den; a candidate if t >= 0 and 0 <= w <= 1;
+ *                cos_inc = |u . n|, n the edge's unit normal.  Any edge counts: an origin inside a polygon reads the distance
+ *                to its way out.
+ *             3. circles, element n_poly + k, face 0.  d = o - centre, b = d . u, q = d . d - r^2, disc = b^2 - q (< 0: no
+ *                candidate); t = -b - sqrt(disc), if that is < 0 t = -b + sqrt(disc), if still < 0 no candidate; cos_inc =
+ *                |u . (o + t u - centre)| / r.
+ *             4. partners, element n_poly + n_circle + o: the posed footprint's edges as a polygon's, face = edge index.
+ *             A comparison with a NaN is false: NaN candidates take part in nothing.
+ *   status    in priority order: 6 bad pose (non-finite x, y or heading), 1 no candidate, 5 the nearest is a partner (blocked),
+ *             2 t < r_min, 3 t > r_max, 4 cos_inc < min_cos, 0 valid.
+ *   outputs   any pointer may be NULL (nothing is written for it).
+ *             per reading [B][capacity][n_sens]: d_range (t wherever a candidate exists, whatever the status; NaN for status
+ *             1 and 6 and for rows >= count), d_cos_incidence (the same NaN rule), d_code (int32) = status | face << 4 |
+ *             (element + 2) << 12, the element field 0 when there is none; -1 for rows >= count.
+ *             per route and sensor: d_status_counts [B][n_sens][8] (rows per status 0..6, slot 7 = 0), d_range_minmax
+ *             [B][n_sens][2] (smallest and largest valid range, NaN if none).
+ *             per route and channel: d_channels [B][n_sens + 2][5] = {n_ok, first_ok, last_ok, gap_rows, gap_row}.  Channel
+ *             s < n_sens: sensor s valid at this row; channel n_sens: some sensor valid on a wall face 0 or 2 (x observable);
+ *             channel n_sens + 1: the same for faces 1 or 3 (y observable).  gap_rows: the longest run of consecutive rows of
+ *             [0, n) that are not ok, leading and trailing runs included (0 if every row is ok, n if none is); gap_row: the
+ *             first row of the earliest longest run, -1 when gap_rows = 0.  A route with n = 0 gets 0 counts, NaN and
+ *             {0, -1, -1, 0, -1}.
+ * VAP_ERR_INVALID: n_sens outside 1..8, a non-finite sensor entry or one outside the bounds above, a null rows or counts
+ * pointer with B > 0, a bad shape or stride, a partner footprint that vap_footprint_clearance would refuse, every scene error
+ * of that call.  VAP_ERR_UNSUPPORTED: its scene limits, more than 16 partners, a capacity above INT_MAX - 2048.  B = 0 is a
+ * no-op.  No pointer has an alignment requirement beyond its type's.  VAP_OPT_FOOTPRINT_CULL governs culling (an element is
+ * skipped only when its bounding circle, with the rounding slack of vap_footprint_clearance, cannot hold a strictly nearer hit);
+ * on and off give the same bits.  Every summary is an integer or a min / max, and the gap is combined with an associative
+ * record, so the result does not depend on how the rows are tiled; no float atomics: two calls on the same inputs give the same
+ * bits.  Works on the context's stream and does not synchronise. */
+int vap_range_readings(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride, int n_sens,
+                       const double *h_sensors, const double *h_field, int n_poly, const int *h_poly_start, const double *h_poly_xy,
+                       int n_circle, const double *h_circles, int Bo, long cap_o, const double *d_rows_o, const int *d_counts_o,
+                       int stride_o, int n_foot_o, const double *h_foot_o, int shift_rows, double *d_range, double *d_cos_incidence,
+                       int *d_code, int *d_status_counts, double *d_range_minmax, int *d_channels);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,465 @@
+"""GPU: range-sensor readings (vap_range_readings, sensors.readings, BatchedTrajectoryGenerator.range_readings) against the
+NumPy reference of tests/range_ref.py on the seeded inputs of tests/range_cases.py: exact wall cases, random scenes, the
+tilings of the gap record, scenes on both sides of the LDS budget, partners, the producers' own rows, the C-ABI's refusals.
+
+A reading is excused from the comparison when the reference's decision margin is below AMBIGUOUS (1e-9) or cos_inc < 0.1
+(range_ref.py); on every other reading status, face and element are equal and range and cos_incidence agree within TOL =
+1e-12.  Excused readings are at most 1 % of a test's readings and touch at most 10 % of its routes; test_range_cpu.py
+holds the reference alone to that on the same inputs.  Every comparison prints its worst values on a line starting with
+"RANGE"."""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+import golden_util as gu
+import range_cases as rc
+import range_ref as rr
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-12
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SUMMARY_KEYS = ("status_counts", "range_minmax", "channels")
+ROW_KEYS = ("range", "cos_incidence", "code")
+
+
+@pytest.fixture(scope="module")
+def torch_mod():
+    import torch
+    assert torch.cuda.is_available()
+    return torch
+
+
+def sn():
+    from vexautonomousplanner_amd import sensors
+    return sensors
+
+
+def scene_of(case_scene):
+    from vexautonomousplanner_amd import footprint
+    return footprint.Scene(field=case_scene["field"], polygons=case_scene["polygons"], circles=case_scene["circles"])
+
+
+def run(case, shift_rows=0, per_row=True, cull=True, device_input=True, stride=1, **kw):
+    import torch
+    rows, counts = case["rows"], case["counts"]
+    if stride > 1:
+        c = np.full((len(counts), stride), -77, dtype=np.int32)
+        c[:, 0] = counts
+        counts = c
+    others = {}
+    if "others" in case:
+        others = dict(others=case["others"], others_counts=case["others_counts"], others_footprint=case["others_foot"])
+    if device_input:
+        rows, counts = torch.tensor(rows, device="cuda:0"), torch.tensor(counts, device="cuda:0")
+        if others:
+            others["others"] = torch.tensor(others["others"], device="cuda:0")
+    res = sn().readings(rows, counts, case["sensors"], scene_of(case["scene"]), shift_rows=shift_rows, per_row=per_row, cull=cull,
+                        **others, **kw)
+    torch.cuda.synchronize()
+    return res
+
+
+def bits(res, keys=SUMMARY_KEYS + ROW_KEYS):
+    return {k: res[k].cpu().numpy().view(np.int64 if res[k].dtype.itemsize == 8 else np.int32).copy() for k in keys if k in res}
+
+
+def same_bits(a, b, keys):
+    a, b = bits(a, keys), bits(b, keys)
+    return all(np.array_equal(a[k], b[k]) for k in keys)
+
+
+class Tally:
+    def __init__(self):
+        self.readings = self.excused = self.routes = self.touched = 0
+        self.worst_t = self.worst_cos = 0.0
+
+    def check_caps(self, what):
+        print(f"RANGE {what}: {self.readings} readings, {self.excused} excused, {self.touched} of {self.routes} routes touched, "
+              f"worst |range - reference| {self.worst_t:.3e} ft, worst |cos - reference| {self.worst_cos:.3e}")
+        assert self.excused <= rc.MAX_EXCUSED * self.readings, what
+        assert self.touched <= rc.MAX_TOUCHED * self.routes, what
+
+
+def own_summaries(code, rng, counts, ns):
+    """The summaries recomputed from the kernel's own per-reading outputs."""
+    st, fa, el = sn().unpack(code)
+    ref = {"status": st.astype(np.int64), "face": fa.astype(np.int64), "element": el.astype(np.int64), "t": rng,
+           "excused": np.zeros(code.shape, dtype=bool), "counts": np.asarray(counts)}
+    return rr.summaries(ref)
+
+
+def compare(res, ref, tally, what):
+    """Per-reading outputs and summaries of one call against the reference."""
+    summ = rr.summaries(ref)
+    counts, live, exc = ref["counts"], ref["live"], ref["excused"]
+    B, cap, ns = ref["status"].shape
+    got_sc, got_mm, got_ch = (res[k].cpu().numpy() for k in SUMMARY_KEYS)
+    assert got_sc.shape == (B, ns, 8) and got_mm.shape == (B, ns, 2) and got_ch.shape == (B, ns + 2, 5)
+    if "code" in res:
+        code, rng, cosi = res["code"].cpu().numpy(), res["range"].cpu().numpy(), res["cos_incidence"].cpu().numpy()
+        assert code.shape == (B, cap, ns)
+        past = ~live
+        assert (code[past] == -1).all() and np.isnan(rng[past]).all() and np.isnan(cosi[past]).all(), what
+        st, fa, el = sn().unpack(code)
+        keep = live[:, :, None] & ~exc
+        for name, got, want in (("status", st, ref["status"]), ("face", fa, ref["face"]), ("element", el, ref["element"])):
+            bad = np.argwhere(keep & (got != want))
+            assert not len(bad), (what, name, bad[0], got[tuple(bad[0])], want[tuple(bad[0])], ref["margin"][tuple(bad[0])])
+        for name, got, want in (("range", rng, ref["t"]), ("cos", cosi, ref["cos"])):
+            assert np.array_equal(np.isnan(got[keep]), np.isnan(want[keep])), (what, name)
+            d = np.abs(got - want)
+            d = np.where(keep & ~np.isnan(want), d, 0.0)
+            bad = np.argwhere(d > TOL)
+            assert not len(bad), (what, name, bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
+            if name == "range":
+                tally.worst_t = max(tally.worst_t, float(d.max()) if d.size else 0.0)
+            else:
+                tally.worst_cos = max(tally.worst_cos, float(d.max()) if d.size else 0.0)
+        # the call's own summaries are those of its own readings, on every route, touched or not
+        own = own_summaries(code, rng, counts, ns)
+        assert np.array_equal(got_sc, own["status_counts"]) and np.array_equal(got_ch, own["channels"]), what
+        assert np.array_equal(np.isnan(got_mm), np.isnan(own["minmax"])) and np.array_equal(np.nan_to_num(got_mm), np.nan_to_num(own["minmax"])), what
+    touched = summ["touched"]
+    for b in range(B):
+        for s in range(ns + 2):
+            if touched[b, s]:
+                continue
+            assert got_ch[b, s].tolist() == summ["channels"][b, s].tolist(), (what, b, s, got_ch[b, s], summ["channels"][b, s])
+            if s < ns:
+                assert got_sc[b, s].tolist() == summ["status_counts"][b, s].tolist(), (what, b, s, got_sc[b, s], summ["status_counts"][b, s])
+                want = summ["minmax"][b, s]
+                if np.isnan(want[0]):
+                    assert np.isnan(got_mm[b, s]).all(), (what, b, s)
+                else:
+                    assert np.max(np.abs(got_mm[b, s] - want)) <= TOL, (what, b, s, got_mm[b, s], want)
+        if counts[b] == 0:
+            assert not got_sc[b].any() and np.isnan(got_mm[b]).all() and (got_ch[b] == [0, -1, -1, 0, -1]).all(), (what, b)
+    tally.readings += int(live.sum()) * ns
+    tally.excused += int(exc.sum())
+    tally.routes += B
+    tally.touched += int(touched.any(axis=1).sum())
+    return summ
+
+
+# ---- 1. exact ---------------------------------------------------------------------------------------------------------------
+def test_exact_walls_bit_for_bit(torch_mod):
+    """phi = 0, cardinal beams, walls only: the range is the hand value, bit for bit."""
+    field = (-5.5, -4.25, 6.125, 3.75)
+    mounts = [(0.6, 0.1), (-0.55, 0.0), (0.05, 0.45), (0.0, -0.6)]
+    dirs = [(1.0, 0.0), (-1.0, 0.0), (0.0, 1.0), (0.0, -1.0)]
+    sens = np.array([[mx, my, ux, uy, 0.0, 50.0, 0.0, 0.0] for (mx, my), (ux, uy) in zip(mounts, dirs)])
+    rng = np.random.default_rng(3)
+    rows = np.zeros((3, 70, 8))
+    rows[:, :, 6] = rng.uniform(-4.0, 4.0, (3, 70))
+    rows[:, :, 7] = rng.uniform(-3.0, 3.0, (3, 70))
+    counts = np.array([70, 1, 66], dtype=np.int32)
+    case = {"scene": {"field": field, "polygons": [], "circles": np.zeros((0, 3))}, "rows": rows, "counts": counts, "sensors": sens}
+    res = run(case)
+    got, code = res["range"].cpu().numpy(), res["code"].cpu().numpy()
+    x, y = rows[:, :, 6], rows[:, :, 7]
+    want = np.stack([(field[2] - (x + mounts[0][0])) / 1.0, (field[0] - (x + mounts[1][0])) / -1.0,
+                     (field[3] - (y + mounts[2][1])) / 1.0, (field[1] - (y + mounts[3][1])) / -1.0], axis=2)
+    for b in range(3):
+        n = counts[b]
+        assert np.array_equal(got[b, :n], want[b, :n]), b
+        st, fa, el = sn().unpack(code[b, :n])
+        assert (st == 0).all() and (el == -1).all() and (fa == [2, 0, 3, 1]).all(), b
+        assert (res["cos_incidence"][b, :n].cpu().numpy() == 1.0).all()
+        assert np.isnan(got[b, n:]).all() and (code[b, n:] == -1).all()
+    ch = res["channels"].cpu().numpy()
+    assert ch[0].tolist() == [[70, 0, 69, 0, -1]] * 6 and ch[1].tolist() == [[1, 0, 0, 0, -1]] * 6
+
+
+# ---- 2. random --------------------------------------------------------------------------------------------------------------
+def test_random_scenes_against_the_reference(torch_mod):
+    tally = Tally()
+    seen = set()
+    for i, seed in enumerate(rc.RANDOM_SEEDS):
+        case = rc.random_case(seed)
+        ref = rc.reference(rr, case)
+        seen |= set(np.unique(ref["status"][ref["live"]]).tolist())
+        stride = 2 + i % 2
+        res = run(case, stride=stride)
+        compare(res, ref, tally, f"random {seed}")
+        # culling off, summaries only, host input, a second call: the same bytes
+        assert same_bits(res, run(case, stride=stride, cull=False), SUMMARY_KEYS + ROW_KEYS), seed
+        assert same_bits(res, run(case, stride=5 - stride, per_row=False), SUMMARY_KEYS), seed
+        assert same_bits(res, run(case, stride=stride, device_input=False), SUMMARY_KEYS + ROW_KEYS), seed
+        assert same_bits(res, run(case, stride=stride), SUMMARY_KEYS + ROW_KEYS), seed
+    assert {0, 1, 2, 3, 4} <= seen, seen
+    tally.check_caps("random")
+
+
+def raw_call(torch, case, out_range, out_cos, out_code, out_sc, out_mm, out_ch, B=None, n_sens=None, sens=None, rows=None, Bo=0,
+             ctx=None):
+    """vap_range_readings through ctypes, on pointers of the caller's choosing.  Returns the status."""
+    from vexautonomousplanner_amd import _lib
+    L = _lib.lib()
+    ctx = ctx or _lib.default_context(0)
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    sc = scene_of(case["scene"])
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    dp = lambda a: a.ctypes.data_as(_lib.dp) if a is not None and a.size else None
+    sens = np.ascontiguousarray(case["sensors"] if sens is None else sens, dtype=np.float64)
+    d_rows = torch.tensor(case["rows"], device="cuda:0") if rows is None else rows
+    d_counts = torch.tensor(case["counts"], device="cuda:0")
+    foot = np.ascontiguousarray(rc.SQUARE)
+    o_rows = torch.zeros((max(Bo, 1), 4, 8), dtype=torch.float64, device="cuda:0")
+    o_counts = torch.ones((max(Bo, 1),), dtype=torch.int32, device="cuda:0")
+    status = L.vap_range_readings(
+        ctx.handle, len(case["counts"]) if B is None else B, case["rows"].shape[1], None if rows == "null" else p(d_rows), p(d_counts), 1,
+        len(sens) if n_sens is None else n_sens, dp(sens), dp(sc.field), sc.n_polygons, sc.poly_start.ctypes.data_as(_lib.ip),
+        dp(sc.poly_xy), sc.n_circles, dp(sc.circles), Bo, 4 if Bo else 0, p(o_rows) if Bo else None, p(o_counts) if Bo else None, 1,
+        4 if Bo else 0, dp(foot) if Bo else None, 0, p(out_range), p(out_cos), p(out_code), p(out_sc), p(out_mm), p(out_ch))
+    torch.cuda.synchronize()
+    return status
+
+
+def test_nothing_is_written_past_the_buffers(torch_mod):
+    """Every output inside a larger, pre-filled allocation: the guard words behind it stay as they were, and each output
+    pointer may be NULL on its own."""
+    torch = torch_mod
+    case = rc.random_case(rc.RANDOM_SEEDS[0])
+    B, cap, ns = len(case["counts"]), case["rows"].shape[1], 4
+    sizes = {"range": B * cap * ns, "cos": B * cap * ns, "code": B * cap * ns, "sc": B * ns * 8, "mm": B * ns * 2, "ch": B * (ns + 2) * 5}
+    GUARD = 64
+
+    def fresh():
+        return {k: (torch.full((n + GUARD,), -12345.0, dtype=torch.float64, device="cuda:0") if k in ("range", "cos", "mm")
+                    else torch.full((n + GUARD,), -12345, dtype=torch.int32, device="cuda:0")) for k, n in sizes.items()}
+    full = fresh()
+    assert raw_call(torch, case, *(full[k] for k in sizes)) == 0
+    for k, n in sizes.items():
+        assert (full[k][n:] == -12345).all().item(), k
+        assert not (full[k][:n] == -12345).any().item(), k
+    for skip in sizes:
+        part = fresh()
+        assert raw_call(torch, case, *(None if k == skip else part[k] for k in sizes)) == 0
+        assert (part[skip] == -12345).all().item(), skip
+        for k, n in sizes.items():
+            if k != skip:
+                a, b = part[k][:n].cpu().numpy(), full[k][:n].cpu().numpy()
+                assert np.array_equal(a.view(np.int64 if a.itemsize == 8 else np.int32), b.view(np.int64 if b.itemsize == 8 else np.int32)), (skip, k)
+
+
+# ---- 3. tilings -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["long", "short", "steps"])
+def test_gap_does_not_depend_on_the_tiling(torch_mod, kind):
+    case = rc.tiling_case(kind)
+    res = run(case, per_row=(kind != "steps"))
+    ch = res["channels"].cpu().numpy()
+    sc = res["status_counts"].cpu().numpy()
+    for b, (ok_x, ok_y) in enumerate(case["ok"]):
+        # sensor 0 and the x channel follow ok_x, sensor 1 and the y channel ok_y
+        want_x, want_y = list(rr.gap_scan(ok_x)), list(rr.gap_scan(ok_y))
+        assert ch[b].tolist() == [want_x, want_y, want_x, want_y], (kind, b, ch[b].tolist(), want_x, want_y)
+        assert sc[b, 0, 0] == int(ok_x.sum()) and sc[b, 0, 3] == int((~ok_x).sum()) and sc[b, 1, 0] == int(ok_y.sum()), (kind, b)
+    if kind != "steps":
+        tally = Tally()
+        compare(res, rc.reference(rr, case), tally, f"tiling {kind}")
+        tally.check_caps(f"tiling {kind}")
+        assert tally.excused == 0
+    assert same_bits(res, run(case, per_row=False, cull=False), SUMMARY_KEYS), kind
+
+
+# ---- 4. scene size ----------------------------------------------------------------------------------------------------------
+def lds_budget():
+    src = open(os.path.join(ROOT, "vexautonomousplanner_amd", "csrc", "vap_range.hip")).read()
+    return int(re.search(r"constexpr int kRangeLdsDoubles = (\d+);", src).group(1))
+
+
+@pytest.mark.parametrize("over", [False, True])
+def test_scene_on_both_sides_of_the_lds_budget(torch_mod, over):
+    case = rc.scene_size_case(over)
+    sc = case["scene"]
+    packed = 4 * len(sc["polygons"]) + 8 * sum(len(p) for p in sc["polygons"]) + 4 * len(sc["circles"])
+    assert (packed > lds_budget()) == over, (packed, lds_budget())
+    tally = Tally()
+    res = run(case)
+    compare(res, rc.reference(rr, case), tally, f"scene {'over' if over else 'under'} the budget ({packed} doubles)")
+    tally.check_caps(f"scene size over={over}")
+    assert same_bits(res, run(case, cull=False), SUMMARY_KEYS + ROW_KEYS)
+
+
+# ---- 5. partners ------------------------------------------------------------------------------------------------------------
+def test_partner_between_the_sensor_and_the_wall(torch_mod):
+    rows = np.zeros((1, 6, 8))
+    others = np.zeros((2, 4, 8))
+    others[0, :, 6] = [2.0, 3.0, 4.0, 5.0]
+    sens = np.array([[0.0, 0.0, 1.0, 0.0, 0.0, 1.0, 0.0, 0.0]])
+    case = {"scene": {"field": (-9.0, -9.0, 9.0, 9.0), "polygons": [], "circles": np.zeros((0, 3))}, "rows": rows,
+            "counts": np.array([6], dtype=np.int32), "sensors": sens, "others": others,
+            "others_counts": np.array([[3, 0], [0, 0]], dtype=np.int32), "others_foot": rc.SQUARE}
+    for shift, want in ((2, [1.25, 1.25, 1.25, 2.25, 3.25, 3.25]), (-2, [3.25] * 6), (0, [1.25, 2.25, 3.25, 3.25, 3.25, 3.25])):
+        res = run(case, shift_rows=shift)
+        assert res["range"][0, :, 0].tolist() == want, shift
+        st, fa, el = sn().unpack(res["code"][0, :, 0].cpu().numpy())
+        assert (st == 5).all() and (el == 0).all() and (fa == 3).all(), shift
+        assert res["status_counts"][0, 0].tolist() == [0, 0, 0, 0, 0, 6, 0, 0] and res["channels"][0, 0].tolist() == [0, -1, -1, 6, 0]
+    # only the partner without rows: it is absent, the wall is read (FAR: the window ends at 1 ft)
+    case["others"], case["others_counts"] = others[1:], np.array([[0, 0]], dtype=np.int32)
+    res = run(case)
+    assert res["range"][0, :, 0].tolist() == [9.0] * 6 and (res["code"][0, :, 0].cpu().numpy() == sn().pack(3, 2, -1)).all()
+
+
+def test_partners_against_the_reference(torch_mod):
+    case = rc.partner_case()
+    tally = Tally()
+    blocked = 0
+    for shift in (0, -7, 11):
+        ref = rc.reference(rr, case, shift)
+        blocked += int((ref["status"] == rr.BLOCKED).sum())
+        res = run(case, shift_rows=shift)
+        compare(res, ref, tally, f"partners shift {shift}")
+        assert same_bits(res, run(case, shift_rows=shift, cull=False, device_input=False), SUMMARY_KEYS + ROW_KEYS), shift
+    assert blocked > 20, blocked
+    tally.check_caps("partners")
+
+
+# ---- 6. the producers' rows, unchanged ---------------------------------------------------------------------------------------
+def box_around(rows, counts, pad=1.5):
+    pts = np.concatenate([rows[b, :int(counts[b]), 6:8] for b in range(len(rows))])
+    pts = pts[np.isfinite(pts).all(axis=1)]
+    lo, hi = pts.min(axis=0), pts.max(axis=0)
+    return (lo[0] - pad, lo[1] - pad - 0.25, hi[0] + pad + 0.5, hi[1] + pad)
+
+
+def check_producer(torch, gen, tp, what, tally, others=None):
+    from vexautonomousplanner_amd import footprint, sensors
+    rows, counts = tp["rows"].cpu().numpy(), tp["counts"].cpu().numpy()
+    field = box_around(rows, counts[:, 0])
+    # walls only, 1.5 ft and more from every row: a beam that an in-place turn sweeps over a polygon or a circle grazes it at
+    # some row, and one grazing reading excuses its whole route from the summaries — with a handful of routes that is the
+    # cap.  A wall this far away is never seen at cos_inc < 0.1 before the other pair of walls is nearer.
+    scene = {"field": field, "polygons": [], "circles": np.zeros((0, 3))}
+    S = [sensors.Sensor(7.2, 0.0, 0, (1.2, 96.0), 60.0), sensors.Sensor(-7.2, 0.0, 180, (1.2, 96.0), 60.0),
+         sensors.Sensor(0.0, 7.2, 90, (1.2, 96.0), 60.0), sensors.Sensor(0.0, -7.2, 270, (1.2, 96.0), 60.0)]
+    sens = sensors.sensor_rows(S)
+    assert np.allclose(sens, rc.SENSORS4, rtol=0, atol=1e-15)
+    res = gen.range_readings(tp, S, footprint.Scene(**scene), per_row=True)
+    torch.cuda.synchronize()
+    assert tp["counts"].shape[1] in (2, 3)
+    ref = rr.readings(rows, counts[:, 0], sens, scene["field"], scene["polygons"], scene["circles"])
+    compare(res, ref, tally, what)
+    dt = 0.01
+    ch = res["channels"].cpu().numpy()
+    gt = res["gap_time"].cpu().numpy()
+    assert np.allclose(gt, ch[:, :, 3] * dt, rtol=0, atol=1e-12), what
+    ft = res["first_time"].cpu().numpy()
+    assert np.array_equal(np.isnan(ft), ch[:, :, 1] < 0) and np.allclose(np.nan_to_num(ft), np.maximum(ch[:, :, 1], 0) * dt, rtol=0, atol=1e-12)
+    return res
+
+
+def full_rows(torch, name, copies=2):
+    from vexautonomousplanner_amd.batch import BatchedTrajectoryGenerator
+    g = gu.load(name)
+    gen = BatchedTrajectoryGenerator(0, "f64")
+    cons = [float(v) for v in g["constraints"]]
+    rep = lambda a: np.repeat(np.asarray(a)[None], copies, axis=0)
+    wp = torch.tensor(rep(g["waypoints"]), dtype=torch.float64, device=gen.device)
+    res = gen.profile_routes(wp, node_reverse=rep(g["node_is_reverse_node"]), node_turn=rep(g["node_turn"]),
+                             node_tangent=rep(g["node_tangent"]), node_magnitudes=rep(g["node_magnitudes"]),
+                             constraints=cons, dd=0.005, capacity=16384)
+    gen.apply_node_limits(res, cons, node_max_velocity=rep(g["node_max_velocity"]), node_stop=rep(g["node_stop"]),
+                          node_max_acceleration=rep(g["node_max_acceleration"]))
+    tp = gen.time_profile(res, cons, dt=0.01, capacity_rows=4096, node_reverse=rep(g["node_is_reverse_node"]))
+    out = gen.insert_waits(res, tp, node_wait_time=rep(g["node_wait_time"]), dt=0.01, node_turn=rep(g["node_turn"]),
+                           node_reverse=rep(g["node_is_reverse_node"]), constraints=cons)
+    torch.cuda.synchronize()
+    assert not res["flags"].any().item()
+    return gen, cons, tp, out
+
+
+@pytest.mark.parametrize("name", ["feat_turn", "feat_reverse"])
+def test_rows_of_the_time_domain_producers(torch_mod, name):
+    torch = torch_mod
+    from vexautonomousplanner_amd import tracking
+    gen, cons, tp, out = full_rows(torch, name)
+    tally = Tally()
+    rows, n = out["rows"].cpu().numpy(), int(out["counts"][0, 0])
+    v = rows[0, :n, 2]
+    assert (v < 0).any() or ((v == 0) & (np.abs(rows[0, :n, 5]) > 0)).any(), name      # reversed rows / in-place turn rows
+    check_producer(torch, gen, tp, f"{name} time_profile", tally)                       # counts stride 2
+    check_producer(torch, gen, out, f"{name} insert_waits", tally)                      # counts stride 3
+    # the two copies chained into one routine
+    tl = gen.routine_timeline(tp, [[0, 1], [1, 0]], constraints=cons, dt=0.01)
+    torch.cuda.synchronize()
+    assert not tl["flags"].any().item()
+    check_producer(torch, gen, tl, f"{name} routine_timeline", tally)
+    # the executed rows of the disturbed rollouts, with their [B K][2] counts
+    K = 4
+    P = tracking.sample_perturbations(2, K, seed=11)
+    ro = gen.tracking_rollouts(out, tracking.Follower(), P, time_step=0.01, executed=True)
+    torch.cuda.synchronize()
+    assert ro["counts"].shape == (2 * K, 2)
+    check_producer(torch, gen, ro, f"{name} executed rows", tally)
+    tally.check_caps(f"producers {name}")
+
+
+# ---- 7. refusals ------------------------------------------------------------------------------------------------------------
+def test_c_abi_refusals_and_the_empty_batch(torch_mod):
+    torch = torch_mod
+    from vexautonomousplanner_amd import _lib
+    case = rc.random_case(rc.RANDOM_SEEDS[1])
+    B, ns = len(case["counts"]), 4
+    sc = torch.full((B, ns, 8), -5, dtype=torch.int32, device="cuda:0")
+    call = lambda **kw: raw_call(torch, case, None, None, None, sc, None, None, **kw)
+    good = case["sensors"]
+
+    def changed(i, v):
+        s = good.copy()
+        s[2, i] = v
+        return s
+    assert call() == 0 and not (sc == -5).any().item()
+    sc.fill_(-5)
+    INV, UNS = _lib.VAP_ERR_INVALID, _lib.VAP_ERR_UNSUPPORTED
+    assert call(n_sens=0) == INV
+    assert call(n_sens=9, sens=np.concatenate([good, good, good[:1]])) == INV
+    assert call(sens=changed(2, 0.5)) == INV                         # (0.5, 1): not a unit direction
+    assert call(sens=changed(3, 1.0 + 1e-9)) == INV
+    assert call(sens=changed(5, 0.05)) == INV                        # r_max < r_min
+    assert call(sens=changed(4, -0.5)) == INV
+    assert call(sens=changed(6, 1.5)) == INV
+    assert call(sens=changed(0, math.nan)) == INV                    # a NaN mount
+    assert call(Bo=17) == UNS
+    assert call(rows="null") == INV
+    assert (sc == -5).all().item()                                   # a refused call writes nothing
+    assert call(B=0) == 0 and (sc == -5).all().item()                # B = 0: a no-op
+    assert call(Bo=16) == 0 and not (sc == -5).any().item()
+    with pytest.raises(ValueError):
+        sn().readings(case["rows"], case["counts"], good, scene_of(case["scene"]), others=np.zeros((17, 4, 8)),
+                      others_counts=np.ones(17, dtype=np.int32), others_footprint=rc.SQUARE)
+    with pytest.raises(ValueError):
+        sn().readings(case["rows"], case["counts"], good, scene_of(case["scene"]), others=np.zeros((1, 4, 8)),
+                      others_counts=np.ones(1, dtype=np.int32))
+    # a single trajectory drops the batch axis
+    one = sn().readings(case["rows"][0, :30], None, good, scene_of(case["scene"]), per_row=True)
+    assert one["range"].shape == (30, 4) and one["channels"].shape == (6, 5) and one["gap_time"].shape == (6,)
+    both = run({**case, "rows": case["rows"][:1, :30], "counts": np.array([30], dtype=np.int32)})
+    assert np.array_equal(bits(one, ("range",))["range"], bits(both, ("range",))["range"][0])
+
+
+# ---- 8. a NaN heading -------------------------------------------------------------------------------------------------------
+def test_nan_heading_is_a_bad_pose_on_that_row_only(torch_mod):
+    case = rc.random_case(rc.RANDOM_SEEDS[2])
+    clean = run(case)
+    b = 7                                                            # the route with every row of the capacity
+    bad = {**case, "rows": case["rows"].copy()}
+    bad["rows"][b, 70, 4] = math.nan
+    bad["rows"][b, 3, 6] = math.inf
+    res = run(bad)
+    code, ccode = res["code"].cpu().numpy(), clean["code"].cpu().numpy()
+    for r in (70, 3):
+        assert (code[b, r] == 6).all() and np.isnan(res["range"][b, r].cpu().numpy()).all() and np.isnan(res["cos_incidence"][b, r].cpu().numpy()).all()
+    mask = np.ones(code.shape, dtype=bool)
+    mask[b, [70, 3]] = False
+    assert np.array_equal(code[mask], ccode[mask])
+    r1, r2 = bits(res, ("range",))["range"], bits(clean, ("range",))["range"]
+    assert np.array_equal(r1[mask], r2[mask])
+    sc = res["status_counts"].cpu().numpy()
+    assert (sc[b, :, 6] == 2).all() and (np.delete(sc, b, axis=0)[:, :, 6] == 0).all()

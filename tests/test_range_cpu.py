@@ -1,0 +1,250 @@
+"""CPU: the range-sensor feature without a device — the export and the module, the NumPy reference of tests/range_ref.py
+against hand-computed cases, the gap record's combine against a brute-force scan, the host side of sensors.py, and the cap
+on excused readings on the very inputs test_gpu_range.py runs the kernel on (tests/range_cases.py)."""
+import math
+
+import numpy as np
+import pytest
+
+import range_cases as rc
+import range_ref as rr
+
+UNIT_SQUARE = [[2.0, -1.0], [4.0, -1.0], [4.0, 1.0], [2.0, 1.0]]
+
+
+def sensor(mx=0.0, my=0.0, ux=1.0, uy=0.0, r_min=0.0, r_max=100.0, min_cos=0.0):
+    return np.array([mx, my, ux, uy, r_min, r_max, min_cos, 0.0])
+
+
+def one(heading, x, y, sens, **scene):
+    r = rr.cast(np.array([heading]), np.array([x]), np.array([y]), sens, **scene)
+    return {k: v[0] for k, v in r.items()}
+
+
+# ---- export and module ----------------------------------------------------------------------------------------------------
+def test_export_and_module():
+    import vexautonomousplanner_amd as pkg
+    from vexautonomousplanner_amd import _lib, sensors
+    assert "vap_range_readings" in _lib.EXPORTS and hasattr(_lib.lib(), "vap_range_readings")
+    assert "sensors" in pkg.__all__ and pkg.sensors is sensors
+    assert (sensors.VALID, sensors.NONE, sensors.NEAR, sensors.FAR, sensors.OBLIQUE, sensors.BLOCKED, sensors.BAD_POSE) == tuple(range(7))
+    from vexautonomousplanner_amd.batch import BatchedTrajectoryGenerator
+    assert callable(BatchedTrajectoryGenerator.range_readings)
+
+
+# ---- the reference against hand-computed cases ------------------------------------------------------------------------------
+def test_reference_walls_from_the_centre():
+    field = (-6.0, -4.0, 5.0, 3.0)
+    for (ux, uy), t, face in (((1.0, 0.0), 5.0, 2), ((-1.0, 0.0), 6.0, 0), ((0.0, 1.0), 3.0, 3), ((0.0, -1.0), 4.0, 1)):
+        r = one(0.0, 0.0, 0.0, sensor(ux=ux, uy=uy), field=field)
+        assert (r["status"], r["face"], r["element"]) == (rr.VALID, face, -1)
+        assert r["t"] == t and r["cos"] == 1.0
+    # the pose turns the beam: phi = -heading = 90 degrees points the +x beam at ymax; the mount point turns with it
+    r = one(-math.pi / 2, 1.0, 0.0, sensor(mx=0.5), field=field)
+    assert (r["face"], r["element"]) == (3, -1) and abs(r["t"] - 2.5) < 1e-15
+
+
+def test_reference_square_and_circle_ahead():
+    r = one(0.0, 0.0, 0.0, sensor(), field=(-9, -9, 9, 9), polygons=[UNIT_SQUARE])
+    assert (r["status"], r["face"], r["element"], r["t"], r["cos"]) == (rr.VALID, 3, 0, 2.0, 1.0)       # edge 3: (2, 1) -> (2, -1)
+    assert r["margin"] == 1.0                                                                              # the edge's ends
+    r = one(0.0, 0.0, 0.0, sensor(), field=(-9, -9, 9, 9), polygons=[UNIT_SQUARE], circles=[(1.5, 0.0, 0.5)])
+    assert (r["status"], r["face"], r["element"], r["t"], r["cos"]) == (rr.VALID, 0, 1, 1.0, 1.0)
+    r = one(0.0, 0.0, 0.3, sensor(), circles=[(1.5, 0.0, 0.5)])                                            # off the axis: 3-4-5
+    assert abs(r["t"] - 1.1) < 1e-15 and abs(r["cos"] - 0.8) < 1e-15
+
+
+def test_reference_vertex_corner_and_ties():
+    # through the vertex (2, 1) along the diagonal: edges 2 and 3 both give t = sqrt(5); the smaller edge index stays
+    d = math.hypot(2.0, 1.0)
+    r = one(0.0, 0.0, 0.0, sensor(ux=2.0 / d, uy=1.0 / d), polygons=[UNIT_SQUARE])
+    assert (r["element"], r["face"]) == (0, 2) and abs(r["t"] - d) < 1e-15 and r["margin"] < rr.AMBIGUOUS and r["excused"]
+    # into the corner of the field: the x side wins the tie
+    q = math.sqrt(0.5)
+    r = one(0.0, 0.0, 0.0, sensor(ux=q, uy=q), field=(-2.0, -2.0, 2.0, 2.0))
+    assert (r["element"], r["face"]) == (-1, 2) and r["cos"] == q and r["excused"]
+    # a wall before a polygon at the same t: the wall stays (the first in order)
+    r = one(0.0, 0.0, 0.0, sensor(), field=(-2.0, -2.0, 2.0, 2.0), polygons=[UNIT_SQUARE])
+    assert (r["element"], r["face"], r["t"]) == (-1, 2, 2.0)
+
+
+def test_reference_origins_inside_and_outside():
+    r = one(0.0, 3.0, 0.0, sensor(), polygons=[UNIT_SQUARE])                       # inside the square: the way out
+    assert (r["status"], r["element"], r["face"], r["t"]) == (rr.VALID, 0, 1, 1.0)
+    r = one(0.0, 0.2, 0.0, sensor(), circles=[(0.0, 0.0, 1.0)])                    # inside the circle: the far root
+    assert (r["status"], r["element"], r["t"], r["cos"]) == (rr.VALID, 0, 0.8, 1.0)
+    r = one(0.0, 5.0, 0.0, sensor(), field=(-2.0, -2.0, 2.0, 2.0))                 # outside the field: no wall
+    assert (r["status"], r["element"], r["face"]) == (rr.NONE, -2, 0) and math.isnan(r["t"]) and math.isnan(r["cos"])
+    r = one(0.0, -5.0, 0.0, sensor(), field=(-2.0, -2.0, 2.0, 2.0), polygons=[UNIT_SQUARE])   # outside: elements still seen
+    assert (r["status"], r["element"], r["t"]) == (rr.VALID, 0, 7.0)
+    r = one(0.0, 2.0, 0.0, sensor(), field=(-2.0, -2.0, 2.0, 2.0))                 # on the box counts as inside
+    assert (r["element"], r["face"], r["t"]) == (-1, 2, 0.0)
+
+
+def test_reference_every_status():
+    field = (-6.0, -6.0, 6.0, 6.0)
+    assert one(0.0, 0.0, 0.0, sensor(), field=field)["status"] == rr.VALID
+    assert one(0.0, 0.0, 0.0, sensor(), field=None)["status"] == rr.NONE
+    assert one(0.0, 0.0, 0.0, sensor(r_min=6.5), field=field)["status"] == rr.NEAR
+    assert one(0.0, 0.0, 0.0, sensor(r_max=5.5), field=field)["status"] == rr.FAR
+    tall = (-6.0, -60.0, 6.0, 60.0)
+    r = one(-math.pi / 3, 0.0, 0.0, sensor(min_cos=0.6), field=tall)               # 60 degrees off the normal: cos 0.5
+    assert r["status"] == rr.OBLIQUE and abs(r["cos"] - 0.5) < 1e-15 and abs(r["t"] - 12.0) < 1e-14
+    for bad in ((math.nan, 0.0, 0.0), (0.0, math.inf, 0.0), (0.0, 0.0, math.nan)):
+        r = one(*bad, sensor(), field=field)
+        assert r["status"] == rr.BAD_POSE and math.isnan(r["t"]) and r["element"] == -2 and not r["excused"]
+    # a partner square parked between the sensor and the wall: blocked, whatever the window says
+    posed = rr.pose_polygon(rc.SQUARE, np.array([0.0]), np.array([3.0]), np.array([0.0]))
+    r = one(0.0, 0.0, 0.0, sensor(r_max=1.0), field=field, partners=[posed])
+    assert (r["status"], r["element"], r["face"], r["t"]) == (rr.BLOCKED, 0, 3, 2.25)
+    # priority: too near comes before too oblique
+    r = one(-math.pi / 3, 0.0, 0.0, sensor(r_min=13.0, min_cos=0.6), field=tall)
+    assert r["status"] == rr.NEAR
+
+
+def test_reference_partner_parking_and_absence():
+    rows = np.zeros((1, 6, 8))
+    others = np.zeros((2, 4, 8))
+    others[0, :, 6] = [2.0, 3.0, 4.0, 5.0]                                          # partner 0 drives away along x
+    ref = rr.readings(rows, [6], [sensor()], field=(-9, -9, 9, 9), others=others, others_counts=[[3], [0]], others_foot=rc.SQUARE,
+                      shift_rows=2)
+    # rows 0..2: parked at its row 0 (x = 2); row 3: its row 1; rows 4, 5: parked at its last row, 2 (x = 4)
+    assert ref["t"][0, :, 0].tolist() == [1.25, 1.25, 1.25, 2.25, 3.25, 3.25]
+    assert (ref["status"][0, :, 0] == rr.BLOCKED).all() and (ref["element"][0, :, 0] == 0).all()
+    ref = rr.readings(rows, [6], [sensor()], field=(-9, -9, 9, 9), others=others, others_counts=[[3], [0]], others_foot=rc.SQUARE,
+                      shift_rows=-2)
+    assert ref["t"][0, :, 0].tolist() == [3.25] * 6
+    ref = rr.readings(rows, [6], [sensor()], field=(-9, -9, 9, 9), others=others[1:], others_counts=[[0]], others_foot=rc.SQUARE)
+    assert (ref["element"][0, :, 0] == -1).all() and (ref["t"][0, :, 0] == 9.0).all()
+
+
+# ---- the gap record ---------------------------------------------------------------------------------------------------------
+def test_gap_combine_against_brute_force():
+    rng = np.random.default_rng(5)
+    for trial in range(400):
+        n = int(rng.integers(0, 90))
+        ok = rng.random(n) < rng.choice([0.0, 0.1, 0.5, 0.9, 1.0])
+        cuts = np.sort(rng.integers(0, n + 1, int(rng.integers(0, 7))))
+        bounds = [0, *cuts.tolist(), n]
+        recs = [rr.gap_record(ok[a:b], a) for a, b in zip(bounds[:-1], bounds[1:])]
+        # left to right, and as a tree: the combine is associative
+        acc = recs[0]
+        for r in recs[1:]:
+            acc = rr.gap_combine(acc, r)
+        assert rr.gap_finish(acc) == rr.gap_scan(ok), (trial, ok, bounds)
+        while len(recs) > 1:
+            recs = [rr.gap_combine(recs[i], recs[i + 1]) if i + 1 < len(recs) else recs[i] for i in range(0, len(recs), 2)]
+        assert rr.gap_finish(recs[0]) == rr.gap_scan(ok), (trial, ok, bounds)
+    assert rr.gap_scan([]) == (0, -1, -1, 0, -1)
+    assert rr.gap_scan([False] * 5) == (0, -1, -1, 5, 0)
+    assert rr.gap_scan([True] * 5) == (5, 0, 4, 0, -1)
+    assert rr.gap_scan([False, True, False, False, True, False, False]) == (2, 1, 4, 2, 2)       # the earliest of the longest
+
+
+def test_crafted_patterns_hold_what_they_promise():
+    for kind in ("long", "steps"):
+        case = rc.tiling_case(kind)
+        ok = case["ok"][3 if kind == "steps" else 0][0]
+        bad = ~ok
+        for e in range(64, len(ok) - 70, 64):
+            assert bad[e - 1] or bad[e], e                               # every wave edge has a run at it
+        starts = {int(i) for i in np.nonzero(bad[1:] & ~bad[:-1])[0] + 1}
+        ends = {int(i) for i in np.nonzero(~bad[1:] & bad[:-1])[0] + 1}
+        for edge in (64, 256, 1024):
+            ks = range(edge, len(ok) - 70, edge)
+            assert any(k in starts for k in ks) or edge == 1024, edge    # a run begins at such an edge
+            assert any(k in ends for k in ks) or edge == 1024, edge      # a run ends at one
+            assert any(bad[k - 1] and bad[k] for k in ks), edge          # a run straddles one
+        if kind == "steps":
+            assert bad[1023] and bad[1024]                                   # across the end of a four-step tile
+
+
+# ---- the Python side --------------------------------------------------------------------------------------------------------
+def test_unpack_round_trip():
+    from vexautonomousplanner_amd import sensors
+    for status in range(7):
+        for face in (0, 1, 3, 15):
+            for el in (-2, -1, 0, 7, 255, 527):
+                assert sensors.unpack(sensors.pack(status, face, el)) == (status, face, el)
+    assert sensors.unpack(-1) == (-1, -1, -2)
+    codes = np.array([sensors.pack(0, 2, -1), sensors.pack(5, 3, 12), -1], dtype=np.int32)
+    st, fa, el = sensors.unpack(codes)
+    assert st.tolist() == [0, 5, -1] and fa.tolist() == [2, 3, -1] and el.tolist() == [-1, 12, -2]
+    import torch
+    st, fa, el = sensors.unpack(torch.tensor(codes))
+    assert st.tolist() == [0, 5, -1] and fa.tolist() == [2, 3, -1] and el.tolist() == [-1, 12, -2]
+
+
+def test_sensor_conversions():
+    from vexautonomousplanner_amd import sensors
+    for deg, u in ((0, (1.0, 0.0)), (90, (0.0, 1.0)), (180, (-1.0, 0.0)), (270, (0.0, -1.0)), (-90, (0.0, -1.0)), (450, (0.0, 1.0))):
+        row = sensors.Sensor(6.0, -3.0, deg, range_in=(1.2, 60.0), max_incidence_deg=60.0).row()
+        assert tuple(row[2:4]) == u, deg                                  # exact, signed zeros aside
+        assert row[0] == 0.5 and row[1] == -0.25 and row[4] == 1.2 / 12 and row[5] == 5.0 and row[7] == 0.0
+        assert abs(row[6] - 0.5) < 1e-15
+    row = sensors.Sensor(0, 0, 37.0).row()
+    assert abs(math.hypot(row[2], row[3]) - 1.0) <= 1e-15 and abs(row[2] - math.cos(math.radians(37))) < 1e-15
+    assert row[6] == 0.0                                                  # 90 degrees: every incidence
+    assert sensors.Sensor(0, 0, 0, max_incidence_deg=0.0).row()[6] == 1.0
+    assert "measured" in sensors.Sensor.__doc__
+    rows = sensors.sensor_rows([sensors.Sensor(0, 0, 0), sensors.Sensor(0, 0, 90)])
+    assert rows.shape == (2, 8) and rows.dtype == np.float64
+    assert sensors.sensor_rows(sensors.Sensor(0, 0, 0)).shape == (1, 8)
+    np.testing.assert_array_equal(sensors.sensor_rows(rc.SENSORS4), rc.SENSORS4)
+
+
+def test_value_errors():
+    from vexautonomousplanner_amd import sensors
+    S = sensors.Sensor
+    for bad in (lambda: S(0, 0, 0, range_in=(5.0, 1.0)), lambda: S(0, 0, 0, range_in=(-1.0, 1.0)), lambda: S(math.nan, 0, 0),
+                lambda: S(0, 0, math.inf), lambda: S(0, 0, 0, max_incidence_deg=91.0), lambda: S(0, 0, 0, max_incidence_deg=-1.0),
+                lambda: S(0, 0, 0, range_in=(1.0, 2.0, 3.0))):
+        with pytest.raises(ValueError):
+            bad()
+    good = rc.SENSORS4[0]
+
+    def changed(i, v):
+        r = good.copy()
+        r[i] = v
+        return [r]
+    for rows in ([], [good] * 9, changed(2, 1.0 + 1e-9), changed(2, 0.0), changed(5, 0.05), changed(4, -0.1), changed(6, 1.5),
+                 changed(6, -0.1), changed(0, math.nan), changed(7, math.inf), np.zeros((2, 7))):
+        with pytest.raises(ValueError):
+            sensors.sensor_rows(rows)
+    with pytest.raises(TypeError):
+        sensors.readings(np.zeros((1, 8)), None, [good], scene={"field": None})
+
+
+# ---- the cap on excused readings, on the GPU tests' own inputs --------------------------------------------------------------
+def cases():
+    yield from ((f"random{seed}", rc.random_case(seed)) for seed in rc.RANDOM_SEEDS)
+    yield "scene_under", rc.scene_size_case(False)
+    yield "scene_over", rc.scene_size_case(True)
+    yield "partners", rc.partner_case()
+    yield "tiling_short", rc.tiling_case("short")
+
+
+def test_excused_readings_stay_inside_the_cap():
+    seen = set()
+    random_read = random_exc = random_routes = random_touched = 0
+    for name, case in cases():
+        for shift in ((0, -7, 11) if name == "partners" else (0,)):
+            ref = rc.reference(rr, case, shift)
+            summ = rr.summaries(ref)
+            share, touched = rc.excused_shares(ref, summ)
+            print(f"RANGE-CAP {name} shift {shift}: excused {share:.5f} of readings, touched {touched:.3f} of routes")
+            if name.startswith("random"):                     # the random test is one test over the six scenes
+                n = int(ref["live"].sum()) * 4
+                random_read += n
+                random_exc += int(ref["excused"].sum())
+                random_routes += len(case["counts"])
+                random_touched += int(summ["touched"].any(axis=1).sum())
+                seen |= set(np.unique(ref["status"][ref["live"]]).tolist())
+            else:
+                assert share <= rc.MAX_EXCUSED, (name, share)
+                assert touched <= rc.MAX_TOUCHED, (name, touched)
+    print(f"RANGE-CAP random: excused {random_exc} of {random_read}, touched {random_touched} of {random_routes} routes")
+    assert random_read == 4 * sum(int(rc.random_case(s)["counts"].sum()) for s in rc.RANDOM_SEEDS)
+    assert random_exc <= rc.MAX_EXCUSED * random_read
+    assert random_touched <= rc.MAX_TOUCHED * random_routes
+    assert {0, 1, 2, 3, 4} <= seen, seen

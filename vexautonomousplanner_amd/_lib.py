@@ -50,6 +50,9 @@ CONFLICT_ALL_PAIRS, CONFLICT_MATCHED = 0, 1
 HOLD_A_FIRST, HOLD_A_LAST, HOLD_O_FIRST, HOLD_O_LAST = 1, 2, 4, 8
 CONFLICT_SHIFTS_MAX = 4096
 FOLLOWER_RAMSETE, FOLLOWER_PURSUIT = 0, 1
+# vap_range_readings: a reading's status, and the limits
+RANGE_VALID, RANGE_NONE, RANGE_NEAR, RANGE_FAR, RANGE_OBLIQUE, RANGE_BLOCKED, RANGE_BAD_POSE = 0, 1, 2, 3, 4, 5, 6
+RANGE_MAX_SENSORS, RANGE_MAX_PARTNERS = 8, 16
 
 
 def closest_mode(mode):
@@ -77,7 +80,7 @@ EXPORTS = (
     "vap_tracking_rollouts", "vap_pursuit_rollouts", "vap_rollout_clearance", "vap_search_sample", "vap_search_update", "vap_plan_grid", "vap_plan_seeds",
     "vap_plan_occupancy", "vap_plan_seeds_occupied", "vap_plan_travel", "vap_plan_order",
     "vap_routine_timeline", "vap_plan_order_timed", "vap_velocity_conditioning",
-    "vap_curve_caps", "vap_drive_audit",
+    "vap_curve_caps", "vap_drive_audit", "vap_range_readings",
 )
 
 
@@ -242,6 +245,8 @@ def lib():
         [C.c_int, C.c_double, C.c_uint64, C.c_uint32, C.c_double] + [vp] * 6
     L.vap_curve_caps.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(Constraints), C.POINTER(CurveLimitsStruct)] + [vp] * 5
     L.vap_drive_audit.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_double, C.POINTER(DriveLimitsStruct)] + [vp] * 6
+    L.vap_range_readings.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_int, dp, dp, C.c_int, ip, dp, C.c_int, dp,
+                                     C.c_int, C.c_long, vp, vp, C.c_int, C.c_int, dp, C.c_int] + [vp] * 6
     _lib = L
     return L
 

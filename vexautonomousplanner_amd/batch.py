@@ -534,6 +534,20 @@ class BatchedTrajectoryGenerator:
             raise ValueError(f"rows must be on {self.device}")
         return fp.clearance(rows, counts, footprint, scene, margin=margin, per_row=per_row, out=out, ctx=self.ctx, cull=cull)
 
+    def range_readings(self, tp, sensors, scene, others=None, **kw):
+        """What range sensors (sensors.Sensor objects) read along the rows of ``tp`` — the dict ``time_profile``,
+        ``insert_waits``, ``routine_timeline`` or ``tracking_rollouts`` returned — against ``scene``, and where along each route
+        a sensor gives a valid reading (vap_range_readings on this generator's context and torch's current stream; see
+        sensors.readings for others_footprint, shift_rows, per_row, out, cull and the returned dict).  ``others``: a dict of
+        partner rows on the same time step, as ``footprint_conflicts`` takes it."""
+        from . import sensors as sn
+        for d in (tp,) if others is None else (tp, others):
+            if d["rows"].device != self.device:
+                raise ValueError(f"rows must be on {self.device}")
+        if others is not None:
+            kw.update(others=others["rows"], others_counts=others["counts"])
+        return sn.readings(tp["rows"], tp["counts"], sensors, scene, ctx=self.ctx, **kw)
+
     def footprint_conflicts(self, tp, footprint, others, others_footprint=None, **kw):
         """Robot-to-robot clearance of the rows of ``tp`` (footprint ``footprint``) against the rows of ``others``
         (``others_footprint``, default the same) — both dicts as ``time_profile`` / ``insert_waits`` return them, on the

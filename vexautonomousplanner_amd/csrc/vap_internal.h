@@ -99,6 +99,8 @@ struct vap_ctx {
     int cond_scratch_mb = 512;        // VAP_OPT_CONDITIONING_SCRATCH_MB
     // vap_drive_audit: the routes' status words and the per-tile partial peaks and counts
     VapBuffer drive_part;
+    // vap_range_readings: the per-tile records (min / max valid range, counts per status, the channels' gap records)
+    VapBuffer range_part;
 
     int ensure(VapBuffer &b, size_t bytes)
     {
