@@ -13,7 +13,7 @@ pat = None
 if "--grep" in sys.argv:
     pat = sys.argv[sys.argv.index("--grep") + 1]
     args = [a for a in args if a != pat]
-files = args or ["vap_kernels.hip"]
+files = args or ["vap_tables.hip", "vap_sample.hip", "vap_velocity_seq.hip", "vap_velocity_relax.hip"]
 for f in files:
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
            "-Rpass-analysis=kernel-resource-usage", "-c", f, "-o", "/dev/null"]

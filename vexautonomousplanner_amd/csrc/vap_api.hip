@@ -1,7 +1,7 @@
 // vap_api.hip — the C-ABI of libvap.so (declared in include/vap.h).
 //
 // Host-side runtime: context (device + stream + scratch arena + stage timers) and the entry points
-// that sequence the kernels of vap_kernels.hip.  There is deliberately no CPU implementation behind
+// that sequence the kernels of the stage files (vap_tables.hip, vap_sample.hip, vap_velocity_*.hip).  There is deliberately no CPU implementation behind
 // any entry point: without a HIP device every call fails with VAP_ERR_NO_DEVICE.
 #include <climits>
 #include <cmath>

@@ -199,9 +199,7 @@ hipError_t launch_conditioning(hipStream_t st, bool r64, const CondArgs &g, int 
 {
     CondKernelArgs a;
     a.B = nb; a.S = g.S; a.b0 = b0;
-    a.c.vmax = g.c[0]; a.c.amax = g.c[1]; a.c.adec = g.c[2]; a.c.tw = g.c[5];
-    a.c.wmax = 2.0 * a.c.vmax / a.c.tw;
-    a.c.almax = 2.0 * a.c.amax / a.c.tw;
+    a.c = make_consts<double>(g.c);
     a.start_u = g.start_vel * g.start_vel;
     a.end_u = g.end_vel * g.end_vel;
     a.delta = g.delta;

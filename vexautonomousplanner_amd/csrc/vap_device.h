@@ -10,6 +10,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "vap_kernels.h"   // AccRowsV
+
 namespace vap {
 
 constexpr int kLutN = 1000;        // SM:427
@@ -472,6 +474,28 @@ struct AccRows {
     const R *bwd = nullptr;
     const R *dec = nullptr;
 };
+
+// Host side, for the launchers: the constants from c[6] = {max_vel, max_acc, max_dec, friction, jerk, track_width}, and
+// the typed view of the caller's limit rows (they have the recurrence's arithmetic type).
+template <typename R>
+inline VelConsts<R> make_consts(const double c[6])
+{
+    VelConsts<R> v;
+    v.vmax = (R)c[0];
+    v.amax = (R)c[1];
+    v.adec = (R)c[2];
+    v.tw = (R)c[5];
+    v.wmax = (R)2 * v.vmax / v.tw;
+    v.almax = (R)2 * v.amax / v.tw;
+    return v;
+}
+template <typename R>
+inline AccRows<R> acc_rows(const AccRowsV &v)
+{
+    AccRows<R> acc;
+    acc.fwd = (const R *)v.fwd; acc.bwd = (const R *)v.bwd; acc.dec = (const R *)v.dec;
+    return acc;
+}
 
 // Curvature-only limits of one sample (MPG:204-233 / 264-293), in squared-velocity space.
 template <typename R>

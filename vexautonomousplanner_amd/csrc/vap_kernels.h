@@ -1,4 +1,4 @@
-// vap_kernels.h — launcher declarations shared by vap_kernels.hip and vap_api.hip.
+// vap_kernels.h — launcher declarations of every kernel file (vap_tables.hip, vap_sample.hip, vap_velocity_*.hip, ...), shared with vap_api.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -10,7 +10,7 @@
 // These routes are GUI-sized (a few thousand samples) and dominated by strictly sequential state
 // machines, so the kernels favour fidelity over occupancy: the per-sample properties are evaluated by
 // a thread per sample, everything sequential by one lane.  The batched throughput path is
-// vap_kernels.hip; this file is the completeness path behind the same drop-in classes.
+// vap_tables.hip, vap_sample.hip and vap_velocity_*.hip; this file is the completeness path behind the same drop-in classes.
 #include <cmath>
 #include <vector>
 

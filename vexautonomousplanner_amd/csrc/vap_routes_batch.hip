@@ -1,6 +1,6 @@
 // vap_routes_batch.hip — batches of routes whose reverse / turn nodes cut them into several splines.
 //
-// The plain-node kernels of vap_kernels.hip treat a path as ONE spline of W control points.  A route with reverse or
+// The plain-node kernels of vap_tables.hip and vap_sample.hip treat a path as ONE spline of W control points.  A route with reverse or
 // turn nodes is several splines (SM:57-168) that share their split nodes: segment i still joins nodes i and i+1, so
 // the segment / coefficient-block layout [B][W-1] is unchanged; what changes is
 //   K1  the derivative estimates at a split node (it is the last point of one spline and the first of the next:
@@ -8,7 +8,7 @@
 //       QuinticHermiteSpline's setters put them (QHS:543-590, quirk Q3: both in the spline's LAST segment), and
 //       the 2-point rule (QHS:170-172, 181-182)                                                     -> k_fit_routes
 //   K2  one 1000-entry table per spline, concatenated with running offsets (SM:436-464)           -> k_lut (per
-//       (route, spline) workgroup, vap_kernels.hip) + k_route_offsets
+//       (route, spline) workgroup, vap_tables.hip) + k_route_offsets
 //   K3+K4  distance -> parameter over the concatenated table, and parameter -> (segment, local t) with a split node
 //       belonging to the earlier spline (SM:243-275)                                                -> k_sample_routes
 // The velocity pass is the plain one: forward_backward_pass does nothing special at a reverse or turn node

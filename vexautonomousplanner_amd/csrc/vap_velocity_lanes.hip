@@ -593,12 +593,8 @@ hipError_t launch_lanes_p(hipStream_t st, int B, int S, const double c[6], doubl
                           float *vres = nullptr)
 {
     using G = LanesGeo<P>;
-    VelConsts<double> vc;
-    vc.vmax = c[0]; vc.amax = c[1]; vc.adec = c[2]; vc.tw = c[5];
-    vc.wmax = 2.0 * vc.vmax / vc.tw;
-    vc.almax = 2.0 * vc.amax / vc.tw;
-    AccRows<double> acc;
-    acc.fwd = (const double *)accv.fwd; acc.bwd = (const double *)accv.bwd; acc.dec = (const double *)accv.dec;
+    const VelConsts<double> vc = make_consts<double>(c);
+    const AccRows<double> acc = acc_rows<double>(accv);
     // rows are addressed by 32-bit byte offsets from the group's first row
     if ((size_t)P * (size_t)S * 8 >= ((size_t)1 << 32)) return hipErrorInvalidValue;
     const dim3 grid((B + P - 1) / P), block(kLanesThreads);
