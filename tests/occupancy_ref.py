@@ -102,13 +102,14 @@ def window_free(free, first, last, window=None):
     return np.asarray(free, dtype=bool) & ~occupied
 
 
-def seeds(starts, goals, windows, field, cell, free, first, last, W=5, max_vertices=64):
-    """vap_plan_seeds_occupied for R problems on a static free mask: a list of plan_ref.plan dicts, and each problem's mask."""
+def seeds(starts, goals, windows, field, cell, free, first, last, W=5, max_vertices=64, fields=None):
+    """vap_plan_seeds_occupied for R problems on a static free mask: a list of plan_ref.plan dicts, and each problem's mask.
+    ``fields``: plan_ref.plan's cache of distance fields by goal cell, for problems that all share ONE window."""
     out, masks = [], []
     for r, (s, g) in enumerate(zip(np.atleast_2d(starts), np.atleast_2d(goals))):
         m = window_free(free, first, last, None if windows is None else windows[r])
         masks.append(m)
-        out.append(pr.plan(s, g, field, cell, m, W, max_vertices))
+        out.append(pr.plan(s, g, field, cell, m, W, max_vertices, fields))
     return out, masks
 
 
