@@ -1347,6 +1347,69 @@ int vap_range_readings(vap_ctx *ctx, int B, long capacity, const double *d_rows,
                        int stride_o, int n_foot_o, const double *h_foot_o, int shift_rows, double *d_range, double *d_cos_incidence,
                        int *d_code, int *d_status_counts, double *d_range_minmax, int *d_channels);
 
+/* ---- odometry rollouts: the follower steers on a dead-reckoned pose with range resets -----------------------------------
+ * vap_tracking_rollouts feeds the follower the true pose and vap_range_readings says what a sensor reads along given rows.
+ * This call closes the loop: the RAMSETE follower of vap_tracking_rollouts steers on an ESTIMATE of the pose, the estimate
+ * drifts with encoder and gyro errors, and it is pulled back whenever a range reading passes a gate.  "With these sensors the
+ * robot ends within x ft of the goal."  fp64 throughout.
+ *
+ *   rows, counts, follower, perturbation records, the plant, saturation, substeps and settle rows: vap_tracking_rollouts'.
+ *   sensors   h_sensors [n_sens][8] and the scene (h_field .. h_circles): vap_range_readings', the same validation and limits.
+ *             There are no partners.  n_sens may be 0 (pure dead reckoning); the sensors, the scene and the rule may then be NULL.
+ *   odometry  d_odometry [B][K][8], or [K][8] with shared_odometry != 0; a record is {enc_left, enc_right, heading_scale,
+ *             heading_drift (rad/s), range_scale, range_bias (ft), 0, 0}; the ideal record is {1, 1, 1, 0, 1, 0, 0, 0}.  A record
+ *             with a non-finite entry, enc_* <= 0, heading_scale <= 0 or range_scale <= 0 is invalid, and its rollout is treated
+ *             as one with an invalid perturbation record.
+ *   rule      vap_reset_rule {gate (ft), min_cos, gain, every}.
+ *   state     the true plant as in vap_tracking_rollouts (row 0's pose plus (dx, dy, dphi)).  The estimate (xh, yh, phih) starts
+ *             at row 0's pose exactly: the robot believes it was placed where the plan starts.
+ *   step      r = 0 .. n + settle_rows - 1, in this order:
+ *             1. resets, only if n_sens > 0 and r % every == 0; sensors s ascending, each sees the estimate as the earlier
+ *                ones left it.  (a) The true reading is what vap_range_readings gives for executed row r: pose heading =
+ *                -wrap(phi), x, y; candidates 1-3 of that call; the same status rules.  Only status 0 yields a reading,
+ *                z = range_scale t + range_bias; any other status leaves the estimate alone and counts nowhere.  (b) The expected
+ *                reading is taken from the estimate against the walls only: oh = ph + R(phih)(mx, my), uh = R(phih)(ux, uy), cos
+ *                and sin of phih taken once per row; rule 1 of vap_range_readings gives th, a face and cosh; no candidate without
+ *                a field or with oh outside the box.  The reset is accepted iff there is a wall candidate, cosh >= min_cos and
+ *                |z - th| <= gate (a NaN comparison is false); otherwise it is rejected.  (c) Accepted, faces 0 and 2:
+ *                xh += gain (th - z) uh.x; faces 1 and 3: yh += gain (th - z) uh.y.  phih is never reset.
+ *             2. errors: the control errors are step 1 of vap_tracking_rollouts with (ph, phih) in place of the pose; the true
+ *                errors e_x, e_y, e_phi, e_pos the same with the true pose; e_est = hypot(xh - x, yh - y), e_estphi =
+ *                |wrap(phih - phi)|.
+ *             3. statistics on the true errors as vap_tracking_rollouts' step 2, plus the maxima of e_est and e_estphi.
+ *             4. executed row r (if requested): vap_tracking_rollouts' step 3.  Estimate row r (if requested):
+ *                {-wrap(phih), xh, yh, (double) mask}, bit s of mask set when sensor s was accepted at this row.
+ *             5. RAMSETE with the control errors.  6. saturation: unchanged.
+ *             7. n_substeps substeps, each the plant's substep and then the estimate's from the wheel speeds and omega the plant
+ *                just used, in exactly these operations: vh = (enc_left (g_L w_L) + enc_right (g_R w_R)) / 2;
+ *                D = (heading_scale omega) h + heading_drift h; uh = D / 2; dh = vh h sinc(uh);
+ *                ph += dh (cos(phih + uh), sin(phih + uh)); phih += D.  With the ideal record and a zero start offset the
+ *                estimate equals the true pose bit for bit, and the call equals vap_tracking_rollouts.
+ *             After the last step: vap_tracking_rollouts' final errors of the true pose, and the final e_est.
+ *   outputs   any pointer may be NULL.  d_stats [B][K][8] = {max e_pos, max |e_y|, max |e_phi|, final position error, final
+ *             heading error, max e_est, max e_estphi, final e_est}; d_stat_rows [B][K][4] = {row of max e_pos, saturated rows,
+ *             resets accepted, resets rejected}; the five per-route outputs as vap_tracking_rollouts over the max e_pos column,
+ *             in the same fixed order; d_exec_rows, d_exec_counts and cap_exec exactly as there (both clearance calls and
+ *             vap_range_readings take them); d_est_rows [B * K][cap_exec][4].  Edges (n = 0, invalid records, a route without
+ *             a valid rollout) as there: NaN / -1 / 0.
+ * VAP_ERR_INVALID, before the context is touched: everything vap_tracking_rollouts and the sensor and scene checks of
+ * vap_range_readings refuse; n_sens outside 0..8; a negative or non-finite gate; min_cos or gain outside [0, 1]; every outside
+ * 1..10000; a null rule or sensors pointer with n_sens > 0; a null odometry pointer with B > 0; a d_odometry or d_est_rows that
+ * is not 16-byte aligned.  VAP_ERR_UNSUPPORTED: the scene limits of vap_range_readings.  B = 0 is a no-op.
+ * VAP_OPT_FOOTPRINT_CULL governs the cull of the true ray, on and off give the same bits.  Works on the context's stream and
+ * does not synchronise.  Two calls on the same inputs give the same bits: no float atomics. */
+typedef struct {
+    double gate, min_cos, gain;
+    int every;
+} vap_reset_rule;
+int vap_odometry_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride,
+                          double time_step, const vap_follower *f, int K, int shared_perturb, const double *d_perturb,
+                          int shared_odometry, const double *d_odometry, int n_sens, const double *h_sensors,
+                          const vap_reset_rule *rule, const double *h_field, int n_poly, const int *h_poly_start,
+                          const double *h_poly_xy, int n_circle, const double *h_circles, double *d_stats, int *d_stat_rows,
+                          double *d_worst, double *d_mean, int *d_worst_rollout, int *d_worst_row, int *d_n_exceeding,
+                          long cap_exec, double *d_exec_rows, int *d_exec_counts, double *d_est_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 package alone touches neither torch nor the device."""
 import importlib
 
-__all__ = ["batch", "drive", "footprint", "plan", "search", "sensors", "timeline", "tracking"]
+__all__ = ["batch", "drive", "footprint", "odometry", "plan", "search", "sensors", "timeline", "tracking"]
 
 
 def __getattr__(name):

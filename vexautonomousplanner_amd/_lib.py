@@ -80,7 +80,7 @@ EXPORTS = (
     "vap_tracking_rollouts", "vap_pursuit_rollouts", "vap_rollout_clearance", "vap_search_sample", "vap_search_update", "vap_plan_grid", "vap_plan_seeds",
     "vap_plan_occupancy", "vap_plan_seeds_occupied", "vap_plan_travel", "vap_plan_order",
     "vap_routine_timeline", "vap_plan_order_timed", "vap_velocity_conditioning",
-    "vap_curve_caps", "vap_drive_audit", "vap_range_readings",
+    "vap_curve_caps", "vap_drive_audit", "vap_range_readings", "vap_odometry_rollouts",
 )
 
 
@@ -100,6 +100,11 @@ class PursuitStruct(C.Structure):
     """vap_pursuit (include/vap.h)."""
     _fields_ = [("track_width", C.c_double), ("lookahead", C.c_double), ("min_speed", C.c_double), ("arrive_tolerance", C.c_double),
                 ("wheel_speed_max", C.c_double), ("tolerance", C.c_double), ("n_substeps", C.c_int), ("settle_rows", C.c_int)]
+
+
+class ResetRuleStruct(C.Structure):
+    """vap_reset_rule (include/vap.h)."""
+    _fields_ = [("gate", C.c_double), ("min_cos", C.c_double), ("gain", C.c_double), ("every", C.c_int)]
 
 
 class SearchWeights(C.Structure):
@@ -247,6 +252,9 @@ def lib():
     L.vap_drive_audit.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_double, C.POINTER(DriveLimitsStruct)] + [vp] * 6
     L.vap_range_readings.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_int, dp, dp, C.c_int, ip, dp, C.c_int, dp,
                                      C.c_int, C.c_long, vp, vp, C.c_int, C.c_int, dp, C.c_int] + [vp] * 6
+    L.vap_odometry_rollouts.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_double, C.POINTER(FollowerStruct), C.c_int,
+                                        C.c_int, vp, C.c_int, vp, C.c_int, dp, C.POINTER(ResetRuleStruct), dp, C.c_int, ip, dp,
+                                        C.c_int, dp] + [vp] * 7 + [C.c_long, vp, vp, vp]
     _lib = L
     return L
 

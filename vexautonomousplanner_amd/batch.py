@@ -593,6 +593,16 @@ class BatchedTrajectoryGenerator:
             raise ValueError(f"rows must be on {self.device}")
         return tracking.rollouts(tp["rows"], tp["counts"], follower, perturbations, ctx=self.ctx, **kw)
 
+    def odometry_rollouts(self, tp, follower, perturbations, records, **kw):
+        """Tracking rollouts along the rows of ``tp`` in which the follower steers on a dead-reckoned pose — drifting
+        under the odometry ``records``, reset by range sensors against ``scene`` under a reset ``rule``
+        (vap_odometry_rollouts on this generator's context and torch's current stream; see odometry.rollouts for sensors,
+        scene, rule, time_step, executed, estimates, out and the returned dict).  ``follower``: a tracking.Follower."""
+        from . import odometry
+        if tp["rows"].device != self.device:
+            raise ValueError(f"rows must be on {self.device}")
+        return odometry.rollouts(tp["rows"], tp["counts"], follower, perturbations, records, ctx=self.ctx, **kw)
+
     def rollout_clearance(self, tp, follower, perturbations, footprint, scene, **kw):
         """Scene clearance of the disturbed rollouts along the rows of ``tp`` — the dict ``time_profile`` or
         ``insert_waits`` returned — under ``perturbations``, without executed rows in memory (vap_rollout_clearance on this

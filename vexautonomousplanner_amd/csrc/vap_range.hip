@@ -24,13 +24,13 @@
 #include <cstring>
 
 #include "vap_footprint.h"
+#include "vap_raycast.h"
 
 namespace vap {
 namespace {
 
 constexpr int kRangeThreads = 256;
 constexpr int kRangeWaves = kRangeThreads / 64;
-constexpr int kRangeMaxSens = 8;
 constexpr int kRangeMaxChan = kRangeMaxSens + 2;
 constexpr int kRangeMaxPartners = 16;
 constexpr int kRangeLdsDoubles = 2048;    // a packed scene of up to 16 KiB is staged in LDS, a larger one is read from global
@@ -38,7 +38,6 @@ constexpr int kRangePartInts = 128;       // per tile: counts [8][8], then the c
 constexpr int kRangeChanAt = 64;
 constexpr int kRangePartDbls = 16;        // per tile: min, max valid range [8][2]
 constexpr int kRangeGridYMax = 65535;
-constexpr double kRangeGuard = 1.0 - 0x1p-40;   // tn * guard >= best * den  =>  fl(tn / den) >= best
 
 // Packed block (fp64), vap_footprint.h's layouts: foot [n_foot_o][8] (the partners' footprint, body frame) | poly [n_poly][4] |
 // pv [nv][8] | circ [n_circle][4].
@@ -120,96 +119,13 @@ __device__ inline Gap gap_of_mask(unsigned long long ok, int L, int row0)
     return g;
 }
 
-// true when nothing within `rad` of (cx, cy) can be hit by the ray at a parameter below best
-__device__ __forceinline__ bool ray_culled(double ox, double oy, double ux, double uy, double best, double slack, double cx,
-                                           double cy, double rad)
-{
-    const double dx = cx - ox, dy = cy - oy;
-    const double along = dx * ux + dy * uy, perp = dx * uy - dy * ux;
-    const double reach = rad + slack;
-    return fabs(perp) > reach || along < -reach || along - reach > best;     // false for a NaN
-}
-
-// Edge a -> a + e of a packed polygon row v = {ax, ay, nx, ny, ex, ey, ..} against the ray: a hit with a parameter strictly
-// below best replaces it.  den = u x e, t = ((a - o) x e) / den, w = ((a - o) x u) / den; t >= 0 and 0 <= w <= 1 are read
-// off the numerators once den is made positive (a correctly rounded quotient is <= 1 exactly when the numerator is <= the
-// denominator), and t is divided out only when the guard product says it may be below best.
-__device__ __forceinline__ void edge_test(const double *v, double ox, double oy, double ux, double uy, int face, int el,
-                                          double &best, double &bcos, int &bface, int &bel)
-{
-    const double ax = v[0], ay = v[1], ex = v[4], ey = v[5];
-    double den = ux * ey - uy * ex;
-    const double dx = ax - ox, dy = ay - oy;
-    double tn = dx * ey - dy * ex, wn = dx * uy - dy * ux;
-    if (den < 0.0) { den = -den; tn = -tn; wn = -wn; }
-    if (den > 0.0 && tn >= 0.0 && wn >= 0.0 && wn <= den && !(tn * kRangeGuard >= best * den)) {
-        const double t = tn / den;
-        if (t < best) {
-            best = t;
-            bcos = fabs(ux * v[2] + uy * v[3]);
-            bface = face;
-            bel = el;
-        }
-    }
-}
-
 // One reading: the ray from (ox, oy) along (ux, uy) at row r.  S: the packed block (LDS or global).
 __device__ inline void cast_ray(const RangeArgs &g, const double *S, bool live, long r, double ox, double oy, double ux, double uy,
                                 double &best, double &bcos, int &bface, int &bel)
 {
-    best = INFINITY;
-    bcos = NAN;
-    bface = 0;
-    bel = -2;
-    // 1. the wall, from inside or on the box only
-    if (g.has_field && ox >= g.xmin && ox <= g.xmax && oy >= g.ymin && oy <= g.ymax) {
-        double tx = INFINITY, ty = INFINITY;
-        int fx = 0, fy = 1;
-        if (ux > 0.0) { tx = (g.xmax - ox) / ux; fx = 2; }
-        else if (ux < 0.0) tx = (g.xmin - ox) / ux;
-        if (uy > 0.0) { ty = (g.ymax - oy) / uy; fy = 3; }
-        else if (uy < 0.0) ty = (g.ymin - oy) / uy;
-        const bool y_side = ty < tx;                      // a tie: the x side
-        const double t = y_side ? ty : tx;
-        if (t < best) {
-            best = t;
-            bcos = y_side ? fabs(uy) : fabs(ux);
-            bface = y_side ? fy : fx;
-            bel = -1;
-        }
-    }
-    const double slack = g.slack + kCullSlack * (fabs(ox) + fabs(oy));
-    // 2. polygons
-#pragma unroll 1
-    for (int k = 0; k < g.n_poly; k++) {
-        const double *pk = S + g.o_poly + k * 4;
-        if (g.cull && !__any(live && !ray_culled(ox, oy, ux, uy, best, slack, pk[0], pk[1], pk[2]))) continue;
-        const int pc = (int)pk[3];
-        const int p0 = pc >> 5, m = pc & 31;
-#pragma unroll 1
-        for (int j = 0; j < m; j++) edge_test(S + g.o_pv + (p0 + j) * 8, ox, oy, ux, uy, j, k, best, bcos, bface, bel);
-    }
-    // 3. circles
-#pragma unroll 1
-    for (int k = 0; k < g.n_circle; k++) {
-        const double *ck = S + g.o_circ + k * 4;
-        const double cx = ck[0], cy = ck[1], rad = ck[2];
-        if (g.cull && !__any(live && !ray_culled(ox, oy, ux, uy, best, slack, cx, cy, rad))) continue;
-        const double dx = ox - cx, dy = oy - cy;
-        const double b = dx * ux + dy * uy, q = (dx * dx + dy * dy) - rad * rad;
-        const double disc = b * b - q;
-        if (disc >= 0.0) {
-            const double sq = sqrt(disc);
-            double t = -b - sq;
-            if (t < 0.0) t = -b + sq;
-            if (t >= 0.0 && t < best) {
-                best = t;
-                bcos = fabs(ux * ((ox + t * ux) - cx) + uy * ((oy + t * uy) - cy)) / rad;
-                bface = 0;
-                bel = g.n_poly + k;
-            }
-        }
-    }
+    // 1-3. the wall, the polygons, the circles (vap_raycast.h)
+    const double slack = ray_slack(g, ox, oy);
+    cast_scene(g, S, live, ox, oy, ux, uy, slack, best, bcos, bface, bel);
     // 4. partners: partner o stands at its row clamp(r - shift, 0, n_o - 1); the ray goes into its body frame
 #pragma unroll 1
     for (int o = 0; o < g.Bo; o++) {
@@ -438,16 +354,7 @@ int vap_range_readings(vap_ctx *ctx, int B, long capacity, const double *d_rows,
     if (B > 0 && (!d_counts || (capacity > 0 && !d_rows))) return vap_fail(VAP_ERR_INVALID, "null rows / counts");
     // the sensors
     if (n_sens < 1 || n_sens > kRangeMaxSens) return vap_fail(VAP_ERR_INVALID, "%d sensors (1..%d)", n_sens, kRangeMaxSens);
-    if (!h_sensors) return vap_fail(VAP_ERR_INVALID, "null sensors");
-    for (int s = 0; s < n_sens; s++) {
-        const double *q = h_sensors + 8 * (size_t)s;
-        for (int j = 0; j < 8; j++)
-            if (!std::isfinite(q[j])) return vap_fail(VAP_ERR_INVALID, "sensor %d: entry %d is not finite", s, j);
-        if (!(std::fabs(std::hypot(q[2], q[3]) - 1.0) <= 1e-12))
-            return vap_fail(VAP_ERR_INVALID, "sensor %d: the beam direction (%g, %g) is not a unit vector", s, q[2], q[3]);
-        if (!(0.0 <= q[4] && q[4] <= q[5])) return vap_fail(VAP_ERR_INVALID, "sensor %d: window %g .. %g (0 <= r_min <= r_max)", s, q[4], q[5]);
-        if (!(0.0 <= q[6] && q[6] <= 1.0)) return vap_fail(VAP_ERR_INVALID, "sensor %d: min_cos %g outside [0, 1]", s, q[6]);
-    }
+    VAP_TRY(check_sensor_rows(n_sens, h_sensors));
     // the scene
     double scale = 0.0;
     int nv = 0;
@@ -474,28 +381,10 @@ int vap_range_readings(vap_ctx *ctx, int B, long capacity, const double *d_rows,
     g.n_sens = n_sens;
     std::memcpy(g.sens, h_sensors, (size_t)n_sens * 8 * sizeof(double));
     // pack: foot [n_foot_o][8] | poly [n_poly][4] | pv [nv][8] | circ [n_circle][4]
-    g.o_poly = n_foot_o * 8;
-    g.o_pv = g.o_poly + n_poly * 4;
-    g.o_circ = g.o_pv + nv * 8;
-    g.n_dbl = g.o_circ + n_circle * 4;
-    const size_t bytes = (size_t)(g.n_dbl > 0 ? g.n_dbl : 1) * sizeof(double);
-    double *h = nullptr;
-    VAP_TRY(scene_stage(ctx, bytes, &h));
+    VAP_TRY(ray_scene_upload(ctx, n_foot_o, h_foot_o, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, nv, g.o_poly, g.o_pv,
+                             g.o_circ, g.n_dbl));
     double far = 0.0;
-    if (Bo > 0) {
-        pack_polygon(h_foot_o, n_foot_o, h);
-        for (int i = 0; i < n_foot_o; i++) far = std::fmax(far, std::hypot(h_foot_o[2 * i], h_foot_o[2 * i + 1]));
-    }
-    for (int k = 0; k < n_poly; k++) {
-        const int p0 = h_poly_start[k], m = h_poly_start[k + 1] - p0;
-        double *pk = h + g.o_poly + (size_t)k * 4;
-        bound_polygon(h_poly_xy + 2 * (size_t)p0, m, pk[0], pk[1], pk[2]);
-        pk[3] = (double)(p0 * 32 + m);
-        pack_polygon(h_poly_xy + 2 * (size_t)p0, m, h + g.o_pv + (size_t)p0 * 8);
-    }
-    for (int k = 0; k < n_circle; k++)
-        for (int j = 0; j < 3; j++) h[g.o_circ + (size_t)k * 4 + j] = h_circles[3 * (size_t)k + j];
-    VAP_TRY(scene_upload(ctx, bytes));
+    for (int i = 0; i < n_foot_o; i++) far = std::fmax(far, std::hypot(h_foot_o[2 * i], h_foot_o[2 * i + 1]));
     g.scene = (const double *)ctx->scene.ptr;
     g.n_poly = n_poly;
     g.n_circle = n_circle;
