@@ -149,6 +149,26 @@ def tile_case(every):
                 O=records(rng, len(ns), K), sensors=rc.SENSORS4, scene=seeded_scene(), rule=rule(GATE_IN, INCIDENCE_DEG, GAIN, every))
 
 
+TRACKING_TILE_K = (64, 256, 1)
+
+
+@functools.lru_cache(maxsize=None)
+def tracking_tile_case(K):
+    """tile_case's routes for vap_tracking_rollouts at a capacity of 160 rows: K = 64 (four routes per workgroup, tiles of 64
+    rows, the last one partial), K = 256 (one route per workgroup) and K = 1 (256 routes per workgroup, tiles of 2 rows) with
+    260 routes, so that a second workgroup holds 4 routes and 252 idle lanes, one of them a route without rows."""
+    base = tile_case(1)
+    B = 260 if K == 1 else len(base["counts"])
+    pick = np.arange(B) % len(base["counts"])
+    rows = np.zeros((B, 160, 8))
+    rows[:, :base["rows"].shape[1]] = base["rows"][pick]
+    counts = base["counts"][pick].copy()
+    if K == 1:
+        counts[257] = 0
+    P = base["P"] if K == 64 else perturbations(np.random.default_rng(640 + K), B, K)
+    return dict(rows=rows, counts=counts, follower=base["follower"], P=P)
+
+
 @functools.lru_cache(maxsize=None)
 def scene_size_case(over):
     """range_cases.scene_size_case's scene, under and over the LDS budget of the packed scene."""

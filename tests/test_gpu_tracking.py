@@ -22,6 +22,7 @@ import pytest
 
 import footprint_ref as fr
 import golden_util as gu
+import odometry_cases as oc
 import tracking_ref as tr
 
 pytestmark = pytest.mark.gpu
@@ -267,7 +268,7 @@ def test_config3_batch_sample(torch_mod):
 
 
 # ---- 3, 4, 5, 7. K sweep: layouts, shared records, short counts, empty routes, invalid records, two calls -------------
-@pytest.mark.parametrize("K,B", [(1, 300), (3, 100), (16, 20), (64, 6), (300, 3)])
+@pytest.mark.parametrize("K,B", [(1, 300), (3, 100), (16, 20), (64, 6), (300, 3), (256, 2), (257, 2), (256, 3), (257, 3)])
 def test_rollout_counts_and_layouts(torch_mod, K, B):
     torch = torch_mod
     tk = trk()
@@ -275,7 +276,8 @@ def test_rollout_counts_and_layouts(torch_mod, K, B):
     cap = 120
     rows = synth_rows(rng, B, cap)
     counts = rng.integers(30, cap + 1, B).astype(np.int32)
-    counts[B // 2] = 0                                          # a route without rows
+    if B > 2:
+        counts[B // 2] = 0                                      # a route without rows (two routes: both have rows)
     counts[0], counts[B - 1] = cap + 500, cap                   # clamped to capacity
     if B > 4:
         counts[1] = -3                                          # clamped to 0
@@ -317,15 +319,56 @@ def test_rollout_counts_and_layouts(torch_mod, K, B):
     np.testing.assert_array_equal(bits(shared)["stats"][B - 1], bits(res)["stats"][B - 1])
     # explicit edge outputs
     e = B // 2
-    assert torch.isnan(res["stats"][e]).all() and (res["stat_rows"][e] == -1).all() and (res["counts"][e * K:(e + 1) * K] == 0).all()
-    assert torch.isnan(res["worst"][e]) and torch.isnan(res["mean"][e])
-    assert (int(res["worst_rollout"][e]), int(res["worst_row"][e]), int(res["n_exceeding"][e])) == (-1, -1, 0)
+    if B > 2:
+        assert torch.isnan(res["stats"][e]).all() and (res["stat_rows"][e] == -1).all() and (res["counts"][e * K:(e + 1) * K] == 0).all()
+        assert torch.isnan(res["worst"][e]) and torch.isnan(res["mean"][e])
+        assert (int(res["worst_rollout"][e]), int(res["worst_row"][e]), int(res["n_exceeding"][e])) == (-1, -1, 0)
     if K >= 3:
         assert torch.isnan(res["stats"][:, K // 2]).all() and (res["stat_rows"][:, K // 2] == -1).all()
         assert (res["counts"].reshape(B, K, 2)[:, K // 2, 0] == 0).all()
         assert (res["worst_rollout"] != K // 2).all()
     else:
         assert torch.isnan(res["worst"][3]) and int(res["worst_rollout"][3]) == -1 and int(res["n_exceeding"][3]) == 0
+
+
+# ---- the edges of the staged tiles --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("K", oc.TRACKING_TILE_K)
+def test_tile_edges(torch_mod, K):
+    """Routes of 63, 64, 65 and 129 rows with 10 settle rows at a capacity of 160, executed rows on (odometry_cases.
+    tracking_tile_case): K = 64 stages four routes in tiles of 64 rows, the last one partial; K = 256 one route; K = 1 stages
+    256 routes in tiles of 2 rows, and its second workgroup holds 4 routes, one of them without rows, and 252 idle lanes.
+    test_tracking_cpu.py holds, on the reference alone, that no rollout of these inputs is excused.  At K = 64 the same call
+    through odometry.rollouts with the ideal record, no start offset and no sensors gives the same bits."""
+    torch = torch_mod
+    tk = trk()
+    case = oc.tracking_tile_case(K)
+    rows, counts, P = case["rows"], case["counts"], case["P"]
+    follower = tk.Follower(**case["follower"])
+    d_rows, d_counts = torch.tensor(rows, device="cuda:0"), torch.tensor(counts, device="cuda:0")
+    res = tk.rollouts(d_rows, d_counts, follower, P, time_step=DT, executed=True)
+    torch.cuda.synchronize()
+    worst = Worst()
+    n_cmp, n_exc, _ = compare(res, rows, counts, follower, P, executed=True, worst=worst)
+    print(f"tile edges K = {K}: {n_cmp} rollouts compared, {n_exc} excluded, worst D {worst.d:.2e}, worst |kernel - reference| {worst.k:.2e}")
+    assert n_exc == 0 and n_cmp == K * int((counts > 0).sum())
+    assert (res["counts"][:, 0].cpu().numpy() == np.repeat(np.where(counts > 0, counts + 10, 0), K)).all()
+    if K != 64:
+        return
+    from vexautonomousplanner_amd import odometry
+    P0 = P.copy()
+    P0[..., 0:3] = 0.0                                          # the estimate starts on row 0: no start offset
+    ref = tk.rollouts(d_rows, d_counts, follower, P0, time_step=DT, executed=True)
+    got = odometry.rollouts(d_rows, d_counts, follower, P0, np.broadcast_to(oc.orf.IDEAL, P0.shape).copy(), time_step=DT, executed=True)
+    torch.cuda.synchronize()
+    a, b = bits(ref, ("worst", "mean", "worst_rollout", "worst_row", "n_exceeding", "counts")), \
+        bits(got, ("worst", "mean", "worst_rollout", "worst_row", "n_exceeding", "counts"))
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+    np.testing.assert_array_equal(bits(ref, ("stats",))["stats"][..., :5], bits(got, ("stats",))["stats"][..., :5])
+    np.testing.assert_array_equal(ref["stat_rows"].cpu().numpy(), got["stat_rows"][..., :2].cpu().numpy())
+    ec = ref["counts"][:, 0].cpu().numpy()
+    live = np.arange(ref["rows"].shape[1])[None, :] < ec[:, None]
+    np.testing.assert_array_equal(ref["rows"].cpu().numpy()[live].view(np.int64), got["rows"].cpu().numpy()[live].view(np.int64))
 
 
 # ---- a large, known saturated-row count ------------------------------------------------------------------------------

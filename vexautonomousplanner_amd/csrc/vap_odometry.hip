@@ -6,9 +6,11 @@
 // per side, a gyro scale and drift), and reset in x or y by the readings vap_range_readings would give for the true pose.
 // Definitions: include/vap.h.
 //
-// One kernel, a lane per rollout, in vap_tracking.hip's layout: R = 256 / K whole routes per workgroup for K <= 256, several
-// workgroups per route above it; the five reference columns staged in double-buffered LDS tiles, the next tile's loads in
-// flight while the current one is marched; the route summary in LDS (K <= 256) or by k_odometry_reduce, in ascending k.
+// One kernel, a lane per rollout, built from the followers' common pieces (vap_track_common.h): RolloutLane's layout, R =
+// 256 / K whole routes per workgroup for K <= 256, several workgroups per route above it; RowStage's five reference columns in
+// double-buffered LDS tiles, the next tile's loads in flight while the current one is marched; PlantRecord's start state and
+// ramsete_command on the control errors; the route summary in LDS (K <= 256) or by k_route_reduce, in ascending k.  The host
+// checks and the grid are tracking_setup's and rollout_place's (vap_rollout_host.h).
 // What is new is in the march:
 //   resets    on a row r with r % every == 0 (the same rows for every lane of the workgroup) each sensor casts the true ray
 //             through the scene (vap_raycast.h: the code vap_range.hip compiles, so the reading is that call's bits) and the
@@ -21,20 +23,14 @@
 //             for bit and the call equals vap_tracking_rollouts.
 // No executed rows are needed for the readings: the ray is cast on the pose while it is in registers.  No float atomics;
 // two calls give the same bits.
-#include <climits>
-#include <cmath>
-#include <cstdint>
 #include <cstring>
 
-#include "vap_internal.h"
 #include "vap_raycast.h"
-#include "vap_track_common.h"
+#include "vap_rollout_host.h"
 
 namespace vap {
 namespace {
 
-constexpr int kOdoRows = 512;          // staged rows per LDS buffer, over all routes of the workgroup (vap_tracking.hip's)
-constexpr int kOdoTileMax = 64;        // rows of one route per tile, at most
 constexpr int kOdoLdsDoubles = 2048;   // a packed scene of up to 16 KiB is staged in LDS (vap_range.hip's budget)
 
 // the scene as vap_raycast.h reads it
@@ -57,72 +53,41 @@ struct OdoArgs {
 template <bool LDS>
 __global__ __launch_bounds__(kTrackThreads) void k_odometry_rollouts(OdoArgs a)
 {
-    __shared__ __attribute__((aligned(16))) double stage[2][kOdoRows * 5];
     __shared__ double s_scene[LDS ? kOdoLdsDoubles : 1];
-    __shared__ int s_n[kTrackThreads];
-    __shared__ int s_total;
     const TrackArgs &g = a.t;
     const int tid = threadIdx.x;
     const int R = g.R, tile = g.tile, ns = a.n_sens;
-    // which rollout this lane walks
-    const int b0 = g.wpr > 1 ? (int)(blockIdx.x / g.wpr) : (int)blockIdx.x * R;
-    const int lr = g.wpr > 1 ? 0 : tid / g.K;                                  // route within the workgroup
-    const int k = g.wpr > 1 ? (int)(blockIdx.x % g.wpr) * kTrackThreads + tid : tid % g.K;
-    const int b = b0 + lr;
-    const bool inside = lr < R && b < g.B && k < g.K;
-    if (tid == 0) s_total = 0;
-    if (tid < R) {
-        int n = 0;
-        if (b0 + tid < g.B) {
-            const long c = g.counts[(size_t)(b0 + tid) * g.stride];
-            n = (int)(c < 0 ? 0 : (c > g.cap ? g.cap : c));
-        }
-        s_n[tid] = n;
-    }
+    const RolloutLane ln(g, true);
     const double *S = a.sc.block;
-    if (LDS) {
+    if (LDS) {                                        // RowStage::begin's first barrier covers these writes
         for (int i = tid; i < a.sc.n_dbl; i += kTrackThreads) s_scene[i] = a.sc.block[i];
         S = s_scene;
     }
-    __syncthreads();
-    if (tid < R && s_n[tid] > 0) atomicMax(&s_total, s_n[tid] + g.settle);
-    __syncthreads();
-    const int wg_total = s_total;                     // steps of the longest route of the workgroup
-    const int n = lr < R ? s_n[lr] : 0;
-    const size_t gi = (size_t)b * g.K + k;            // flattened (b, k)
+    RowStage st;
+    st.begin(g, ln.b0, true);
+    const int wg_total = st.total;
+    const int n = ln.lr < R ? st.n[ln.lr] : 0;
+    const int b = ln.b;
+    const size_t gi = ln.gi;
 
     // the rollout's constants and start state: the plant's and the estimate's
     TrackPlant pl;
     double hx = 0.0, hy = 0.0, hphi = 0.0;            // the estimate
     double encl = 1.0, encr = 1.0, hscale = 1.0, hdrift = 0.0, rscale = 1.0, rbias = 0.0;
     bool valid = false;
-    if (inside && n > 0) {
-        const double *p = g.perturb + (g.shared ? (size_t)k : gi) * 8;
-        const double2 p01 = *(const double2 *)p, p23 = *(const double2 *)(p + 2), p45 = *(const double2 *)(p + 4),
-                      p67 = *(const double2 *)(p + 6);
-        const double *o = a.odo + (a.shared_odo ? (size_t)k : gi) * 8;
+    if (ln.inside && n > 0) {
+        const PlantRecord rec(g, ln);
+        const double *o = a.odo + (a.shared_odo ? (size_t)ln.k : gi) * 8;
         const double2 o01 = *(const double2 *)o, o23 = *(const double2 *)(o + 2), o45 = *(const double2 *)(o + 4),
                       o67 = *(const double2 *)(o + 6);
-        const double tau = p67.x;
-        valid = isfinite(p01.x) && isfinite(p01.y) && isfinite(p23.x) && isfinite(p23.y) && isfinite(p45.x) &&
-                isfinite(p45.y) && isfinite(p67.x) && isfinite(p67.y) && p23.y > 0.0 && p45.x > 0.0 && p45.y > 0.0 && tau >= 0.0;
-        valid = valid && isfinite(o01.x) && isfinite(o01.y) && isfinite(o23.x) && isfinite(o23.y) && isfinite(o45.x) &&
+        valid = rec.valid() && isfinite(o01.x) && isfinite(o01.y) && isfinite(o23.x) && isfinite(o23.y) && isfinite(o45.x) &&
                 isfinite(o45.y) && isfinite(o67.x) && isfinite(o67.y) && o01.x > 0.0 && o01.y > 0.0 && o23.x > 0.0 && o45.x > 0.0;
         if (valid) {
             const double *row0 = g.rows + (size_t)b * (size_t)g.cap * 8;
-            const double v0 = row0[2], w0 = -row0[5];
             hx = row0[6];
             hy = row0[7];
             hphi = -row0[4];
-            pl.x = row0[6] + p01.x;
-            pl.y = row0[7] + p01.y;
-            pl.phi = -row0[4] + p23.x;
-            pl.wl = v0 - w0 * g.T / 2.0;
-            pl.wr = v0 + w0 * g.T / 2.0;
-            pl.gl = p23.y;
-            pl.gr = p45.x;
-            pl.tts = g.T * p45.y;
-            pl.a = tau == 0.0 ? 1.0 : 1.0 - exp(-g.h / tau);
+            rec.start(g, row0, pl);
             encl = o01.x;
             encr = o01.y;
             hscale = o23.x;
@@ -137,56 +102,11 @@ __global__ __launch_bounds__(kTrackThreads) void k_odometry_rollouts(OdoArgs a)
     double *erow = g.exec_rows && valid ? g.exec_rows + gi * (size_t)g.cap_exec * 8 : nullptr;
     double *hrow = a.est_rows && valid ? a.est_rows + gi * (size_t)g.cap_exec * 4 : nullptr;
 
-    // the loader: item j < R * tile is row j % tile of route j / tile of the tile (consecutive threads on consecutive
-    // rows of a route); at most two items per thread
-    const int items = R * tile;
-    double lv[2], lh[2], lw[2], lx[2], ly[2];
-    auto load = [&](int ti) {
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const int j = tid + i * kTrackThreads;
-            lv[i] = lh[i] = lw[i] = lx[i] = ly[i] = 0.0;
-            if (j < items) {
-                const int route = j / tile, r = ti * tile + j % tile, nr = s_n[route];
-                if (nr > 0 && r < nr + g.settle) {
-                    const int src = r < nr ? r : nr - 1;
-                    const double *q = g.rows + ((size_t)(b0 + route) * (size_t)g.cap + (size_t)src) * 8;
-                    const double2 hw = *(const double2 *)(q + 4), xy = *(const double2 *)(q + 6);
-                    lv[i] = r < nr ? q[2] : 0.0;
-                    lh[i] = hw.x;
-                    lw[i] = r < nr ? hw.y : 0.0;
-                    lx[i] = xy.x;
-                    ly[i] = xy.y;
-                }
-            }
-        }
-    };
-    auto store = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const int j = tid + i * kTrackThreads;
-            if (j < items) {
-                double *d = stage[buf] + (size_t)(j % tile) * 5 * R + j / tile;
-                d[0] = lv[i];
-                d[R] = lh[i];
-                d[2 * R] = lw[i];
-                d[3 * R] = lx[i];
-                d[4 * R] = ly[i];
-            }
-        }
-    };
-
-    const int ntiles = (wg_total + tile - 1) / tile;
-    if (ntiles > 0) {
-        load(0);
-        store(0);
-    }
-    __syncthreads();
+    const int ntiles = st.tiles(g);
 #pragma unroll 1
     for (int ti = 0; ti < ntiles; ti++) {
         const bool more = ti + 1 < ntiles;
-        if (more) load(ti + 1);                        // in flight while this tile is marched
-        const double *cur = stage[ti & 1] + (lr < R ? lr : 0);
+        if (more) st.load(g, ti + 1);                  // in flight while this tile is marched
         const int r0 = ti * tile;
         const int rend = min(tile, wg_total - r0);
 #pragma unroll 1
@@ -235,7 +155,7 @@ __global__ __launch_bounds__(kTrackThreads) void k_odometry_rollouts(OdoArgs a)
                 }
             }
             if (!act) continue;
-            const double *q = cur + (size_t)t * 5 * R;
+            const double *q = st.row(g, ti, t, ln.lr);
             const double vr = q[0], phr = -q[R], wref = -q[2 * R], xr = q[3 * R], yr = q[4 * R];
             // 2. errors in the body frame: the true ones, and the ones the follower sees
             double sp, cp;
@@ -262,12 +182,8 @@ __global__ __launch_bounds__(kTrackThreads) void k_odometry_rollouts(OdoArgs a)
                 o[1] = make_double2(hy, (double)mask);
             }
             // 5. RAMSETE on the control errors
-            double se, ce;
-            sincos(heph, &se, &ce);
-            const double kk = g.two_zeta * sqrt(wref * wref + g.b * vr * vr);
-            const double vc = vr * ce + kk * hex;
-            const double wc = wref + kk * heph + g.b * vr * track_sinc(heph, se) * hey;
-            double cl = vc - wc * g.T / 2.0, cr = vc + wc * g.T / 2.0;
+            double cl, cr;
+            ramsete_command(g, vr, wref, hex, hey, heph, cl, cr);
             // 6. saturation, keeping c_L : c_R
             if (track_saturate(cl, cr, g.wmax)) nsat++;
             // 7. substeps: the plant's, then the estimate's from the wheel speeds and the turn rate the plant just used
@@ -286,13 +202,13 @@ __global__ __launch_bounds__(kTrackThreads) void k_odometry_rollouts(OdoArgs a)
                 hphi += dl;
             }
         }
-        if (more) store((ti + 1) & 1);
+        if (more) st.store(g, (ti + 1) & 1);
         __syncthreads();
     }
 
     // final errors against row n - 1, and the rollout's outputs
     const bool have = mrow >= 0;
-    if (inside) {
+    if (ln.inside) {
         double fpos = NAN, fphi = NAN, fest = NAN;
         if (have) {
             const double *ql = g.rows + ((size_t)b * (size_t)g.cap + (size_t)(n - 1)) * 8;
@@ -314,43 +230,17 @@ __global__ __launch_bounds__(kTrackThreads) void k_odometry_rollouts(OdoArgs a)
             o[2] = have ? nacc : -1;
             o[3] = have ? nrej : -1;
         }
-        if (g.exec_counts) {
-            g.exec_counts[gi * 2] = my_total;
-            g.exec_counts[gi * 2 + 1] = 0;
-        }
-        if (g.part_e) {
-            g.part_e[gi] = maxe;
-            g.part_row[gi] = mrow;
-        }
+        rollout_outputs(g, gi, my_total, maxe, mrow);
     }
-    if (g.wpr > 1) return;                              // the route's summary: k_odometry_reduce
+    if (g.wpr > 1) return;                              // the route's summary: k_route_reduce
     // the route's summary inside the workgroup: the stage buffers are free (the last barrier is behind every thread)
-    double *s_e = stage[0];
-    int *s_r = s_n;
-    __syncthreads();                                    // s_n was read above
+    double *s_e = st.buf;
+    int *s_r = st.n;
+    __syncthreads();                                    // st.n was read above
     s_e[tid] = maxe;
-    s_r[tid] = inside ? mrow : -1;
+    s_r[tid] = ln.inside ? mrow : -1;
     __syncthreads();
-    if (inside && k == 0) {
-        TrackSummary sum;
-#pragma unroll 1
-        for (int kk = 0; kk < g.K; kk++) sum.take(s_e[tid + kk], s_r[tid + kk], kk, g.tol);
-        sum.store(g, b);
-    }
-}
-
-// K > 256: per route, its rollouts' partials in ascending k
-__global__ __launch_bounds__(64) void k_odometry_reduce(TrackArgs g)
-{
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= g.B) return;
-    TrackSummary sum;
-#pragma unroll 1
-    for (int kk = 0; kk < g.K; kk++) {
-        const size_t p = (size_t)b * g.K + kk;
-        sum.take(g.part_e[p], g.part_row[p], kk, g.tol);
-    }
-    sum.store(g, b);
+    route_summary<TrackSummary>(g, ln, g.K, s_e, s_r, nullptr, g.tol);
 }
 
 }  // namespace
@@ -370,9 +260,10 @@ int vap_odometry_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_ro
     // host validation first: it needs no device
     OdoArgs a{};
     TrackArgs &g = a.t;
-    VAP_TRY(tracking_setup(B, capacity, d_rows, d_counts, counts_stride, time_step, f, K, shared_perturb, d_perturb, d_stats,
-                           d_stat_rows, d_worst, d_mean, d_worst_rollout, d_worst_row, d_n_exceeding, cap_exec, d_exec_rows,
-                           d_exec_counts, g));
+    const RolloutCall call{B, capacity, d_rows, d_counts, counts_stride, time_step, K, shared_perturb, d_perturb, d_stats, d_stat_rows,
+                           d_worst, d_mean, d_worst_rollout, d_worst_row, d_n_exceeding, nullptr, nullptr, cap_exec, d_exec_rows,
+                           d_exec_counts};
+    VAP_TRY(tracking_setup(call, f, g));
     if (B > 0 && !d_odometry) return vap_fail(VAP_ERR_INVALID, "null odometry records");
     if ((((uintptr_t)d_odometry | (uintptr_t)d_est_rows) & 15) != 0)
         return vap_fail(VAP_ERR_INVALID, "odometry records and estimate rows must be 16-byte aligned");
@@ -416,33 +307,14 @@ int vap_odometry_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_ro
         sc.cull = ctx->footprint_cull;
     }
 
-    // the grid and the summary's scratch: vap_tracking.hip's
-    const bool summary = g.worst || g.mean || g.worst_rollout || g.worst_row || g.n_exceeding;
-    size_t part_bytes = 0;
     long grid;
-    if (K <= kTrackThreads) {
-        g.R = kTrackThreads / K;
-        g.wpr = 1;
-        grid = ((long)B + g.R - 1) / g.R;
-    } else {
-        g.R = 1;
-        g.wpr = (K + kTrackThreads - 1) / kTrackThreads;
-        grid = (long)B * g.wpr;
-        if (summary) part_bytes = (size_t)B * (size_t)K * (sizeof(double) + sizeof(int));
-    }
-    if (grid > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "%d routes x %d rollouts: too many workgroups for one launch", B, K);
-    if (part_bytes) {
-        VAP_TRY(ctx->ensure(ctx->track_part, part_bytes));
-        g.part_e = (double *)ctx->track_part.ptr;
-        g.part_row = (int *)(g.part_e + (size_t)B * (size_t)K);
-    }
-    g.tile = kOdoRows / g.R < kOdoTileMax ? kOdoRows / g.R : kOdoTileMax;
+    VAP_TRY(rollout_place(ctx, g, g.summary(), 1, 0, nullptr, grid));
+    g.tile = stage_tile(g.R, false);
     if (n_sens > 0 && a.sc.n_dbl > kOdoLdsDoubles)
         hipLaunchKernelGGL(k_odometry_rollouts<false>, dim3((unsigned)grid), dim3(kTrackThreads), 0, ctx->stream, a);
     else
         hipLaunchKernelGGL(k_odometry_rollouts<true>, dim3((unsigned)grid), dim3(kTrackThreads), 0, ctx->stream, a);
-    if (g.wpr > 1 && summary)
-        hipLaunchKernelGGL(k_odometry_reduce, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, g);
+    rollout_reduce<TrackSummary>(ctx, g);
     HIP_TRY(hipGetLastError());
     return VAP_OK;
 }

@@ -9,8 +9,8 @@
 // Two kernels (three with K > 256):
 //   check    a workgroup per route: rows 0 .. n - 1 for a negative speed (bit 0) and a non-finite x, y or v (bit 1), ORed
 //            with integer atomics in LDS; the mask goes to context scratch for the rollouts and to d_route_status.
-//   rollouts a lane per rollout, vap_tracking.hip's route-to-workgroup mapping (K <= 256: 256 / K whole routes per
-//            workgroup; K > 256: ceil(K / 256) workgroups per route).  Unlike RAMSETE's, the lanes of a route are not at
+//   rollouts a lane per rollout in the followers' common layout (K <= 256: 256 / K whole routes per workgroup; K > 256:
+//            ceil(K / 256) workgroups per route), written out here (below).  Unlike RAMSETE's, the lanes of a route are not at
 //            the same row: each carries its own closest segment ic and lookahead segment il, which only advance.  A lane
 //            keeps the three points P_ic, P_ic+1, P_ic+2 and the two points P_il, P_il+1 in registers with the chord
 //            length c and the segment length of each pointer; an advance loads one point (the K lanes of a route hit the
@@ -18,18 +18,20 @@
 //            len_i in index order, so c is the same number whichever pointer computed it.  The total chord length and
 //            the last tangent are needed only once il has reached the last segment; they are formed there.  Nothing
 //            waits across lanes: every loop is bounded by n.
-//   summary  as vap_tracking.hip: K <= 256 the first lane of each route walks its K rollouts in LDS in ascending k;
-//            K > 256 the partials go to context scratch and k_pursuit_reduce walks them, a lane per route.  No float
-//            atomics, so two calls give the same bits.
+//   summary  as vap_tracking.hip, with PursuitSummary (the rollouts that never arrived): K <= 256 the first lane of each
+//            route walks its K rollouts in LDS in ascending k; K > 256 the partials, the row of arrival
+//            among them, go to context scratch and k_route_reduce walks them, a lane per route.  No float atomics, so two
+//            calls give the same bits.
 //   modes    as vap_tracking.hip: pursuit_rollouts<MODE> is the march; k_pursuit_rollouts<false / true>,
 //            k_pursuit_clearance and k_pursuit_clearance_split (vap_rollout_clearance.hip, through pursuit_setup /
-//            pursuit_launch) instantiate it.  Only the split cuts the row loop into tiles with a barrier each.
-#include <climits>
-#include <cmath>
-#include <cstdint>
-
-#include "vap_internal.h"
-#include "vap_track_common.h"
+//            pursuit_launch) instantiate it.  Only the split cuts the row loop into tiles of kSplitRows rows with a barrier
+//            each, on SplitLds' buffers.
+// The plant, the count clamp, the outputs every follower writes, the reduce kernel, the split's buffers and the host's common
+// checks, grid and launches are vap_track_common.h and vap_rollout_host.h.  This file holds the pure-pursuit march,
+// k_pursuit_check, PursuitSummary and the checks of vap_pursuit's own fields, and, unlike the other two followers, its own
+// lane mapping, record parsing, plant start, split schedule and summary walk in LDS: these kernels sit where any change
+// around the march moves their scalar spills and scratch (see PursuitArgs in vap_track_common.h).
+#include "vap_rollout_host.h"
 
 namespace vap {
 
@@ -41,8 +43,7 @@ __global__ __launch_bounds__(kCheckThreads) void k_pursuit_check(PursuitArgs g)
     const int b = blockIdx.x, tid = threadIdx.x;
     if (tid == 0) s_mask = 0;
     __syncthreads();
-    const long c = g.counts[(size_t)b * g.stride];
-    const int n = (int)(c < 0 ? 0 : (c > g.cap ? g.cap : c));
+    const int n = route_rows(g, b);
     int m = 0;
     for (int r = tid; r < n; r += kCheckThreads) {
         const double *q = g.rows + ((size_t)b * (size_t)g.cap + (size_t)r) * 8;
@@ -93,7 +94,7 @@ struct PursuitSummary : TrackSummary {
     int nun = 0;
     __device__ void take(double e, int r, int arrived, int kk, double tol)
     {
-        TrackSummary::take(e, r, kk, tol);
+        TrackSummary::take(e, r, 0, kk, tol);
         nun += r >= 0 && arrived < 0 ? 1 : 0;
     }
     __device__ void store(const PursuitArgs &g, int b) const
@@ -114,11 +115,8 @@ __device__ __forceinline__ void pursuit_rollouts(const PursuitArgs &g, const Tra
     const int tid = threadIdx.x;
     const int R = g.R;
     const bool producer = !SPLIT || tid < kTrackThreads;     // SPLIT: the threads behind the rollout lanes take clearances
-    double *s_pose = nullptr, *s_cap = nullptr;
-    if constexpr (SPLIT) {
-        s_pose = lds_doubles<2 * kSplitTile, 0>();
-        s_cap = lds_doubles<2 * kTrackThreads, 1>();
-    }
+    SplitLds sl;
+    if constexpr (SPLIT) sl.begin();
     // which rollout this lane walks
     const int b0 = g.wpr > 1 ? (int)(blockIdx.x / g.wpr) : (int)blockIdx.x * R;
     const int lr = g.wpr > 1 ? 0 : tid / g.K;                                  // route within the workgroup
@@ -127,10 +125,7 @@ __device__ __forceinline__ void pursuit_rollouts(const PursuitArgs &g, const Tra
     const bool inside = producer && lr < R && b < g.B && k < g.K;
     const size_t gi = (size_t)b * g.K + k;            // flattened (b, k)
     int n = 0;
-    if (inside && g.status[b] == 0) {
-        const long c = g.counts[(size_t)b * g.stride];
-        n = (int)(c < 0 ? 0 : (c > g.cap ? g.cap : c));
-    }
+    if (inside && g.status[b] == 0) n = route_rows(g, b);
     const double *route = g.rows + (size_t)(inside ? b : 0) * (size_t)g.cap * 8;
 
     // the rollout's constants and start state
@@ -207,20 +202,20 @@ __device__ __forceinline__ void pursuit_rollouts(const PursuitArgs &g, const Tra
             rbeg = rstop = ti * kSplitRows;
             if (!producer) {
                 if (ti >= 1 && ti <= ntiles)
-                    split_clear(*c, s_pose, s_cap, ti - 1, min(kSplitRows, wg_total - (ti - 1) * kSplitRows), tid - kTrackThreads,
+                    sl.clear(*c, ti - 1, min(kSplitRows, wg_total - (ti - 1) * kSplitRows), tid - kTrackThreads,
                                 (int)blockDim.x - kTrackThreads);
             } else {
                 if (ti >= 2)
-                    split_fold(acc, s_pose, ti - 2, (ti - 2) * kSplitRows, min(kSplitRows, wg_total - (ti - 2) * kSplitRows), my_total,
+                    sl.fold(acc, ti - 2, (ti - 2) * kSplitRows, min(kSplitRows, wg_total - (ti - 2) * kSplitRows), my_total,
                                tid, c->margin);
-                s_cap[(size_t)(ti & 1) * kTrackThreads + tid] = acc.best;
+                sl.cap[(size_t)(ti & 1) * kTrackThreads + tid] = acc.best;
                 if (ti < ntiles) rstop = min(rbeg + kSplitRows, wg_total);
             }
         }
 #pragma unroll 1
         for (int r = rbeg; r < rstop; r++) {
             if (SPLIT && r >= my_total) {
-                split_put(s_pose, ti & 1, r - rbeg, tid, NAN, 0.0, 0.0);
+                sl.put(ti, r - rbeg, tid, NAN, 0.0, 0.0);
                 continue;
             }
             // 1. the closest point: ic advances while the next segment is no farther
@@ -256,7 +251,7 @@ __device__ __forceinline__ void pursuit_rollouts(const PursuitArgs &g, const Tra
             // 3. the executed row
             if (EXEC) pl.write_row(erow, r, g.dt);
             if (MODE == kTrackClear) acc.take(c->s, c->margin, pl, r);
-            if (SPLIT) split_put(s_pose, ti & 1, r - rbeg, tid, -track_wrap(pl.phi), pl.x, pl.y);
+            if (SPLIT) sl.put(ti, r - rbeg, tid, -track_wrap(pl.phi), pl.x, pl.y);
             // 4. arrival
             if (arrived < 0) {
                 const double ex = lastx - pl.x, ey = lasty - pl.y;
@@ -358,15 +353,8 @@ __device__ __forceinline__ void pursuit_rollouts(const PursuitArgs &g, const Tra
             o[2] = have ? arrived : -1;
             o[3] = have ? ic : -1;
         }
-        if (g.exec_counts) {
-            g.exec_counts[gi * 2] = my_total;
-            g.exec_counts[gi * 2 + 1] = 0;
-        }
-        if (g.part_e) {
-            g.part_e[gi] = maxe;
-            g.part_row[gi] = mrow;
-            g.part_arr[gi] = arrived;
-        }
+        rollout_outputs(g, gi, my_total, maxe, mrow);
+        if (g.part_e) g.part_aux[gi] = arrived;
         if (MODE == kTrackClear || SPLIT) acc.store(*c, gi);
     }
     if (g.wpr > 1) return;                              // the route's summary: k_pursuit_reduce
@@ -417,24 +405,7 @@ __global__ __launch_bounds__(kSplitThreads) void k_pursuit_clearance_split(Pursu
     pursuit_rollouts<kTrackSplit>(g, &c);
 }
 
-// K > 256: per route, its rollouts' partials in ascending k
-__global__ __launch_bounds__(64) void k_pursuit_reduce(PursuitArgs g)
-{
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= g.B) return;
-    PursuitSummary sum;
-#pragma unroll 1
-    for (int kk = 0; kk < g.K; kk++) {
-        const size_t p = (size_t)b * g.K + kk;
-        sum.take(g.part_e[p], g.part_row[p], g.part_arr[p], kk, g.tol);
-    }
-    sum.store(g, b);
-}
-
-int pursuit_setup(int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride, double time_step,
-                  const vap_pursuit *f, int K, int shared_perturb, const double *d_perturb, double *d_stats, int *d_stat_rows,
-                  double *d_worst, double *d_mean, int *d_worst_rollout, int *d_worst_row, int *d_n_exceeding, int *d_n_unfinished,
-                  int *d_route_status, long cap_exec, double *d_exec_rows, int *d_exec_counts, PursuitArgs &g)
+int pursuit_setup(const RolloutCall &c, const vap_pursuit *f, PursuitArgs &g)
 {
     // host validation first: it needs no device
     if (!f) return vap_fail(VAP_ERR_INVALID, "null follower");
@@ -445,101 +416,25 @@ int pursuit_setup(int B, long capacity, const double *d_rows, const int *d_count
     if (!(f->min_speed >= 0.0) || !(f->arrive_tolerance >= 0.0) || !std::isfinite(f->min_speed) || !std::isfinite(f->arrive_tolerance))
         return vap_fail(VAP_ERR_INVALID, "pursuit: min_speed and arrive_tolerance must be >= 0 and finite (got %g, %g)", f->min_speed,
                         f->arrive_tolerance);
-    if (std::isnan(f->tolerance)) return vap_fail(VAP_ERR_INVALID, "pursuit: tolerance is NaN");
-    if (!(time_step > 0.0) || !std::isfinite(time_step)) return vap_fail(VAP_ERR_INVALID, "time_step must be positive and finite (got %g)", time_step);
-    if (f->n_substeps < 1 || f->n_substeps > 16) return vap_fail(VAP_ERR_INVALID, "pursuit: n_substeps %d outside 1..16", f->n_substeps);
-    if (f->settle_rows < 0 || f->settle_rows > 10000) return vap_fail(VAP_ERR_INVALID, "pursuit: settle_rows %d outside 0..10000", f->settle_rows);
-    if (K < 1 || K > 4096) return vap_fail(VAP_ERR_INVALID, "K = %d rollouts per route outside 1..4096", K);
-    if (B < 0 || capacity < 0) return vap_fail(VAP_ERR_INVALID, "bad shape B=%d capacity=%ld", B, capacity);
-    if (counts_stride < 1) return vap_fail(VAP_ERR_INVALID, "counts_stride must be >= 1 (got %d)", counts_stride);
-    if (B > 0 && (!d_counts || (capacity > 0 && !d_rows))) return vap_fail(VAP_ERR_INVALID, "null rows / counts");
-    if (B > 0 && !d_perturb) return vap_fail(VAP_ERR_INVALID, "null perturbation records");
-    if (capacity + f->settle_rows > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "capacity %ld + settle rows above %d", capacity, INT_MAX);
-    if (d_exec_rows && cap_exec < capacity + f->settle_rows)
-        return vap_fail(VAP_ERR_INVALID, "cap_exec %ld below capacity + settle_rows = %ld", cap_exec, capacity + f->settle_rows);
-    if ((((uintptr_t)d_rows | (uintptr_t)d_perturb | (uintptr_t)d_stats | (uintptr_t)d_exec_rows) & 15) != 0)
-        return vap_fail(VAP_ERR_INVALID, "rows, perturbation records, stats and executed rows must be 16-byte aligned");
-    g.rows = d_rows;
-    g.counts = d_counts;
-    g.cap = capacity;
-    g.stride = counts_stride;
-    g.B = B;
-    g.K = K;
-    g.shared = shared_perturb != 0;
-    g.perturb = d_perturb;
-    g.T = f->track_width;
+    VAP_TRY(rollout_check(c, "pursuit", *f, g));
     g.L = f->lookahead;
     g.vmin = f->min_speed;
     g.atol = f->arrive_tolerance;
-    g.wmax = f->wheel_speed_max;
-    g.tol = f->tolerance;
-    g.dt = time_step;
-    g.h = time_step / (double)f->n_substeps;
-    g.nsub = f->n_substeps;
-    g.settle = f->settle_rows;
-    g.stats = d_stats;
-    g.stat_rows = d_stat_rows;
-    g.worst = d_worst;
-    g.mean = d_mean;
-    g.worst_rollout = d_worst_rollout;
-    g.worst_row = d_worst_row;
-    g.n_exceeding = d_n_exceeding;
-    g.n_unfinished = d_n_unfinished;
-    g.route_status = d_route_status;
-    g.cap_exec = cap_exec;
-    g.exec_rows = d_exec_rows;
-    g.exec_counts = d_exec_counts;
+    g.n_unfinished = c.n_unfinished;
+    g.route_status = c.route_status;
     return VAP_OK;
 }
 
 int pursuit_launch(vap_ctx *ctx, PursuitArgs &g, TrackClear *clear)
 {
-    const int B = g.B, K = g.K;
-    const bool summary = g.worst || g.mean || g.worst_rollout || g.worst_row || g.n_exceeding || g.n_unfinished;
-    // context scratch: the routes' status words, then (K > 256 with a summary) the rollouts' partials, then those of the
-    // clearance summary
-    const size_t status_bytes = (((size_t)B * sizeof(int)) + 15) & ~(size_t)15;
-    size_t part_bytes = 0;
-    const size_t clear_bytes = clear_part_bytes(clear, B, K);
+    // context scratch: the routes' status words, then the partials
     long grid;
-    if (K <= kTrackThreads) {
-        g.R = kTrackThreads / K;
-        g.wpr = 1;
-        grid = ((long)B + g.R - 1) / g.R;
-    } else {
-        g.R = 1;
-        g.wpr = (K + kTrackThreads - 1) / kTrackThreads;
-        grid = (long)B * g.wpr;
-        if (summary) part_bytes = (size_t)B * (size_t)K * (sizeof(double) + 2 * sizeof(int));
-    }
-    if (grid > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "%d routes x %d rollouts: too many workgroups for one launch", B, K);
-    VAP_TRY(ctx->ensure(ctx->track_part, status_bytes + part_bytes + clear_bytes));
+    VAP_TRY(rollout_place(ctx, g, g.summary(), 2, (((size_t)g.B * sizeof(int)) + 15) & ~(size_t)15, clear, grid));
     g.status = (int *)ctx->track_part.ptr;
-    if (part_bytes) {
-        const size_t np = (size_t)B * (size_t)K;
-        g.part_e = (double *)((char *)ctx->track_part.ptr + status_bytes);
-        g.part_row = (int *)(g.part_e + np);
-        g.part_arr = g.part_row + np;
-    }
-    if (clear_bytes) clear_part_place(clear, (char *)ctx->track_part.ptr + status_bytes + part_bytes, B, K);
-
-    hipLaunchKernelGGL(k_pursuit_check, dim3((unsigned)B), dim3(kCheckThreads), 0, ctx->stream, g);
-    // the clearance split off the rollout lanes where every workgroup gets a CU of its own (K = 16 at config 3: one rollout
-    // wave per SIMD, which cannot hide the clearance's loads); with more workgroups than CUs the lanes' own clearance,
-    // several workgroups to a CU, measured faster
-    const bool split = clear && grid <= track_cus(ctx->device);
-    if (split)
-        hipLaunchKernelGGL(k_pursuit_clearance_split, dim3((unsigned)grid), dim3(kSplitThreads), 0, ctx->stream, g, *clear);
-    else if (clear)
-        hipLaunchKernelGGL(k_pursuit_clearance, dim3((unsigned)grid), dim3(kTrackThreads), 0, ctx->stream, g, *clear);
-    else if (g.exec_rows)
-        hipLaunchKernelGGL(k_pursuit_rollouts<true>, dim3((unsigned)grid), dim3(kTrackThreads), 0, ctx->stream, g);
-    else
-        hipLaunchKernelGGL(k_pursuit_rollouts<false>, dim3((unsigned)grid), dim3(kTrackThreads), 0, ctx->stream, g);
-    if (g.wpr > 1 && summary)
-        hipLaunchKernelGGL(k_pursuit_reduce, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, g);
-    HIP_TRY(hipGetLastError());
-    return VAP_OK;
+    hipLaunchKernelGGL(k_pursuit_check, dim3((unsigned)g.B), dim3(kCheckThreads), 0, ctx->stream, g);
+    return rollout_run<PursuitSummary>(ctx, g, clear, grid,
+                                       RolloutKernels<PursuitArgs>{k_pursuit_rollouts<false>, k_pursuit_rollouts<true>, k_pursuit_clearance,
+                                                                   k_pursuit_clearance_split});
 }
 
 }  // namespace vap
@@ -553,10 +448,11 @@ int vap_pursuit_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_row
                          double *d_exec_rows, int *d_exec_counts)
 {
     using namespace vap;
+    const RolloutCall call{B, capacity, d_rows, d_counts, counts_stride, time_step, K, shared_perturb, d_perturb, d_stats, d_stat_rows,
+                           d_worst, d_mean, d_worst_rollout, d_worst_row, d_n_exceeding, d_n_unfinished, d_route_status, cap_exec,
+                           d_exec_rows, d_exec_counts};
     PursuitArgs g{};
-    VAP_TRY(pursuit_setup(B, capacity, d_rows, d_counts, counts_stride, time_step, f, K, shared_perturb, d_perturb, d_stats,
-                          d_stat_rows, d_worst, d_mean, d_worst_rollout, d_worst_row, d_n_exceeding, d_n_unfinished, d_route_status,
-                          cap_exec, d_exec_rows, d_exec_counts, g));
+    VAP_TRY(pursuit_setup(call, f, g));
     VAP_TRY(vap_set_device(ctx));
     if (B == 0) return VAP_OK;
     return pursuit_launch(ctx, g, nullptr);

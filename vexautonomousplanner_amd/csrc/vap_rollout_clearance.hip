@@ -15,32 +15,11 @@
 // culling decisions mostly agree across the wave.
 //   summary  K <= 256: inside the follower's kernel, the first lane of each route walks its K rollouts in LDS in ascending
 //            k after the follower's own summary.  K > 256: the rollouts' (clearance, row, element) go to context scratch
-//            behind the follower's partials and k_clearance_reduce walks them, a lane per route.  No float atomics.
-// This file holds the entry point and that reduce kernel; the scene is validated, packed and uploaded by vap_footprint.hip's
-// host functions, the followers' arguments by tracking_setup / pursuit_setup.
-#include <cmath>
-#include <cstdint>
-
-#include "vap_internal.h"
-#include "vap_track_common.h"
-
-namespace vap {
-
-// K > 256: per route, its rollouts' clearance partials in ascending k
-__global__ __launch_bounds__(64) void k_clearance_reduce(TrackClear c, int B, int K)
-{
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= B) return;
-    ClearSummary sum;
-#pragma unroll 1
-    for (int kk = 0; kk < K; kk++) {
-        const size_t p = (size_t)b * K + kk;
-        sum.take(c.part_c[p], c.part_row[p], c.part_el[p], kk, c.margin);
-    }
-    sum.store(c, b);
-}
-
-}  // namespace vap
+//            behind the follower's partials and k_route_reduce<ClearSummary> walks them, a lane per route, launched with
+//            the follower's own reduce by rollout_run (vap_rollout_host.h).  No float atomics.
+// This file holds the entry point; the scene is validated, packed and uploaded by vap_footprint.hip's host functions, the
+// followers' arguments by tracking_setup / pursuit_setup.
+#include "vap_rollout_host.h"
 
 extern "C" {
 
@@ -60,16 +39,12 @@ int vap_rollout_clearance(vap_ctx *ctx, int follower_kind, const void *follower,
     const bool pursuit = follower_kind == VAP_FOLLOWER_PURSUIT;
     if (!pursuit && (d_n_unfinished || d_route_status))
         return vap_fail(VAP_ERR_INVALID, "d_n_unfinished and d_route_status are the pure-pursuit follower's: NULL with VAP_FOLLOWER_RAMSETE");
+    const RolloutCall call{B, capacity, d_rows, d_counts, counts_stride, time_step, K, shared_perturb, d_perturb, d_stats, d_stat_rows,
+                           d_worst, d_mean, d_worst_rollout, d_worst_row, d_n_exceeding, d_n_unfinished, d_route_status, 0, nullptr, nullptr};
     TrackArgs tg{};
     PursuitArgs pg{};
-    if (pursuit)
-        VAP_TRY(pursuit_setup(B, capacity, d_rows, d_counts, counts_stride, time_step, (const vap_pursuit *)follower, K, shared_perturb,
-                              d_perturb, d_stats, d_stat_rows, d_worst, d_mean, d_worst_rollout, d_worst_row, d_n_exceeding,
-                              d_n_unfinished, d_route_status, 0, nullptr, nullptr, pg));
-    else
-        VAP_TRY(tracking_setup(B, capacity, d_rows, d_counts, counts_stride, time_step, (const vap_follower *)follower, K, shared_perturb,
-                               d_perturb, d_stats, d_stat_rows, d_worst, d_mean, d_worst_rollout, d_worst_row, d_n_exceeding, 0, nullptr,
-                               nullptr, tg));
+    if (pursuit) VAP_TRY(pursuit_setup(call, (const vap_pursuit *)follower, pg));
+    else VAP_TRY(tracking_setup(call, (const vap_follower *)follower, tg));
     if (!std::isfinite(margin)) return vap_fail(VAP_ERR_INVALID, "margin must be finite");
     // the scene
     if (!h_footprint) return vap_fail(VAP_ERR_INVALID, "null footprint");
@@ -92,13 +67,7 @@ int vap_rollout_clearance(vap_ctx *ctx, int follower_kind, const void *follower,
     c.worst_element = d_worst_clear_element;
     c.n_colliding = d_n_colliding;
     c.n_valid = d_n_clear_valid;
-    if (pursuit) VAP_TRY(pursuit_launch(ctx, pg, &c));
-    else VAP_TRY(tracking_launch(ctx, tg, &c));
-    if (c.part_c) {
-        hipLaunchKernelGGL(k_clearance_reduce, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, c, B, K);
-        HIP_TRY(hipGetLastError());
-    }
-    return VAP_OK;
+    return pursuit ? pursuit_launch(ctx, pg, &c) : tracking_launch(ctx, tg, &c);
 }
 
 }  // extern "C"
