@@ -1410,6 +1410,62 @@ int vap_odometry_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_ro
                           double *d_worst, double *d_mean, int *d_worst_rollout, int *d_worst_row, int *d_n_exceeding,
                           long cap_exec, double *d_exec_rows, int *d_exec_counts, double *d_est_rows);
 
+/* ---- a routine's waits against its partners, every slot at once ------------------------------------------------------------
+ * vap_conflict_shifts delays a whole route, and a caller can delay everything from one slot on.  Neither says "leave the start
+ * before the partner parks on it, then wait at site 1 until the crossing is free".  A chained routine stands still at every
+ * slot boundary, so a wait there is free: these two calls return, per routine, how many rows to wait in front of every slot
+ * so that the whole routine clears every partner and finishes as early as possible.
+ *   side A    R routines: d_rows_a [R][cap_a][8], d_counts_a with stride_a, the footprint and the pose (columns 4, 6, 7, phi =
+ *             -heading) as vap_footprint_conflicts reads them; n = the count clamped to 0 .. cap_a.  d_seg_start [R][M] int32, 1
+ *             <= M <= VAP_TIMELINE_MAX_LEGS: entry m is the first row of segment m (vap_routine_timeline's d_map[r][m][0]); a
+ *             negative entry is an unused slot.  With S the number of used slots, b_0 .. b_{S-1} their entries and b_S = n,
+ *             segment m is rows [b_m, b_{m+1}).  A routine with n > 0 and S >= 1 is bad unless b_0 == 0, the starts ascend
+ *             strictly, b_{S-1} < n and no used slot stands behind an unused one: VAP_FLAG_BAD_ROUTE is OR-ed into d_flags,
+ *             n_seg = 0, NaN tables.  A routine with n = 0 or S = 0 gets n_seg = 0 and NaN tables without a flag.
+ *   side O    Bo partners: rows, counts, stride and footprint as in vap_conflict_shifts.  At instant t a partner stands at its
+ *             row clamp(t, 0, n_o - 1); one with n_o == 0 takes part in nothing.  Every routine is taken against every
+ *             partner.  The clearance of a pose pair is vap_footprint_conflicts'; a NaN clearance takes part in nothing.
+ *   delays    n_delays = C (1 .. VAP_SCHEDULE_MAX_DELAYS) cumulative delays k = 0 .. C - 1 of k * delay_step rows, delay_step =
+ *             q >= 1; (C - 1) q must not exceed INT_MAX.
+ *   tables    d_move, d_wait [R][M][C] fp64; an unused slot's entries are NaN.
+ *             move[m][k]: the smallest clearance over the partners and the rows i in [b_m, b_{m+1}) of A's row i against the
+ *             partner's pose at instant i + k q.  For the last used segment also A parked at row n - 1 at the instants n + k q
+ *             .. n_o - 1 of each partner (VAP_HOLD_A_LAST of the calls above).
+ *             wait[m][u]: the smallest clearance of the hold pose, A's row max(b_m - 1, 0), at the instants b_m + u q .. b_m +
+ *             (u + 1) q - 1.
+ *             An entry is NaN when nothing finite was examined.  An entry is blocked iff it is < margin; NaN never blocks.
+ *             The tables are a composition of vap_conflict_shifts' table: move[m] is that call on the segment's rows as a
+ *             route of their own at the shifts -(b_m + k q) with hold 12 (14 for the last used segment), wait[m][u] the
+ *             minimum of q entries of the one-row route of the hold pose at hold 12 — the same numbers.
+ *   schedule  indices 0 <= k_0 <= .. <= k_{S-1} < C with move[m][k_m] unblocked for every m and wait[m][u] unblocked for
+ *             every k_{m-1} <= u < k_m (k_{-1} = 0).  The answer has the smallest k_{S-1}; among those, from m = S - 2 down to
+ *             0, the largest k_m: the waits happen as early in the routine as the partners allow.
+ *   outputs   d_delay_rows [R][M] int32: d_0 = k_0 q, d_m = (k_m - k_{m-1}) q rows to wait in front of slot m; 0 for unused
+ *             slots; -1 in EVERY slot when the window holds no schedule or n_seg == 0.  d_total_rows [R]: k_{S-1} q or -1.
+ *             d_clearance [R]: the smallest finite table entry the schedule uses (its moves and its waits), or NaN.  A
+ *             routine with rows and no valid partner is blocked nowhere: all zeros.
+ * vap_schedule_tables packs both sides as vap_conflict_shifts does and sweeps: one wave per (routine, band of up to 64 delays),
+ * one walk over the routine's rows per partner.  Any of d_move, d_wait, d_n_seg [R], d_flags [R] may be NULL.  Context scratch
+ * is the two packs, (R cap_a + Bo cap_o) x 32 B with capacities rounded up to 64 rows; nothing grows with R x M x C beside the
+ * two tables.  VAP_OPT_FOOTPRINT_CULL governs culling; on and off, and two calls, give the same bits.
+ * vap_schedule_solve is the search alone, on any tables the caller hands it: F_{-1} = {0}; G_m[k] = F_{m-1}[k] or (G_m[k - 1]
+ * and wait[m][k - 1] unblocked); F_m[k] = move[m][k] unblocked and G_m[k]; one wave per routine, bit-packed in LDS.  d_n_seg
+ * [R] is S per routine (clamped to 0 .. M); any of the three outputs may be NULL.  Integers only: two calls give the same bits.
+ * VAP_ERR_INVALID: M, n_delays or delay_step < 1, a negative R, Bo or capacity, a count stride < 1, a margin that is not
+ * finite, a bad footprint, null rows, counts, segment starts or (solve) tables or d_n_seg with R > 0.  VAP_ERR_UNSUPPORTED: M
+ * above VAP_TIMELINE_MAX_LEGS, n_delays above VAP_SCHEDULE_MAX_DELAYS, (C - 1) q or a capacity above INT_MAX, more workgroups
+ * than one launch takes.  Arguments are checked before the context is touched.  R = 0 is a no-op; Bo = 0 is valid (NaN tables,
+ * so an all-zero schedule for a routine with rows).  Both work on the context's stream and do not synchronise. */
+#define VAP_SCHEDULE_MAX_DELAYS 4096
+int vap_schedule_tables(vap_ctx *ctx, int n_delays, int delay_step,
+                        int R, long cap_a, const double *d_rows_a, const int *d_counts_a, int stride_a, int n_foot_a,
+                        const double *h_foot_a, int M, const int *d_seg_start,
+                        int Bo, long cap_o, const double *d_rows_o, const int *d_counts_o, int stride_o, int n_foot_o,
+                        const double *h_foot_o,
+                        double *d_move, double *d_wait, int *d_n_seg, uint32_t *d_flags);
+int vap_schedule_solve(vap_ctx *ctx, int R, int M, int n_delays, int delay_step, double margin, const double *d_move,
+                       const double *d_wait, const int *d_n_seg, int *d_delay_rows, int *d_total_rows, double *d_clearance);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,7 @@ CLOSEST_MODES = {"gui": CLOSEST_GUI, "exact": CLOSEST_EXACT}
 CONFLICT_ALL_PAIRS, CONFLICT_MATCHED = 0, 1
 HOLD_A_FIRST, HOLD_A_LAST, HOLD_O_FIRST, HOLD_O_LAST = 1, 2, 4, 8
 CONFLICT_SHIFTS_MAX = 4096
+SCHEDULE_MAX_DELAYS = 4096
 FOLLOWER_RAMSETE, FOLLOWER_PURSUIT = 0, 1
 # vap_range_readings: a reading's status, and the limits
 RANGE_VALID, RANGE_NONE, RANGE_NEAR, RANGE_FAR, RANGE_OBLIQUE, RANGE_BLOCKED, RANGE_BAD_POSE = 0, 1, 2, 3, 4, 5, 6
@@ -76,7 +77,7 @@ EXPORTS = (
     "vap_grid_distances", "vap_route_limits", "vap_velocity_pass_limits", "vap_time_insert_waits", "vap_fit_ex",
     "vap_profile_routes", "vap_time_profile_routes", "vap_time_insert_events", "vap_limit_rows_dtype",
     "vap_closest_points", "vap_route_closest", "vap_footprint_clearance", "vap_footprint_conflicts",
-    "vap_conflict_shifts",
+    "vap_conflict_shifts", "vap_schedule_tables", "vap_schedule_solve",
     "vap_tracking_rollouts", "vap_pursuit_rollouts", "vap_rollout_clearance", "vap_search_sample", "vap_search_update", "vap_plan_grid", "vap_plan_seeds",
     "vap_plan_occupancy", "vap_plan_seeds_occupied", "vap_plan_travel", "vap_plan_order",
     "vap_routine_timeline", "vap_plan_order_timed", "vap_velocity_conditioning",
@@ -225,6 +226,8 @@ def lib():
     L.vap_footprint_conflicts.argtypes = [vp, C.c_int, C.c_int, C.c_double] + side + side + [vp] * 8
     L.vap_conflict_shifts.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int] + side + side + \
         [vp] * 6
+    L.vap_schedule_tables.argtypes = [vp, C.c_int, C.c_int] + side + [C.c_int, vp] + side + [vp] * 4
+    L.vap_schedule_solve.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double] + [vp] * 6
     L.vap_tracking_rollouts.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_double, C.POINTER(FollowerStruct), C.c_int,
                                         C.c_int, vp] + [vp] * 7 + [C.c_long, vp, vp]
     L.vap_pursuit_rollouts.argtypes = [vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_double, C.POINTER(PursuitStruct), C.c_int,

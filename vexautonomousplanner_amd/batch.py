@@ -582,6 +582,17 @@ class BatchedTrajectoryGenerator:
         return fp.earliest_start(tp["rows"], tp["counts"], footprint, others["rows"], others["counts"], others_footprint,
                                  ctx=self.ctx, **kw)
 
+    def routine_schedule(self, tl, footprint, others, others_footprint=None, **kw):
+        """The rows to wait in front of every slot of the routines of ``tl`` — the dict ``timeline.chain`` returned — so that
+        each clears the rows of ``others`` and ends as early as possible (vap_schedule_tables + vap_schedule_solve on this
+        generator's context and torch's current stream; see timeline.schedule for margin, n_delays, delay_step, tables, out,
+        cull and the returned dict)."""
+        from . import timeline
+        for d in (tl, others):
+            if d["rows"].device != self.device:
+                raise ValueError(f"rows must be on {self.device}")
+        return timeline.schedule(tl, footprint, others["rows"], others["counts"], others_footprint, ctx=self.ctx, **kw)
+
     def tracking_rollouts(self, tp, follower, perturbations, **kw):
         """Closed-loop tracking rollouts along the rows of ``tp`` — the dict ``time_profile`` or ``insert_waits``
         returned — under ``perturbations`` (vap_tracking_rollouts on this generator's context and torch's current stream;

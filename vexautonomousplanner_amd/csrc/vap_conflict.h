@@ -1,5 +1,6 @@
-// vap_conflict.h — what the two robot-to-robot calls share: vap_conflict.hip (vap_footprint_conflicts, one start shift)
-// and vap_conflict_shifts.hip (vap_conflict_shifts, a window of them).  The packed footprint and side, the pack kernel
+// vap_conflict.h — what the robot-to-robot calls share: vap_conflict.hip (vap_footprint_conflicts, one start shift),
+// vap_conflict_shifts.hip (vap_conflict_shifts, a window of them) and vap_schedule.hip (vap_schedule_tables, a delay in
+// front of every slot of a routine).  The packed footprint and side, the pack kernel
 // (defined in vap_conflict.hip), the exact polygon pair in one footprint's body frame and the bounding-circle cull.
 #pragma once
 #include <climits>

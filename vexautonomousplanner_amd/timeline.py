@@ -7,7 +7,9 @@ reference's own turn, MPG:319-346 and 487-507), the leg's rows at their place in
 dwell at the site.  The result has the rows and counts of ``time_profile``, so it goes where those go: ``footprint.
 clearance`` (does the turning robot clear the post beside the site?), ``footprint.conflicts`` (a later leg against the
 partner at its real start time), ``tracking.rollouts`` and ``plan.occupancy``.  ``dwell_to_clear`` asks the question a
-crossing partner raises: how much longer must the robot stay at the previous site for the rest of the routine to clear it.
+crossing partner raises: how much longer must the robot stay at the previous site for the rest of the routine to clear it;
+``schedule`` asks it for every slot at once: how long to wait in front of each so that the whole routine clears every partner
+and ends as early as it can.
 
 Nothing here reads the device: the visiting order may stay a device tensor from ``plan.order`` to the chained rows.
 """
@@ -18,10 +20,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._call import buffers, context_for, device_array, ptr, time_rows
+from ._call import buffers, context_for, device_array, dptr, ptr, time_rows
 from .synth import DEFAULT_CONSTRAINTS
 
 MAX_LEGS = _lib.TIMELINE_MAX_LEGS
+MAX_DELAYS = _lib.SCHEDULE_MAX_DELAYS
 FLAGS = {"truncated": _lib.FLAG_TRUNCATED, "bad_route": _lib.FLAG_BAD_ROUTE}
 
 
@@ -168,3 +171,84 @@ def dwell_to_clear(tl, slot, footprint, others_rows, others_counts, others_footp
         d = e["delay_rows"][0]
         out[r] = torch.where(d >= 0, (d.to(torch.float64) + 0.5) * dt, torch.full_like(dt, float("nan")))
     return out
+
+
+def schedule(tl, footprint, others_rows, others_counts, others_footprint=None, margin=0.0, n_delays=256, delay_step=1,
+             tables=False, out=None, device=0, ctx=None, cull=True):
+    """The rows to wait in front of every slot of a routine so that all of it clears the other robots and it ends as early
+    as possible (vap_schedule_tables + vap_schedule_solve; the definitions are in include/vap.h).
+
+      tl             what ``chain`` returned, or a tuple (rows, counts, seg_start): rows and counts as ``footprint.conflicts``
+                     takes its side A ((R, cap, 8) with (R, k) / (R,) counts, device or host), seg_start (R, M) int, device or
+                     host, 1 <= M <= 32: the first row of segment m, -1 for an unused trailing slot (``tl["map"][:, :, 0]``)
+      footprint      (n, 2) body-frame polygon of the routines' robot, counter-clockwise
+      others_rows, others_counts, others_footprint   the other robots' rows on the routines' clock and time step, as
+                     ``footprint.conflicts`` takes its side O; footprint None = the same as ``footprint``.  Every routine is
+                     taken against every one of them
+      margin         a clearance < margin blocks
+      n_delays, delay_step   the window: cumulative delays of k * delay_step rows, k = 0 .. n_delays - 1 (<= 4096)
+      tables         also return move and wait (R, M, n_delays): the clearance of driving segment m at cumulative delay k and
+                     of standing in front of it during delay step u
+      out            optional dict of tensors to fill (delay_rows, total_rows, clearance, n_seg, flags, move, wait)
+    Returns a dict of device tensors: delay_rows (R, M) int32, the rows to wait in front of slot m (0 for unused slots; -1 in
+    every slot when the window holds no schedule, or the routine has no rows, no slots or a bad slot list), total_rows (R,)
+    their sum or -1, clearance (R,) the smallest clearance the schedule meets (NaN: none), n_seg (R,) slots used, flags (R,)
+    (FLAGS: bad_route), start_delay_rows = delay_rows[:, 0], and dwell_add (R, M) seconds: dwell_add[:, m - 1] = (d_m + 0.5) dt
+    for d_m = delay_rows[:, m] > 0, else 0 (``dwell_to_clear``'s convention; column M - 1 is 0), so that ``chain`` with
+    dwell + dwell_add waits exactly d_m more rows at site m - 1.  THE CALLER'S OWN DWELL MUST BE A WHOLE NUMBER OF ROWS
+    (a multiple of dt, or 0) for the sum to stay exact; the wait in front of slot 0 is not a dwell: shift the routine's start
+    by start_delay_rows.  Nothing is read on the host; work runs on torch's current stream and is not synchronised."""
+    from . import footprint as fp
+    foot_a = fp._ccw_polygon(footprint, "footprint")
+    foot_o = foot_a if others_footprint is None else fp._ccw_polygon(others_footprint, "others_footprint")
+    margin, n_delays, delay_step = float(margin), int(n_delays), int(delay_step)
+    if not math.isfinite(margin):
+        raise ValueError(f"margin must be finite (got {margin!r})")
+    if not 1 <= n_delays <= MAX_DELAYS:
+        raise ValueError(f"n_delays must be in [1, {MAX_DELAYS}] (got {n_delays})")
+    if delay_step < 1 or (n_delays - 1) * delay_step > 2 ** 31 - 1:
+        raise ValueError(f"delay_step must be >= 1 and (n_delays - 1) * delay_step below 2^31 (got {delay_step})")
+    if isinstance(tl, dict):
+        rows, counts, seg_start = tl["rows"], tl["counts"], tl["map"][:, :, 0]
+    else:
+        try:
+            rows, counts, seg_start = tl
+        except (TypeError, ValueError):
+            raise ValueError("tl must be what chain returned or a tuple (rows, counts, seg_start)") from None
+    given = [r.device for r in (rows, others_rows) if isinstance(r, torch.Tensor)]
+    rows, counts, single, dev = time_rows(rows, counts, given[0] if given else None, device, "routines")
+    if single:
+        raise ValueError("rows must be (R, capacity, 8): a batch of routines")
+    o_rows, o_counts, _, _ = time_rows(others_rows, others_counts, dev, device, "others")
+    R, cap, Bo, cap_o = int(rows.shape[0]), int(rows.shape[1]), int(o_rows.shape[0]), int(o_rows.shape[1])
+    if isinstance(seg_start, torch.Tensor) and seg_start.device != dev:
+        raise ValueError(f"seg_start is on {seg_start.device}, the rows on {dev}")
+    seg_start = device_array(seg_start, dev, torch.int32)
+    if seg_start is None or seg_start.dim() != 2 or seg_start.shape[0] != R or not 1 <= seg_start.shape[1] <= MAX_LEGS:
+        raise ValueError(f"seg_start must be ({R}, M) with 1 <= M <= {MAX_LEGS}, got "
+                         f"{None if seg_start is None else tuple(seg_start.shape)}")
+    M = int(seg_start.shape[1])
+    shapes = {"delay_rows": ((R, M), torch.int32), "total_rows": ((R,), torch.int32), "clearance": ((R,), torch.float64),
+              "n_seg": ((R,), torch.int32), "flags": ((R,), torch.int32)}
+    res = buffers(out, shapes, dev)
+    # the tables are the call's only R x M x n_delays memory; without ``tables`` they live for this call only
+    tab = buffers(res if tables else None, {"move": ((R, M, n_delays), torch.float64), "wait": ((R, M, n_delays), torch.float64)}, dev)
+    res["flags"].zero_()                          # the call ORs its bit in
+    ctx = context_for(dev, ctx)
+    ctx.set_option(_lib.OPT_FOOTPRINT_CULL, 1 if cull else 0)
+    _lib.check(ctx._L.vap_schedule_tables(
+        ctx.handle, n_delays, delay_step, R, cap, ptr(rows), ptr(counts), int(counts.shape[1]), len(foot_a), dptr(foot_a),
+        M, ptr(seg_start), Bo, cap_o, ptr(o_rows), ptr(o_counts), int(o_counts.shape[1]), len(foot_o), dptr(foot_o),
+        ptr(tab["move"]), ptr(tab["wait"]), ptr(res["n_seg"]), ptr(res["flags"])), "vap_schedule_tables")
+    _lib.check(ctx._L.vap_schedule_solve(
+        ctx.handle, R, M, n_delays, delay_step, margin, ptr(tab["move"]), ptr(tab["wait"]), ptr(res["n_seg"]),
+        ptr(res["delay_rows"]), ptr(res["total_rows"]), ptr(res["clearance"])), "vap_schedule_solve")
+    d = res["delay_rows"]
+    res["start_delay_rows"] = d[:, 0]
+    dt = fp._time_step((rows, counts), (o_rows, o_counts))
+    add = torch.zeros((R, M), dtype=torch.float64, device=dev)
+    if M > 1:
+        later = d[:, 1:]
+        add[:, :M - 1] = torch.where(later > 0, (later.to(torch.float64) + 0.5) * dt, torch.zeros_like(add[:, :M - 1]))
+    res["dwell_add"] = add
+    return res
