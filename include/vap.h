@@ -575,6 +575,9 @@ int vap_route_closest(vap_route *route, int mode, int n, const double *h_queries
  *             row at that minimum), d_min_element (the element at that row), d_first_row (the first row with clearance <
  *             margin, or -1), d_n_below (rows with clearance < margin).  A route without rows gets NaN, -1, -1, -1, 0.
  *             d_row_clearance [B][capacity] (optional): each row's clearance, NaN from counts[b] on.
+ *   NaN       a row with a NaN in its pose (heading, x or y) has a NaN clearance and takes part in nothing: no minimum, no
+ *             first row, no count; a route without a finite clearance gets the outputs of a route without rows.  Infinite
+ *             coordinates are undefined.
  * The check is discrete at the rows' dt: motion between two rows is not swept.  A caller who wants a guard band passes
  * margin > 0 (one 10 ms row moves at most max_vel * dt, 0.04 ft at 4 ft/s).  B = 0 is a no-op. */
 int vap_footprint_clearance(vap_ctx *ctx, int B, long capacity, const double *d_rows, const int *d_counts, int counts_stride,
@@ -600,8 +603,10 @@ int vap_footprint_clearance(vap_ctx *ctx, int B, long capacity, const double *d_
  *   clearance of a pair at a row: the polygon clearance above between the two posed footprints — separated: the Euclidean
  *             distance; overlapping: minus the smallest projection overlap over the edge normals of both; touching: 0.
  *             Symmetric in the two sides.  It saturates at minus the narrower footprint's extent once one projection
- *             contains the other, so deep overlaps tie exactly over many rows.
- *   pairing   VAP_CONFLICT_ALL_PAIRS: every (a, o), P = Bo.  VAP_CONFLICT_MATCHED: Ba == Bo, pairs (i, i) only, P = 1.
+ *             contains the other, so deep overlaps tie exactly over many rows.  A row where either pose has a NaN
+ *             (heading, x or y) has a NaN clearance and takes part in nothing; a pair without a finite clearance gets
+ *             the outputs of an invalid pair.  Infinite coordinates are undefined.
+ *   pairing  VAP_CONFLICT_ALL_PAIRS: every (a, o), P = Bo.  VAP_CONFLICT_MATCHED: Ba == Bo, pairs (i, i) only, P = 1.
  *   outputs   per pair [Ba][P], any pointer may be NULL: d_pair_clearance (the minimum over the pair's rows), d_pair_row
  *             (the first row at that minimum), d_pair_first_row (the first row with clearance < margin, or -1).  A pair
  *             with n_a == 0 or n_o == 0 gets NaN, -1, -1 and takes part in nothing below.

@@ -78,6 +78,10 @@ __device__ double pair_clearance(const double *FA, int na, const double *FO, int
     const double dx = ox - ax, dy = oy - ay;
     const double c = ac * oc + as * os, s = ac * os - as * oc;          // R(phi_o - phi_a)
     const double tx = ac * dx + as * dy, ty = ac * dy - as * dx;        // O's centre in A's frame
+    // A NaN in either pose gives NaN: fmin and fmax drop a NaN operand, so sat_axes would see a footprint's own extent as
+    // the overlap and report the deepest contact.  Every pose entry reaches c + s + tx + ty.
+    const double any = (c + s) + (tx + ty);
+    if (any != any) return NAN;
     double sep = INFINITY;
     bool overlap = sat_axes(FA, na, FO, no, tx, ty, c, s, sep);
     if (overlap) {

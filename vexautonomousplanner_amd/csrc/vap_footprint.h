@@ -158,7 +158,8 @@ __device__ __forceinline__ bool culled(const FootScene &s, double best, double s
     return dx * dx + dy * dy > reach * reach;          // false for best = +inf or NaN
 }
 
-// The clearance of one row and the element that gives it.
+// The clearance of one row and the element that gives it.  A NaN in the pose gives NaN (fmin and fmax drop a NaN operand,
+// so the tests below would turn one into +-inf or into a finite overlap).
 inline __device__ double row_clearance(const FootScene &s, double heading, double x, double y, int &elem)
 {
     const double phi = -heading;
@@ -166,6 +167,7 @@ inline __device__ double row_clearance(const FootScene &s, double heading, doubl
     sincos(phi, &sn, &c);
     double best = INFINITY;
     elem = INT_MAX;
+    if (heading != heading || x != x || y != y) return NAN;
     if (s.has_field) {
         double w = INFINITY;
 #pragma unroll 1
@@ -207,6 +209,7 @@ inline __device__ double row_clearance_capped(const FootScene &s, double heading
     sincos(phi, &sn, &c);
     double best = INFINITY;
     elem = INT_MAX;
+    if (heading != heading || x != x || y != y) return NAN;
     if (s.has_field) {
         double w = INFINITY;
 #pragma unroll 1
