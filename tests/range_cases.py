@@ -141,11 +141,49 @@ def partner_case():
             "others_foot": SQUARE}
 
 
-def reference(rr, case, shift_rows=0):
-    """range_ref.readings of a case."""
+def reference(rr, case, shift_rows=0, **kw):
+    """range_ref.readings of a case (kw: its ftype and ambiguous)."""
     sc = case["scene"]
     return rr.readings(case["rows"], case["counts"], case["sensors"], sc["field"], sc["polygons"], sc["circles"],
-                       case.get("others"), case.get("others_counts"), case.get("others_foot"), shift_rows)
+                       case.get("others"), case.get("others_counts"), case.get("others_foot"), shift_rows, **kw)
+
+
+# ---- random scenes away from the origin -----------------------------------------------------------------------------------------
+TRANSLATIONS = (2.0 ** 10, 2.0 ** 17)          # ft, along both axes
+TRANSLATED_SEEDS = RANDOM_SEEDS[:2]
+TOL = 1e-12                                    # test_gpu_range.py's, the floor of the measured tolerance
+_TOLERANCE = {}
+
+
+def translated_case(seed, d):
+    """random_case(seed) moved by (d, d): field, polygons, circles and poses, each rounded to a double once."""
+    case = random_case(seed)
+    sc = case["scene"]
+    rows = case["rows"].copy()
+    rows[:, :, 6:8] += d
+    circles = sc["circles"].copy()
+    circles[:, :2] += d
+    scene = {"field": tuple(v + d for v in sc["field"]), "polygons": [p + d for p in sc["polygons"]], "circles": circles}
+    return {**case, "scene": scene, "rows": rows}
+
+
+def translation_tolerance(rr, d):
+    """(D, tol, ambiguous) of the translation d: D = the largest |float64 reference - long-double reference| of a range or a
+    cosine over the translated seeds, on the readings both precisions decide alike and the float64 one does not excuse;
+    tol = max(TOL, 8 D), the project's convention; a reading is excused below a margin of max(1e-9, 2 tol)."""
+    if d not in _TOLERANCE:
+        D = 0.0
+        for seed in TRANSLATED_SEEDS:
+            case = translated_case(seed, d)
+            r64, rld = reference(rr, case), reference(rr, case, ftype=np.longdouble)
+            keep = r64["live"][:, :, None] & ~r64["excused"] & (r64["element"] != -2)
+            for k in ("status", "face", "element"):
+                keep &= r64[k] == rld[k]
+            for k in ("t", "cos"):
+                D = max(D, float(np.max(np.abs(r64[k].astype(np.longdouble) - rld[k])[keep])))
+        tol = max(TOL, 8.0 * D)
+        _TOLERANCE[d] = (D, tol, max(1e-9, 2.0 * tol))
+    return _TOLERANCE[d]
 
 
 def excused_shares(ref, summ):

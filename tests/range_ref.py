@@ -18,14 +18,15 @@ INF = np.inf
 class _State:
     """Best candidate per reading, the runner-up's t, the best's own margin and the near misses."""
 
-    def __init__(self, n):
-        self.t = np.full(n, INF)
-        self.cos = np.full(n, np.nan)
+    def __init__(self, n, ftype=np.float64, ambiguous=AMBIGUOUS):
+        self.t = np.full(n, INF, dtype=ftype)
+        self.cos = np.full(n, np.nan, dtype=ftype)
         self.face = np.zeros(n, dtype=np.int64)
         self.el = np.full(n, -2, dtype=np.int64)
-        self.second = np.full(n, INF)
-        self.own = np.full(n, INF)
+        self.second = np.full(n, INF, dtype=ftype)
+        self.own = np.full(n, INF, dtype=ftype)
         self.misses = []
+        self.ambiguous = ambiguous
 
     def offer(self, ok, t, cos, face, el, own):
         t = np.where(ok, t, INF)
@@ -44,7 +45,7 @@ class _State:
     def miss_margin(self):
         m = np.full(self.t.shape, INF)
         for cond, tw, viol in self.misses:
-            matters = cond & (np.maximum(tw, 0.0) <= self.t + AMBIGUOUS)     # it would have taken the lead (or tied)
+            matters = cond & (np.maximum(tw, 0.0) <= self.t + self.ambiguous)     # it would have taken the lead (or tied)
             m = np.where(matters, np.minimum(m, viol), m)
         return m
 
@@ -118,23 +119,27 @@ def pose_polygon(foot, heading, x, y):
     return np.stack([vx, vy], axis=2)
 
 
-def cast(heading, x, y, sensor, field=None, polygons=(), circles=(), partners=()):
+def cast(heading, x, y, sensor, field=None, polygons=(), circles=(), partners=(), ftype=np.float64, ambiguous=AMBIGUOUS):
     """One sensor (8,) at N poses.  partners: a list of (N, n, 2) posed footprints, or None for an absent partner.  Returns a
-    dict of (N,) arrays: status, face, element, t, cos (NaN for status 1 and 6), margin, excused."""
-    heading, x, y = (np.asarray(v, dtype=np.float64) for v in (heading, x, y))
+    dict of (N,) arrays: status, face, element, t, cos (NaN for status 1 and 6), margin, excused.  ftype: the precision of the
+    whole computation (np.longdouble measures the float64 path's own rounding; the inputs are the same doubles); ambiguous: the
+    margin below which a reading is excused."""
+    heading, x, y = (np.asarray(v, dtype=ftype) for v in (heading, x, y))
     n = heading.shape[0]
-    mx, my, bx, by, r_min, r_max, min_cos = (float(v) for v in sensor[:7])
+    mx, my, bx, by, r_min, r_max, min_cos = (ftype(v) for v in sensor[:7])
+    if field is not None:
+        field = tuple(ftype(v) for v in field)
     phi = -heading
     with np.errstate(all="ignore"):
         c, s = np.cos(phi), np.sin(phi)
         ox, oy = x + (c * mx - s * my), y + (s * mx + c * my)
         ux, uy = c * bx - s * by, s * bx + c * by
-    st = _State(n)
+    st = _State(n, ftype, ambiguous)
     if field is not None:
         _wall(st, ox, oy, ux, uy, field)
-    polygons, circles = list(polygons), np.asarray(circles, dtype=np.float64).reshape(-1, 3)
+    polygons, circles = list(polygons), np.asarray(circles, dtype=ftype).reshape(-1, 3)
     for k, verts in enumerate(polygons):
-        _polygon(st, ox, oy, ux, uy, np.asarray(verts, dtype=np.float64), k)
+        _polygon(st, ox, oy, ux, uy, np.asarray(verts, dtype=ftype), k)
     for k, (cx, cy, r) in enumerate(circles):
         _circle(st, ox, oy, ux, uy, cx, cy, r, len(polygons) + k)
     first_partner = len(polygons) + len(circles)
@@ -154,19 +159,19 @@ def cast(heading, x, y, sensor, field=None, polygons=(), circles=(), partners=()
         thresholds = np.minimum(np.minimum(np.abs(st.t - r_min), np.abs(st.t - r_max)), np.abs(st.cos - min_cos))
         margin = np.where(has & (st.el < first_partner), np.minimum(margin, thresholds), margin)
         margin = np.where(bad, INF, margin)
-        excused = ~bad & ((margin < AMBIGUOUS) | (has & (st.cos < COS_EXCUSE)))
+        excused = ~bad & ((margin < ambiguous) | (has & (st.cos < COS_EXCUSE)))
     none = bad | ~has
     return {"status": status, "face": np.where(none, 0, st.face), "element": np.where(none, -2, st.el),
             "t": np.where(none, np.nan, st.t), "cos": np.where(none, np.nan, st.cos), "margin": margin, "excused": excused}
 
 
 def readings(rows, counts, sensors, field=None, polygons=(), circles=(), others=None, others_counts=None, others_foot=None,
-             shift_rows=0):
+             shift_rows=0, ftype=np.float64, ambiguous=AMBIGUOUS):
     """Every reading of a batch: rows (B, cap, 8), counts (B,), sensors (ns, 8).  Returns a dict of (B, cap, ns) arrays
-    (status -1, NaN past counts; ``live`` marks the rows below the counts)."""
-    rows = np.asarray(rows, dtype=np.float64)
+    (status -1, NaN past counts; ``live`` marks the rows below the counts).  ftype, ambiguous: ``cast``'s."""
+    rows = np.asarray(rows, dtype=ftype)
     B, cap = rows.shape[:2]
-    sensors = np.asarray(sensors, dtype=np.float64).reshape(-1, 8)
+    sensors = np.asarray(sensors, dtype=ftype).reshape(-1, 8)
     ns = len(sensors)
     counts = np.clip(np.asarray(counts).reshape(B, -1)[:, 0], 0, cap)
     live = np.arange(cap)[None, :] < counts[:, None]
@@ -174,20 +179,20 @@ def readings(rows, counts, sensors, field=None, polygons=(), circles=(), others=
     h, x, y = rows[bi, ri, 4], rows[bi, ri, 6], rows[bi, ri, 7]
     partners = []
     if others is not None:
-        others = np.asarray(others, dtype=np.float64)
+        others = np.asarray(others, dtype=ftype)
         oc = np.clip(np.asarray(others_counts).reshape(len(others), -1)[:, 0], 0, others.shape[1])
         for o in range(len(others)):
             if oc[o] == 0:
                 partners.append(None)
                 continue
             ro = np.clip(ri - int(shift_rows), 0, oc[o] - 1)
-            partners.append(pose_polygon(np.asarray(others_foot, dtype=np.float64), others[o, ro, 4], others[o, ro, 6], others[o, ro, 7]))
+            partners.append(pose_polygon(np.asarray(others_foot, dtype=ftype), others[o, ro, 4], others[o, ro, 6], others[o, ro, 7]))
     out = {"status": np.full((B, cap, ns), -1, dtype=np.int64), "face": np.full((B, cap, ns), -1, dtype=np.int64),
-           "element": np.full((B, cap, ns), -2, dtype=np.int64), "t": np.full((B, cap, ns), np.nan),
-           "cos": np.full((B, cap, ns), np.nan), "margin": np.full((B, cap, ns), INF),
+           "element": np.full((B, cap, ns), -2, dtype=np.int64), "t": np.full((B, cap, ns), np.nan, dtype=ftype),
+           "cos": np.full((B, cap, ns), np.nan, dtype=ftype), "margin": np.full((B, cap, ns), INF, dtype=ftype),
            "excused": np.zeros((B, cap, ns), dtype=bool), "live": live, "counts": counts}
     for s in range(ns):
-        r = cast(h, x, y, sensors[s], field, polygons, circles, partners)
+        r = cast(h, x, y, sensors[s], field, polygons, circles, partners, ftype, ambiguous)
         for k, v in r.items():
             out[k][bi, ri, s] = v
     return out

@@ -93,8 +93,10 @@ def own_summaries(code, rng, counts, ns):
     return rr.summaries(ref)
 
 
-def compare(res, ref, tally, what):
-    """Per-reading outputs and summaries of one call against the reference."""
+def compare(res, ref, tally, what, tol=TOL):
+    """Per-reading outputs and summaries of one call against the reference.  tol: TOL, or the tolerance measured for inputs away
+    from the origin (range_cases.translation_tolerance), never below TOL."""
+    assert tol >= TOL
     summ = rr.summaries(ref)
     counts, live, exc = ref["counts"], ref["live"], ref["excused"]
     B, cap, ns = ref["status"].shape
@@ -114,7 +116,7 @@ def compare(res, ref, tally, what):
             assert np.array_equal(np.isnan(got[keep]), np.isnan(want[keep])), (what, name)
             d = np.abs(got - want)
             d = np.where(keep & ~np.isnan(want), d, 0.0)
-            bad = np.argwhere(d > TOL)
+            bad = np.argwhere(d > tol)
             assert not len(bad), (what, name, bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
             if name == "range":
                 tally.worst_t = max(tally.worst_t, float(d.max()) if d.size else 0.0)
@@ -136,13 +138,47 @@ def compare(res, ref, tally, what):
                 if np.isnan(want[0]):
                     assert np.isnan(got_mm[b, s]).all(), (what, b, s)
                 else:
-                    assert np.max(np.abs(got_mm[b, s] - want)) <= TOL, (what, b, s, got_mm[b, s], want)
+                    assert np.max(np.abs(got_mm[b, s] - want)) <= tol, (what, b, s, got_mm[b, s], want)
         if counts[b] == 0:
             assert not got_sc[b].any() and np.isnan(got_mm[b]).all() and (got_ch[b] == [0, -1, -1, 0, -1]).all(), (what, b)
     tally.readings += int(live.sum()) * ns
     tally.excused += int(exc.sum())
     tally.routes += B
     tally.touched += int(touched.any(axis=1).sum())
+    return summ
+
+
+def same_double_bits(got, want):
+    """Two fp64 arrays bit for bit, every NaN one NaN."""
+    got, want = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(want, dtype=np.float64)
+    return np.where(np.isnan(got), -1, got.view(np.int64)) == np.where(np.isnan(want), -1, want.view(np.int64))
+
+
+def compare_exact(res, ref, what):
+    """One call against the reference with nothing excused (the inputs of tests/range_exact_cases.py, where every decision is
+    exact): status, face and element equal and range and cos_incidence the same bits on every reading, and every route's status
+    counts, channels and min / max equal to the reference's (min / max bit for bit).  Returns the summaries."""
+    summ = rr.summaries(ref)
+    counts, live = ref["counts"], ref["live"]
+    B, cap, ns = ref["status"].shape
+    got_sc, got_mm, got_ch = (res[k].cpu().numpy() for k in SUMMARY_KEYS)
+    assert got_sc.shape == (B, ns, 8) and got_mm.shape == (B, ns, 2) and got_ch.shape == (B, ns + 2, 5)
+    if "code" in res:
+        code, rng, cosi = res["code"].cpu().numpy(), res["range"].cpu().numpy(), res["cos_incidence"].cpu().numpy()
+        assert code.shape == (B, cap, ns)
+        past = ~live
+        assert (code[past] == -1).all() and np.isnan(rng[past]).all() and np.isnan(cosi[past]).all(), what
+        st, fa, el = sn().unpack(code)
+        for name, got, want in (("status", st, ref["status"]), ("face", fa, ref["face"]), ("element", el, ref["element"])):
+            bad = np.argwhere(live[:, :, None] & (got != want))
+            assert not len(bad), (what, name, len(bad), bad[0], got[tuple(bad[0])], want[tuple(bad[0])], ref["t"][tuple(bad[0])])
+        for name, got, want in (("range", rng, ref["t"]), ("cos", cosi, ref["cos"])):
+            bad = np.argwhere(live[:, :, None] & ~same_double_bits(got, want))
+            assert not len(bad), (what, name, len(bad), bad[0], float(got[tuple(bad[0])]).hex(), float(want[tuple(bad[0])]).hex())
+    assert np.array_equal(got_sc, summ["status_counts"]), what
+    assert np.array_equal(got_ch, summ["channels"]), what
+    # (+ 0.0: a minimum over -0.0 and +0.0, which compare equal, may be either)
+    assert same_double_bits(got_mm + 0.0, summ["minmax"] + 0.0).all(), what
     return summ
 
 
@@ -193,6 +229,24 @@ def test_random_scenes_against_the_reference(torch_mod):
         assert same_bits(res, run(case, stride=stride), SUMMARY_KEYS + ROW_KEYS), seed
     assert {0, 1, 2, 3, 4} <= seen, seen
     tally.check_caps("random")
+
+
+@pytest.mark.parametrize("d", rc.TRANSLATIONS)
+def test_random_scenes_away_from_the_origin(torch_mod, d):
+    """Two of the random scenes moved d ft along both axes.  The coordinates' own rounding grows with d, so the tolerance is
+    measured, not fixed: max(TOL, 8 D) with D = |float64 reference - long-double reference| on the same doubles, and a reading is
+    excused below a margin of max(1e-9, 2 tol) (range_cases.translation_tolerance); the caps on excused readings and touched
+    routes stay what they are (test_range_cpu.py holds the reference alone to them)."""
+    D, tol, ambiguous = rc.translation_tolerance(rr, d)
+    tally = Tally()
+    for seed in rc.TRANSLATED_SEEDS:
+        case = rc.translated_case(seed, d)
+        ref = rc.reference(rr, case, ambiguous=ambiguous)
+        res = run(case)
+        compare(res, ref, tally, f"random {seed} moved {d:g} ft", tol=tol)
+        assert same_bits(res, run(case, cull=False), SUMMARY_KEYS + ROW_KEYS), (seed, d)
+    print(f"RANGE moved {d:g} ft: D {D:.3e}, tolerance {tol:.3e}, excused below {ambiguous:.3e}")
+    tally.check_caps(f"random moved {d:g} ft")
 
 
 def raw_call(torch, case, out_range, out_cos, out_code, out_sc, out_mm, out_ch, B=None, n_sens=None, sens=None, rows=None, Bo=0,

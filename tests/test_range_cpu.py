@@ -248,3 +248,25 @@ def test_excused_readings_stay_inside_the_cap():
     assert random_exc <= rc.MAX_EXCUSED * random_read
     assert random_touched <= rc.MAX_TOUCHED * random_routes
     assert {0, 1, 2, 3, 4} <= seen, seen
+
+
+
+# ---- random scenes away from the origin: the reference alone stays inside the caps --------------------------------------------
+@pytest.mark.parametrize("d", rc.TRANSLATIONS)
+def test_translated_random_scenes_stay_inside_the_caps(d):
+    """test_gpu_range.py compares two random scenes moved d ft with a measured tolerance max(TOL, 8 D) and excuses a reading below
+    a margin of max(1e-9, 2 tol).  The caps are conditions: with that excuse the reference excuses at most 1 % of the readings
+    and touches at most 10 % of the routes, at each translation."""
+    D, tol, ambiguous = rc.translation_tolerance(rr, d)
+    assert 0.0 < D < 1e-9 and tol >= rc.TOL and ambiguous >= 1e-9
+    n_read = n_exc = n_routes = n_touched = 0
+    for seed in rc.TRANSLATED_SEEDS:
+        ref = rc.reference(rr, rc.translated_case(seed, d), ambiguous=ambiguous)
+        summ = rr.summaries(ref)
+        n_read += int(ref["live"].sum()) * ref["status"].shape[2]
+        n_exc += int(ref["excused"].sum())
+        n_routes += len(ref["counts"])
+        n_touched += int(summ["touched"].any(axis=1).sum())
+    print(f"RANGE moved {d:g} ft: D {D:.3e}, tolerance {tol:.3e}, excused below {ambiguous:.3e}: {n_exc} of {n_read} readings excused, "
+          f"{n_touched} of {n_routes} routes touched")
+    assert n_exc <= rc.MAX_EXCUSED * n_read and n_touched <= rc.MAX_TOUCHED * n_routes
