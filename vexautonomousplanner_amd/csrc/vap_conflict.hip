@@ -33,6 +33,9 @@
 // The exact pair is vap_footprint.hip's polygon clearance (separating axes over the edge normals of both, else the
 // vertex-to-edge distance), evaluated in one footprint's body frame: the other sits at t + R(rel) v, so the frame's own
 // vertices, normals and projection extents are call constants (LDS) and only the other's vertices are transformed.
+//
+// This file defines the pack kernel all three robot-to-robot calls launch (conf_pack_sides, vap_conflict.h) and keeps its
+// own tile walk; the exact pair on two packed rows, the row and block bounds and the argument checks are vap_conflict.h's.
 #include "vap_conflict.h"
 
 namespace vap {
@@ -83,13 +86,9 @@ __global__ __launch_bounds__(256) void k_conflict_pack(ConfSide s, double fcx, d
     }
 }
 
-struct ConfArgs {
-    const double *pack_a, *pack_o, *blk_a, *blk_o;
-    ConfSide a, o;
-    long Tp;
-    int nblk, nto;            // blocks per route; O tiles per A route (1 when matched)
-    double margin, slack;     // slack: kCullSlack * (1 + R_a + R_o)
-    int cull;
+struct ConfArgs : ConfPacked {    // both sides are packed to one horizon: Tpa == Tpo, nblk_a == nblk_o
+    int nto;                  // O tiles per A route (1 when matched)
+    double margin;
     double *pair_c;           // [Ba][P], optional
     int *pair_row, *pair_first;
     double *part_c;           // [Ba][nto] per-tile partials: min clearance (+inf: no valid pair) ...
@@ -127,7 +126,7 @@ __global__ __launch_bounds__(kConfThreads) void k_conflict_pairs(ConfFoot fa, Co
     const int nchunk = (s_T + kConfBlock - 1) / kConfBlock;  // the tile's horizon; rows past a pair's own T are not examined
     const int na = fa.n, no = fo.n;
     const double radii = fa.R + fo.R;
-    const double *pa = g.pack_a + (size_t)ia * (size_t)g.Tp * 4, *po = g.pack_o + (size_t)io * (size_t)g.Tp * 4;
+    const double *pa = g.pack_a + (size_t)ia * (size_t)g.Tpa * 4, *po = g.pack_o + (size_t)io * (size_t)g.Tpa * 4;
 
     double best = INFINITY;
     int brow = INT_MAX, first = INT_MAX;
@@ -146,7 +145,7 @@ __global__ __launch_bounds__(kConfThreads) void k_conflict_pairs(ConfFoot fa, Co
         int kn = 0;
 #pragma unroll 1
         for (int k = 0; k < nb; k++) {
-            const double *qa = g.blk_a + ((size_t)ia * g.nblk + k) * 4, *qo = g.blk_o + ((size_t)io * g.nblk + k) * 4;
+            const double *qa = g.blk_a + ((size_t)ia * g.nblk_a + k) * 4, *qo = g.blk_o + ((size_t)io * g.nblk_a + k) * 4;
             const double dx = qo[0] - qa[0], dy = qo[1] - qa[1];
             const double d = sqrt(dx * dx + dy * dy) - qa[2] - qo[2];
             if (d < near) { near = d; kn = k; }
@@ -154,9 +153,7 @@ __global__ __launch_bounds__(kConfThreads) void k_conflict_pairs(ConfFoot fa, Co
 #pragma unroll 1
         for (int i = 0; i < 4; i++) {
             const int r = min(kn * kConfBlock + i * 21, T - 1);
-            const double2 a01 = *(const double2 *)(pa + (size_t)r * 4), a23 = *(const double2 *)(pa + (size_t)r * 4 + 2);
-            const double2 o01 = *(const double2 *)(po + (size_t)r * 4), o23 = *(const double2 *)(po + (size_t)r * 4 + 2);
-            take(pair_clearance(sfa, na, sfo, no, a01.x, a01.y, a23.x, a23.y, o01.x, o01.y, o23.x, o23.y), r);
+            take(pair_at(sfa, na, sfo, no, pa + (size_t)r * 4, po + (size_t)r * 4), r);
         }
     }
 #pragma unroll 1
@@ -164,11 +161,9 @@ __global__ __launch_bounds__(kConfThreads) void k_conflict_pairs(ConfFoot fa, Co
         const int r0 = k * kConfBlock;
         bool need = valid && r0 < T;
         if (need && g.cull) {
-            const double *qa = g.blk_a + ((size_t)ia * g.nblk + k) * 4, *qo = g.blk_o + ((size_t)io * g.nblk + k) * 4;
-            const double ax = qa[0], ay = qa[1], ox = qo[0], oy = qo[1];
+            const double *qa = g.blk_a + ((size_t)ia * g.nblk_a + k) * 4, *qo = g.blk_o + ((size_t)io * g.nblk_a + k) * 4;
             const double thresh = first < r0 ? best : fmax(best, g.margin);
-            const double slack = g.slack + kCullSlack * (fabs(ax) + fabs(ay) + fabs(ox) + fabs(oy) + qa[2] + qo[2]);
-            need = !conf_culled(thresh + slack + radii + qa[2] + qo[2], ox - ax, oy - ay);
+            need = !block_culled(g, radii, thresh, qa[0], qa[1], qa[2], qo[0], qo[1], qo[2]);
         }
         if (!MATCHED) {
             if (!__syncthreads_or(need)) continue;           // also: every thread has left the previous chunk's rows
@@ -180,7 +175,7 @@ __global__ __launch_bounds__(kConfThreads) void k_conflict_pairs(ConfFoot fa, Co
                 const bool side_o = route >= kConfTile;
                 const int idx = side_o ? to * kConfTile + (route - kConfTile) : ta * kConfTile + route;
                 if (idx < (side_o ? g.o.B : g.a.B)) {
-                    const double *src = (side_o ? g.pack_o : g.pack_a) + ((size_t)idx * (size_t)g.Tp + (size_t)r0) * 4;
+                    const double *src = (side_o ? g.pack_o : g.pack_a) + ((size_t)idx * (size_t)g.Tpa + (size_t)r0) * 4;
                     *(double2 *)(stage + route * kConfRouteStride + piece * 2) = *(const double2 *)(src + piece * 2);
                 }
             }
@@ -201,8 +196,8 @@ __global__ __launch_bounds__(kConfThreads) void k_conflict_pairs(ConfFoot fa, Co
             const double *rla, *rlo;
             if (MATCHED) {
                 const size_t route = (size_t)blockIdx.x * kConfThreads + (tid - lane) + l;
-                rla = g.pack_a + (route * (size_t)g.Tp + (size_t)r0) * 4;
-                rlo = g.pack_o + (route * (size_t)g.Tp + (size_t)r0) * 4;
+                rla = g.pack_a + (route * (size_t)g.Tpa + (size_t)r0) * 4;
+                rlo = g.pack_o + (route * (size_t)g.Tpa + (size_t)r0) * 4;
             } else {
                 const int pair = (tid - lane) + l;
                 rla = stage + (pair / kConfTile) * kConfRouteStride;
@@ -211,11 +206,9 @@ __global__ __launch_bounds__(kConfThreads) void k_conflict_pairs(ConfFoot fa, Co
             double v = INFINITY;
             int vr = INT_MAX, vf = INT_MAX;
             if (r0 + lane < T_l) {
-                const double2 a01 = *(const double2 *)(rla + lane * 4), a23 = *(const double2 *)(rla + lane * 4 + 2);
-                const double2 o01 = *(const double2 *)(rlo + lane * 4), o23 = *(const double2 *)(rlo + lane * 4 + 2);
-                const double slack = g.slack + kCullSlack * (fabs(a01.x) + fabs(a01.y) + fabs(o01.x) + fabs(o01.y));
-                if (!g.cull || !conf_culled(th + slack + radii, o01.x - a01.x, o01.y - a01.y)) {
-                    const double c = pair_clearance(sfa, na, sfo, no, a01.x, a01.y, a23.x, a23.y, o01.x, o01.y, o23.x, o23.y);
+                const double2 a01 = *(const double2 *)(rla + lane * 4), o01 = *(const double2 *)(rlo + lane * 4);
+                if (!g.cull || !row_culled(g, radii, th, a01.x, a01.y, o01.x, o01.y)) {
+                    const double c = pair_at(sfa, na, sfo, no, rla + lane * 4, rlo + lane * 4);
                     if (c == c) {                            // a NaN clearance takes part in nothing
                         v = c;
                         vr = r0 + lane;
@@ -306,68 +299,40 @@ int vap_footprint_conflicts(vap_ctx *ctx, int pairing, int shift_rows, double ma
                             double *d_min_clearance, int *d_min_other, int *d_min_row, int *d_n_conflicts, int *d_first_row)
 {
     using namespace vap;
+    const ConfInput a{Ba, cap_a, d_rows_a, d_counts_a, stride_a, n_foot_a, h_foot_a}, o{Bo, cap_o, d_rows_o, d_counts_o, stride_o, n_foot_o, h_foot_o};
+    const bool matched = pairing == VAP_CONFLICT_MATCHED;
     VAP_TRY(vap_set_device(ctx));
-    if (pairing != VAP_CONFLICT_ALL_PAIRS && pairing != VAP_CONFLICT_MATCHED) return vap_fail(VAP_ERR_INVALID, "unknown pairing %d", pairing);
-    if (Ba < 0 || Bo < 0 || cap_a < 0 || cap_o < 0)
-        return vap_fail(VAP_ERR_INVALID, "bad shape Ba=%d cap_a=%ld Bo=%d cap_o=%ld", Ba, cap_a, Bo, cap_o);
+    if (pairing != VAP_CONFLICT_ALL_PAIRS && !matched) return vap_fail(VAP_ERR_INVALID, "unknown pairing %d", pairing);
+    VAP_TRY(conf_check_shape("Ba", a, o));
     if (cap_a > INT_MAX || cap_o > INT_MAX)
         return vap_fail(VAP_ERR_UNSUPPORTED, "capacity %ld above %d rows", cap_a > cap_o ? cap_a : cap_o, INT_MAX);
-    if (stride_a < 1 || stride_o < 1) return vap_fail(VAP_ERR_INVALID, "count strides must be >= 1 (got %d, %d)", stride_a, stride_o);
-    if (pairing == VAP_CONFLICT_MATCHED && Ba != Bo) return vap_fail(VAP_ERR_INVALID, "matched pairing needs Ba == Bo (got %d, %d)", Ba, Bo);
-    if ((Ba > 0 && (!d_counts_a || (cap_a > 0 && !d_rows_a))) || (Bo > 0 && (!d_counts_o || (cap_o > 0 && !d_rows_o))))
-        return vap_fail(VAP_ERR_INVALID, "null rows / counts");
-    if (!std::isfinite(margin)) return vap_fail(VAP_ERR_INVALID, "margin must be finite");
-    if (!h_foot_a || !h_foot_o) return vap_fail(VAP_ERR_INVALID, "null footprint");
-    VAP_TRY(check_convex(h_foot_a, n_foot_a, "footprint", 0));
-    VAP_TRY(check_convex(h_foot_o, n_foot_o, "footprint", 1));
+    VAP_TRY(conf_check_sides(a, o, Bo, matched, margin, false, "null rows / counts"));
     if (Ba == 0 || Bo == 0) return VAP_OK;
 
     // the horizon every pair fits in: T = max(n_a, n_o + shift, 1) <= max(cap_a, cap_o + shift, 1)
     long Tcap = cap_a > cap_o + (long)shift_rows ? cap_a : cap_o + (long)shift_rows;
     Tcap = Tcap < 1 ? 1 : Tcap;
-    const long nblk_l = (Tcap + kConfBlock - 1) / kConfBlock, Tp = nblk_l * kConfBlock;
-    if (Tp > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "horizon of %ld rows above %d", Tcap, INT_MAX);
-    const int nblk = (int)nblk_l, groups = (nblk + 3) / 4;
-    const bool matched = pairing == VAP_CONFLICT_MATCHED;
+    const ConfHorizon h = conf_horizon(Tcap);
+    if (h.Tp > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "horizon of %ld rows above %d", Tcap, INT_MAX);
     const long nta = (Ba + kConfTile - 1) / kConfTile, nto = matched ? 1 : (Bo + kConfTile - 1) / kConfTile;
     const long grid_pairs = matched ? (Ba + kConfThreads - 1) / kConfThreads : nta * nto;
-    const long grid_pack = (long)(Ba > Bo ? Ba : Bo) * groups;
+    const long grid_pack = (long)(Ba > Bo ? Ba : Bo) * h.groups;
     if (grid_pairs > INT_MAX || grid_pack > INT_MAX)
         return vap_fail(VAP_ERR_UNSUPPORTED, "%d x %d routes over %ld rows: too many workgroups for one launch", Ba, Bo, Tcap);
 
-    VAP_TRY(ctx->ensure(ctx->conf_pack_a, (size_t)Ba * (size_t)Tp * 32));
-    VAP_TRY(ctx->ensure(ctx->conf_pack_o, (size_t)Bo * (size_t)Tp * 32));
-    VAP_TRY(ctx->ensure(ctx->conf_blk_a, (size_t)Ba * (size_t)nblk * 32));
-    VAP_TRY(ctx->ensure(ctx->conf_blk_o, (size_t)Bo * (size_t)nblk * 32));
+    ConfFoot fa, fo;
+    ConfArgs g;
+    VAP_TRY(conf_pack_sides(ctx, a, o, shift_rows, h, h, fa, fo, g));
     const size_t n_part = (size_t)Ba * (size_t)nto;
     VAP_TRY(ctx->ensure(ctx->conf_part, n_part * (sizeof(double) + 4 * sizeof(int))));
-
-    ConfFoot fa, fo;
-    conf_foot(h_foot_a, n_foot_a, fa);
-    conf_foot(h_foot_o, n_foot_o, fo);
-    ConfArgs g;
-    g.a = ConfSide{d_rows_a, d_counts_a, cap_a, stride_a, Ba, 0};
-    g.o = ConfSide{d_rows_o, d_counts_o, cap_o, stride_o, Bo, (long)shift_rows};
-    g.pack_a = (const double *)ctx->conf_pack_a.ptr;
-    g.pack_o = (const double *)ctx->conf_pack_o.ptr;
-    g.blk_a = (const double *)ctx->conf_blk_a.ptr;
-    g.blk_o = (const double *)ctx->conf_blk_o.ptr;
-    g.Tp = Tp;
-    g.nblk = nblk;
     g.nto = (int)nto;
     g.margin = margin;
-    g.slack = kCullSlack * (1.0 + fa.R + fo.R);
-    g.cull = ctx->footprint_cull;
     g.pair_c = d_pair_clearance;
     g.pair_row = d_pair_row;
     g.pair_first = d_pair_first_row;
     g.part_c = (double *)ctx->conf_part.ptr;
     g.part_i = (int *)(g.part_c + n_part);
 
-    hipLaunchKernelGGL(k_conflict_pack, dim3((unsigned)(Ba * (long)groups)), dim3(256), 0, ctx->stream, g.a, fa.cx, fa.cy, Tp, nblk,
-                       groups, (double *)ctx->conf_pack_a.ptr, (double *)ctx->conf_blk_a.ptr);
-    hipLaunchKernelGGL(k_conflict_pack, dim3((unsigned)(Bo * (long)groups)), dim3(256), 0, ctx->stream, g.o, fo.cx, fo.cy, Tp, nblk,
-                       groups, (double *)ctx->conf_pack_o.ptr, (double *)ctx->conf_blk_o.ptr);
     if (matched)
         hipLaunchKernelGGL(k_conflict_pairs<true>, dim3((unsigned)grid_pairs), dim3(kConfThreads), 0, ctx->stream, fa, fo, g);
     else

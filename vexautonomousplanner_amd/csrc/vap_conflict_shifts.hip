@@ -32,81 +32,39 @@
 //
 // Scratch: the two packs, (Ba capP_a + Bo capP_o) x 32 B plus their block circles, and Ba (P + 1) ceil(n_shifts / 64)
 // words of blocked bits.  Nothing grows with pairs x blocks x shifts.
-#include "vap_conflict.h"
+//
+// Kept here: the [tb, te) interval, the two runs of blocks, the seeds, the blocked bits, the finalise kernel.  The stage,
+// the block test and the survivor queue are vap_band_sweep.h's; the row bound, the checks and the packing vap_conflict.h's.
+#include "vap_band_sweep.h"
 
 namespace vap {
 
-constexpr int kShiftLanes = 64;                  // one wave: a lane per shift of the band
-constexpr long kShiftStageRows = 1024;           // O rows staged at most (32 KB); the band halves until it fits
-constexpr int kShiftQueue = 128;                 // ring of queued (instant, shift) survivors
 // k_shift_sweep's static LDS: two footprints, the A block, the keys, the queue.  The staged O band follows it as dynamic
 // LDS and is read 16 bytes at a time, so the static part must stay a multiple of 16.
-constexpr size_t kShiftStaticLds = 2 * kFootMaxVerts * 8 * 8 + kConfBlock * 32 + kShiftLanes * 8 + kShiftQueue * 2;
+constexpr size_t kShiftStaticLds = 2 * kFootMaxVerts * 8 * 8 + kConfBlock * 32 + kSweepLanes * 8 + kSweepQueue * 2;
 static_assert(kShiftStaticLds % 16 == 0, "the dynamic LDS behind k_shift_sweep's statics must start 16-byte aligned");
 
-struct ShiftArgs {
-    const double *pack_a, *pack_o, *blk_a, *blk_o;
-    ConfSide a, o;
-    long Tpa, Tpo;            // packed rows per route
-    int nblk_a, nblk_o;
-    int matched, P, hold, cull;
+struct ShiftArgs : ConfPacked {
+    int matched, P, hold;
     long shift_lo;
     int step, n_shifts;
     const int *base;          // [Ba] or null
     int band, nbands, nwords; // shifts per workgroup (a power of two <= 64), bands per route, bit words per window
-    double margin, slack;
+    double margin;
     double *table, *route_table;
     unsigned long long *pair_bits, *route_bits;   // null: not needed
 };
 
-__device__ __forceinline__ long floordiv64(long x) { return x >= 0 ? x / 64 : -((63 - x) / 64); }
-__device__ __forceinline__ long clampl(long x, long lo, long hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
-// an order-preserving map of doubles (no NaN) to unsigned 64-bit keys, and back
-__device__ __forceinline__ unsigned long long shift_key(double v)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double shift_unkey(unsigned long long k)
-{
-    return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_min(T v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const T o = __shfl_xor(v, off);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ T wave_max(T v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const T o = __shfl_xor(v, off);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-__global__ __launch_bounds__(kShiftLanes) void k_shift_sweep(ConfFoot fa, ConfFoot fo, ShiftArgs g)
+__global__ __launch_bounds__(kSweepLanes) void k_shift_sweep(ConfFoot fa, ConfFoot fo, ShiftArgs g)
 {
     __shared__ double sfa[kFootMaxVerts * 8], sfo[kFootMaxVerts * 8];
     __shared__ __attribute__((aligned(16))) double stage_a[kConfBlock * 4];
-    __shared__ unsigned long long s_key[kShiftLanes];
-    __shared__ unsigned short s_queue[kShiftQueue];
+    __shared__ unsigned long long s_key[kSweepLanes];
+    __shared__ unsigned short s_queue[kSweepQueue];
     extern __shared__ __attribute__((aligned(16))) double stage_o[];     // [64 + (band - 1) step][4]
 
     const int lane = threadIdx.x;
-    sfa[lane] = fa.v[lane];
-    sfa[lane + 64] = fa.v[lane + 64];
-    sfo[lane] = fo.v[lane];
-    sfo[lane + 64] = fo.v[lane + 64];
+    sweep_load_feet(sfa, sfo, fa, fo, lane);
     const int ia = blockIdx.x / g.nbands, gi = blockIdx.x % g.nbands;
     const int k0 = gi * g.band, k = k0 + lane;
     const int nb = min(g.band, g.n_shifts - k0);             // live lanes of this band
@@ -150,15 +108,16 @@ __global__ __launch_bounds__(kShiftLanes) void k_shift_sweep(ConfFoot fa, ConfFo
 #pragma unroll 1
             for (int q = 0; q < 4; q++) {
                 const long t = tb + ((te - tb) * (2 * q + 1)) / 8;
-                const double *ra = pa + (size_t)clampl(t, 0, n_a - 1) * 4, *ro = po + (size_t)clampl(t - s, 0, n_o - 1) * 4;
-                const double2 a01 = *(const double2 *)ra, a23 = *(const double2 *)(ra + 2);
-                const double2 o01 = *(const double2 *)ro, o23 = *(const double2 *)(ro + 2);
-                const double c = pair_clearance(sfa, na, sfo, no, a01.x, a01.y, a23.x, a23.y, o01.x, o01.y, o23.x, o23.y);
+                const double c = pair_at(sfa, na, sfo, no, pa + (size_t)clampl(t, 0, n_a - 1) * 4, po + (size_t)clampl(t - s, 0, n_o - 1) * 4);
                 if (c < best) best = c;
             }
         }
-        s_key[lane] = shift_key(best);
-        int qn = 0, head = 0;                                // the queue's fill and first entry (uniform)
+        s_key[lane] = conf_key(best);
+        SweepQueue queue{sfa, sfo, stage_a, stage_o, s_queue, na, no, lane};
+        // entry (tt, l): lane l's O row of instant tt sits at stage slot tt + (nb - 1 - l) step; the lane's own minimum
+        const auto slot_of = [&](int tt, int l) { return tt + (nb - 1 - l) * g.step; };
+        const auto key_of = [&](int, int l) { return &s_key[l]; };
+        const auto own_min = [&]() { return conf_unkey(s_key[lane]); };
 
         // up to two runs of 64-instant blocks: A's own rows and the O band's own rows, inside what any lane examines
         long seg[2][2];
@@ -193,76 +152,26 @@ __global__ __launch_bounds__(kShiftLanes) void k_shift_sweep(ConfFoot fa, ConfFo
                     // A's block circle against every O block the band's rows of this block lie in
                     const double thr = wave_max(mine ? best : -INFINITY);
                     const double *qa = qa_all + (size_t)clampl(m, 0, g.nblk_a - 1) * 4;
-                    const double ax = qa[0], ay = qa[1], ar = qa[2];
                     const long b0 = clampl(floordiv64(t0 - s_hi), 0, g.nblk_o - 1), b1 = clampl(floordiv64(t0 + kConfBlock - 1 - s_lo), 0, g.nblk_o - 1);
-                    bool need = false;
-#pragma unroll 1
-                    for (long b = b0 + lane; b <= b1; b += kShiftLanes) {
-                        const double *qo = qo_all + (size_t)b * 4;
-                        const double ox = qo[0], oy = qo[1];
-                        const double slack = g.slack + kCullSlack * (fabs(ax) + fabs(ay) + fabs(ox) + fabs(oy) + ar + qo[2]);
-                        need = need || !conf_culled(thr + slack + radii + ar + qo[2], ox - ax, oy - ay);
-                    }
-                    if (!__any(need)) continue;
+                    if (!band_needs_block(g, radii, thr, qa, qo_all, b0, b1, lane)) continue;
                 }
-                // stage: every lane has left the previous block's rows (a flush ends with a barrier)
-                {
-                    const double *src = pa + (size_t)clampl(t0 + lane, 0, n_a - 1) * 4;
-                    *(double2 *)(stage_a + lane * 4) = *(const double2 *)src;
-                    *(double2 *)(stage_a + lane * 4 + 2) = *(const double2 *)(src + 2);
-                }
-#pragma unroll 1
-                for (int q = lane; q < nq; q += kShiftLanes) {
-                    const double *src = po + (size_t)clampl(t0 - s_hi + q, 0, n_o - 1) * 4;
-                    *(double2 *)(stage_o + (size_t)q * 4) = *(const double2 *)src;
-                    *(double2 *)(stage_o + (size_t)q * 4 + 2) = *(const double2 *)(src + 2);
-                }
+                sweep_stage(stage_a, pa, t0, n_a, stage_o, po, t0 - s_hi, n_o, nq, lane);
                 __syncthreads();
-                // the exact pair of `n` queued survivors, a lane each; afterwards every lane's running minimum is current
-                auto flush = [&](int n) {
-                    __syncthreads();
-                    if (lane < n) {
-                        const int e = s_queue[(head + lane) & (kShiftQueue - 1)];
-                        const int tt = e & 63, l = e >> 6;
-                        const double *ra = stage_a + tt * 4, *ro = stage_o + (size_t)(tt + (nb - 1 - l) * g.step) * 4;
-                        const double2 a01 = *(const double2 *)ra, a23 = *(const double2 *)(ra + 2);
-                        const double2 o01 = *(const double2 *)ro, o23 = *(const double2 *)(ro + 2);
-                        const double c = pair_clearance(sfa, na, sfo, no, a01.x, a01.y, a23.x, a23.y, o01.x, o01.y, o23.x, o23.y);
-                        if (c == c) atomicMin(&s_key[l], shift_key(c));      // a NaN clearance takes part in nothing
-                    }
-                    __syncthreads();
-                    best = shift_unkey(s_key[lane]);
-                };
 #pragma unroll 1
                 for (int tt = lo_u; tt < hi_u; tt++) {
                     bool cand = tt >= lo_l && tt < hi_l;
                     if (cand && g.cull) {
                         const double2 a01 = *(const double2 *)(stage_a + tt * 4);
                         const double2 o01 = *(const double2 *)(stage_o + (size_t)(tt + off_o) * 4);
-                        const double slack = g.slack + kCullSlack * (fabs(a01.x) + fabs(a01.y) + fabs(o01.x) + fabs(o01.y));
-                        cand = !conf_culled(best + slack + radii, o01.x - a01.x, o01.y - a01.y);
+                        cand = !row_culled(g, radii, best, a01.x, a01.y, o01.x, o01.y);
                     }
-                    const unsigned long long mask = __ballot(cand);
-                    if (mask) {
-                        if (cand) {
-                            const int pos = head + qn + __popcll(mask & ((1ull << lane) - 1ull));
-                            s_queue[pos & (kShiftQueue - 1)] = (unsigned short)(tt | (lane << 6));
-                        }
-                        qn += __popcll(mask);
-                        if (qn >= kShiftLanes) {
-                            flush(kShiftLanes);
-                            head = (head + kShiftLanes) & (kShiftQueue - 1);
-                            qn -= kShiftLanes;
-                        }
-                    }
+                    queue.push(cand, tt, best, slot_of, key_of, own_min);
                 }
-                flush(qn);                                   // the rows leave LDS with this block; also the barrier
-                head = 0;
-                qn = 0;
+                queue.close(best, slot_of, key_of, own_min);
             }
         }
         __syncthreads();
-        best = shift_unkey(s_key[lane]);
+        best = conf_unkey(s_key[lane]);
         __syncthreads();                                     // s_key is rewritten for the next pair
         const bool have = some && best != INFINITY;          // a finite clearance was examined
         const bool blocked = have && best < g.margin;
@@ -341,21 +250,15 @@ int vap_conflict_shifts(vap_ctx *ctx, int pairing, int hold, double margin, int 
                         double *d_route_table, int *d_route_first, int *d_route_safe)
 {
     using namespace vap;
-    if (pairing != VAP_CONFLICT_ALL_PAIRS && pairing != VAP_CONFLICT_MATCHED) return vap_fail(VAP_ERR_INVALID, "unknown pairing %d", pairing);
+    const ConfInput a{Ba, cap_a, d_rows_a, d_counts_a, stride_a, n_foot_a, h_foot_a}, o{Bo, cap_o, d_rows_o, d_counts_o, stride_o, n_foot_o, h_foot_o};
+    const bool matched = pairing == VAP_CONFLICT_MATCHED;
+    if (pairing != VAP_CONFLICT_ALL_PAIRS && !matched) return vap_fail(VAP_ERR_INVALID, "unknown pairing %d", pairing);
     if (hold < 0 || hold > 15) return vap_fail(VAP_ERR_INVALID, "hold must be a mask of the four VAP_HOLD bits (got %d)", hold);
     if (n_shifts < 1 || shift_step < 1 || min_run < 1)
         return vap_fail(VAP_ERR_INVALID, "n_shifts, shift_step and min_run must be >= 1 (got %d, %d, %d)", n_shifts, shift_step, min_run);
     if (scan != 1 && scan != -1) return vap_fail(VAP_ERR_INVALID, "scan must be +1 or -1 (got %d)", scan);
-    if (Ba < 0 || Bo < 0 || cap_a < 0 || cap_o < 0)
-        return vap_fail(VAP_ERR_INVALID, "bad shape Ba=%d cap_a=%ld Bo=%d cap_o=%ld", Ba, cap_a, Bo, cap_o);
-    if (stride_a < 1 || stride_o < 1) return vap_fail(VAP_ERR_INVALID, "count strides must be >= 1 (got %d, %d)", stride_a, stride_o);
-    if (pairing == VAP_CONFLICT_MATCHED && Ba != Bo) return vap_fail(VAP_ERR_INVALID, "matched pairing needs Ba == Bo (got %d, %d)", Ba, Bo);
-    if ((Ba > 0 && (!d_counts_a || (cap_a > 0 && !d_rows_a))) || (Bo > 0 && (!d_counts_o || (cap_o > 0 && !d_rows_o))))
-        return vap_fail(VAP_ERR_INVALID, "null rows / counts");
-    if (!std::isfinite(margin)) return vap_fail(VAP_ERR_INVALID, "margin must be finite");
-    if (!h_foot_a || !h_foot_o) return vap_fail(VAP_ERR_INVALID, "null footprint");
-    VAP_TRY(check_convex(h_foot_a, n_foot_a, "footprint", 0));
-    VAP_TRY(check_convex(h_foot_o, n_foot_o, "footprint", 1));
+    VAP_TRY(conf_check_shape("Ba", a, o));
+    VAP_TRY(conf_check_sides(a, o, Bo, matched, margin, false, "null rows / counts"));
     if (n_shifts > VAP_CONFLICT_SHIFTS_MAX)
         return vap_fail(VAP_ERR_UNSUPPORTED, "%d shifts above VAP_CONFLICT_SHIFTS_MAX = %d", n_shifts, VAP_CONFLICT_SHIFTS_MAX);
     if (cap_a > INT_MAX || cap_o > INT_MAX)
@@ -364,75 +267,41 @@ int vap_conflict_shifts(vap_ctx *ctx, int pairing, int hold, double margin, int 
     if (Ba == 0 || Bo == 0) return VAP_OK;
     if (!d_table && !d_pair_first && !d_pair_safe && !d_route_table && !d_route_first && !d_route_safe) return VAP_OK;
 
-    const bool matched = pairing == VAP_CONFLICT_MATCHED;
-    const long nblk_a = cap_a > 0 ? (cap_a + kConfBlock - 1) / kConfBlock : 1, nblk_o = cap_o > 0 ? (cap_o + kConfBlock - 1) / kConfBlock : 1;
-    const long Tpa = nblk_a * kConfBlock, Tpo = nblk_o * kConfBlock;
-    const int groups_a = (int)((nblk_a + 3) / 4), groups_o = (int)((nblk_o + 3) / 4);
-    // the band: the most shifts, a power of two, whose O rows fit the stage
-    int band = kShiftLanes;
-    while (band > 1 && kConfBlock + (long)(band - 1) * shift_step > kShiftStageRows) band /= 2;
-    const int nbands = (n_shifts + band - 1) / band, nwords = (n_shifts + 63) / 64;
-    const int nb_max = band < n_shifts ? band : n_shifts;
-    const size_t lds = (size_t)(kConfBlock + (long)(nb_max - 1) * shift_step) * 32;
-    int lds_max = 0;
-    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess) lds_max = 0;
-    const size_t avail = lds_max > 0 && lds_max < 64 * 1024 ? (size_t)lds_max : (size_t)64 * 1024;
-    if (lds + kShiftStaticLds > avail)
-        return vap_fail(VAP_ERR_UNSUPPORTED, "a band of %d shifts at step %d needs %zu bytes of LDS; the device gives a workgroup %zu",
-                        band, shift_step, lds + kShiftStaticLds, avail);
-    const long grid = (long)Ba * nbands, grid_pack = (long)Ba * groups_a > (long)Bo * groups_o ? (long)Ba * groups_a : (long)Bo * groups_o;
+    const ConfHorizon ha = conf_horizon(cap_a), ho = conf_horizon(cap_o);
+    const SweepBands bands = sweep_bands(n_shifts, shift_step, 0);
+    VAP_TRY(sweep_fits(ctx, bands, shift_step, kShiftStaticLds, "shifts"));
+    const int nwords = (n_shifts + 63) / 64;
+    const long grid = (long)Ba * bands.nbands, grid_pack = (long)Ba * ha.groups > (long)Bo * ho.groups ? (long)Ba * ha.groups : (long)Bo * ho.groups;
     const size_t P = matched ? 1 : (size_t)Bo, n_fin = (size_t)Ba * P + (size_t)Ba;
     if (grid > INT_MAX || grid_pack > INT_MAX || (n_fin + 63) / 64 > (size_t)INT_MAX)
         return vap_fail(VAP_ERR_UNSUPPORTED, "%d x %d routes, %d shifts: too many workgroups for one launch", Ba, Bo, n_shifts);
 
-    VAP_TRY(ctx->ensure(ctx->conf_pack_a, (size_t)Ba * (size_t)Tpa * 32));
-    VAP_TRY(ctx->ensure(ctx->conf_pack_o, (size_t)Bo * (size_t)Tpo * 32));
-    VAP_TRY(ctx->ensure(ctx->conf_blk_a, (size_t)Ba * (size_t)nblk_a * 32));
-    VAP_TRY(ctx->ensure(ctx->conf_blk_o, (size_t)Bo * (size_t)nblk_o * 32));
+    ConfFoot fa, fo;
+    ShiftArgs g;
+    VAP_TRY(conf_pack_sides(ctx, a, o, 0, ha, ho, fa, fo, g));
     const bool want_pair = d_pair_first || d_pair_safe, want_route = d_route_first || d_route_safe;
     const size_t pair_words = want_pair ? (size_t)Ba * P * (size_t)nwords : 0, route_words = want_route ? (size_t)Ba * (size_t)nwords : 0;
     if (pair_words + route_words) {
         VAP_TRY(ctx->ensure(ctx->conf_part, (pair_words + route_words) * 8));
         HIP_TRY(hipMemsetAsync(ctx->conf_part.ptr, 0, (pair_words + route_words) * 8, ctx->stream));
     }
-
-    ConfFoot fa, fo;
-    conf_foot(h_foot_a, n_foot_a, fa);
-    conf_foot(h_foot_o, n_foot_o, fo);
-    ShiftArgs g;
-    g.a = ConfSide{d_rows_a, d_counts_a, cap_a, stride_a, Ba, 0};
-    g.o = ConfSide{d_rows_o, d_counts_o, cap_o, stride_o, Bo, 0};
-    g.pack_a = (const double *)ctx->conf_pack_a.ptr;
-    g.pack_o = (const double *)ctx->conf_pack_o.ptr;
-    g.blk_a = (const double *)ctx->conf_blk_a.ptr;
-    g.blk_o = (const double *)ctx->conf_blk_o.ptr;
-    g.Tpa = Tpa;
-    g.Tpo = Tpo;
-    g.nblk_a = (int)nblk_a;
-    g.nblk_o = (int)nblk_o;
     g.matched = matched ? 1 : 0;
     g.P = (int)P;
     g.hold = hold;
-    g.cull = ctx->footprint_cull;
     g.shift_lo = shift_lo;
     g.step = shift_step;
     g.n_shifts = n_shifts;
     g.base = d_shift_base;
-    g.band = band;
-    g.nbands = nbands;
+    g.band = bands.band;
+    g.nbands = bands.nbands;
     g.nwords = nwords;
     g.margin = margin;
-    g.slack = kCullSlack * (1.0 + fa.R + fo.R);
     g.table = d_table;
     g.route_table = d_route_table;
     g.pair_bits = want_pair ? (unsigned long long *)ctx->conf_part.ptr : nullptr;
     g.route_bits = want_route ? (unsigned long long *)ctx->conf_part.ptr + pair_words : nullptr;
 
-    hipLaunchKernelGGL(k_conflict_pack, dim3((unsigned)((long)Ba * groups_a)), dim3(256), 0, ctx->stream, g.a, fa.cx, fa.cy, Tpa,
-                       (int)nblk_a, groups_a, (double *)ctx->conf_pack_a.ptr, (double *)ctx->conf_blk_a.ptr);
-    hipLaunchKernelGGL(k_conflict_pack, dim3((unsigned)((long)Bo * groups_o)), dim3(256), 0, ctx->stream, g.o, fo.cx, fo.cy, Tpo,
-                       (int)nblk_o, groups_o, (double *)ctx->conf_pack_o.ptr, (double *)ctx->conf_blk_o.ptr);
-    hipLaunchKernelGGL(k_shift_sweep, dim3((unsigned)grid), dim3(kShiftLanes), lds, ctx->stream, fa, fo, g);
+    hipLaunchKernelGGL(k_shift_sweep, dim3((unsigned)grid), dim3(kSweepLanes), bands.lds, ctx->stream, fa, fo, g);
     if (want_pair || want_route)
         hipLaunchKernelGGL(k_shift_finalise, dim3((unsigned)((n_fin + 63) / 64)), dim3(64), 0, ctx->stream, g, min_run, scan, d_pair_first,
                            d_pair_safe, d_route_first, d_route_safe);

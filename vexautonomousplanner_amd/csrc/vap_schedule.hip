@@ -30,86 +30,41 @@
 // stay in LDS, bit-packed (M C / 4 bytes), for the backtrack, which is a handful of ballots per slot.
 //
 // Scratch: the two packs and their block circles.  Nothing grows with R x M x C beside the caller's two tables.
-#include "vap_conflict.h"
+//
+// Kept here: the slot map, the per-segment keys and seeds, the parked tail, the hold poses, the solve.  The stage, the
+// block test and the survivor queue are vap_band_sweep.h's; the row bound, the checks and the packing vap_conflict.h's.
+#include "vap_band_sweep.h"
 
 namespace vap {
 
-constexpr int kSchedLanes = 64;                  // one wave: a lane per delay of the band
-constexpr long kSchedStageRows = 1024;           // partner rows staged at most (32 KB); the band halves until it fits
-constexpr int kSchedQueue = 128;                 // ring of queued (row, delay) survivors
+// k_schedule_sweep's static LDS: two footprints, the A block, the tail's suffix minima, the slot map, the queue, the rows'
+// segments.  The keys and the staged partner band follow it as dynamic LDS, read 16 bytes at a time.
+constexpr size_t kSchedStaticLds =
+    (2 * kFootMaxVerts * 8 * 8 + kConfBlock * 32 + kSweepLanes * 8 + (VAP_TIMELINE_MAX_LEGS + 1) * 4 + kSweepQueue * 2 + kConfBlock + 15) / 16 * 16;
 
-struct SchedArgs {
-    const double *pack_a, *pack_o, *blk_a, *blk_o;
-    ConfSide a, o;
-    long Tpa, Tpo;            // packed rows per route
-    int nblk_a, nblk_o;
-    int cull;
+struct SchedArgs : ConfPacked {
     const int *seg_start;     // [R][M]
     int M, C, q;
     int band, nbands;         // delays per workgroup (a power of two <= 64), bands per routine
-    double slack;
     double *move, *wait;      // [R][M][C]; null: not asked for
     int *n_seg;
     uint32_t *flags;
 };
 
-__device__ __forceinline__ long sched_clampl(long x, long lo, long hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
-// an order-preserving map of doubles (no NaN) to unsigned 64-bit keys, and back
-__device__ __forceinline__ unsigned long long sched_key(double v)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double sched_unkey(unsigned long long k)
-{
-    return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
-}
-
-__device__ __forceinline__ double sched_wave_max(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double o = __shfl_xor(v, off);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ double sched_wave_min(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double o = __shfl_xor(v, off);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-// the clearance of two packed poses; rows of four doubles, 16-byte aligned
-__device__ __forceinline__ double sched_pair(const double *sfa, int na, const double *sfo, int no, const double *ra, const double *ro)
-{
-    const double2 a01 = *(const double2 *)ra, a23 = *(const double2 *)(ra + 2);
-    const double2 o01 = *(const double2 *)ro, o23 = *(const double2 *)(ro + 2);
-    return pair_clearance(sfa, na, sfo, no, a01.x, a01.y, a23.x, a23.y, o01.x, o01.y, o23.x, o23.y);
-}
-
-__global__ __launch_bounds__(kSchedLanes) void k_schedule_sweep(ConfFoot fa, ConfFoot fo, SchedArgs g)
+__global__ __launch_bounds__(kSweepLanes) void k_schedule_sweep(ConfFoot fa, ConfFoot fo, SchedArgs g)
 {
     __shared__ double sfa[kFootMaxVerts * 8], sfo[kFootMaxVerts * 8];
     __shared__ __attribute__((aligned(16))) double stage_a[kConfBlock * 4];
-    __shared__ double s_suf[kSchedLanes];
+    __shared__ double s_suf[kSweepLanes];
     __shared__ int s_b[VAP_TIMELINE_MAX_LEGS + 1];
-    __shared__ unsigned short s_queue[kSchedQueue];
+    __shared__ unsigned short s_queue[kSweepQueue];
     __shared__ unsigned char s_seg_of[kConfBlock];
     extern __shared__ __attribute__((aligned(16))) unsigned long long s_dyn[];
     unsigned long long *s_key = s_dyn;                                   // [M][64]: the (segment, delay) minima
-    double *stage_o = (double *)(s_dyn + (size_t)g.M * kSchedLanes);     // [64 + (band - 1) q][4]
+    double *stage_o = (double *)(s_dyn + (size_t)g.M * kSweepLanes);     // [64 + (band - 1) q][4]
 
     const int lane = threadIdx.x;
-    sfa[lane] = fa.v[lane];
-    sfa[lane + 64] = fa.v[lane + 64];
-    sfo[lane] = fo.v[lane];
-    sfo[lane + 64] = fo.v[lane + 64];
+    sweep_load_feet(sfa, sfo, fa, fo, lane);
     const int r = blockIdx.x / g.nbands, gi = blockIdx.x % g.nbands;
     const int k0 = gi * g.band, k = k0 + lane;
     const int nb = min(g.band, g.C - k0);                    // live lanes of this band
@@ -142,7 +97,7 @@ __global__ __launch_bounds__(kSchedLanes) void k_schedule_sweep(ConfFoot fa, Con
     }
     __syncthreads();
     if (lane == 0) s_b[S] = (int)n;
-    for (int m = 0; m < M; m++) s_key[m * kSchedLanes + lane] = sched_key(INFINITY);
+    for (int m = 0; m < M; m++) s_key[m * kSweepLanes + lane] = conf_key(INFINITY);
     __syncthreads();
 
     const int q = g.q;
@@ -166,18 +121,17 @@ __global__ __launch_bounds__(kSchedLanes) void k_schedule_sweep(ConfFoot fa, Con
 #pragma unroll 1
                 for (int m = 0; m < S; m++) {
                     const long b0 = s_b[m], len = s_b[m + 1] - b0;
-                    double best = sched_unkey(s_key[m * kSchedLanes + lane]);
+                    double best = conf_unkey(s_key[m * kSweepLanes + lane]);
 #pragma unroll 1
                     for (int j = 0; j < 3; j++) {
                         const long i = b0 + (len * (2 * j + 1)) / 6;
-                        const double c = sched_pair(sfa, na, sfo, no, pa + (size_t)i * 4, po + (size_t)sched_clampl(i + kq, 0, n_o - 1) * 4);
+                        const double c = pair_at(sfa, na, sfo, no, pa + (size_t)i * 4, po + (size_t)clampl(i + kq, 0, n_o - 1) * 4);
                         if (c < best) best = c;
                     }
-                    s_key[m * kSchedLanes + lane] = sched_key(best);
+                    s_key[m * kSweepLanes + lane] = conf_key(best);
                 }
             }
             __syncthreads();
-            int qn = 0, head = 0;                            // the queue's fill and first entry (uniform)
             int m_lo = 0;                                    // the segment of the block's first row (uniform)
 #pragma unroll 1
             for (int blk = 0; blk < nblocks; blk++) {
@@ -191,121 +145,77 @@ __global__ __launch_bounds__(kSchedLanes) void k_schedule_sweep(ConfFoot fa, Con
                     double worst = -INFINITY;
                     if (live)
                         for (int m = m_lo; m <= m_hi; m++) {
-                            const double v = sched_unkey(s_key[m * kSchedLanes + lane]);
+                            const double v = conf_unkey(s_key[m * kSweepLanes + lane]);
                             worst = v > worst ? v : worst;
                         }
-                    const double thr = sched_wave_max(worst);
-                    const double *qa = qa_all + (size_t)blk * 4;
-                    const double ax = qa[0], ay = qa[1], ar = qa[2];
-                    const long b0 = sched_clampl(t0 + (long)k0 * q, 0, n_o - 1) / kConfBlock;
-                    const long b1 = sched_clampl(t0 + kConfBlock - 1 + (long)(k0 + nb - 1) * q, 0, n_o - 1) / kConfBlock;
-                    bool need = false;
-#pragma unroll 1
-                    for (long b = b0 + lane; b <= b1; b += kSchedLanes) {
-                        const double *qo = qo_all + (size_t)b * 4;
-                        const double ox = qo[0], oy = qo[1];
-                        const double slack = g.slack + kCullSlack * (fabs(ax) + fabs(ay) + fabs(ox) + fabs(oy) + ar + qo[2]);
-                        need = need || !conf_culled(thr + slack + radii + ar + qo[2], ox - ax, oy - ay);
-                    }
-                    if (!__any(need)) continue;
+                    const double thr = wave_max(worst);
+                    const long b0 = clampl(t0 + (long)k0 * q, 0, n_o - 1) / kConfBlock;
+                    const long b1 = clampl(t0 + kConfBlock - 1 + (long)(k0 + nb - 1) * q, 0, n_o - 1) / kConfBlock;
+                    if (!band_needs_block(g, radii, thr, qa_all + (size_t)blk * 4, qo_all, b0, b1, lane)) continue;
                 }
-                // stage: every lane has left the previous block's rows (a flush ends with a barrier)
+                sweep_stage(stage_a, pa, t0, n, stage_o, po, t0 + (long)k0 * q, n_o, nq, lane);
                 {
-                    const double *src = pa + (size_t)sched_clampl(t0 + lane, 0, n - 1) * 4;
-                    *(double2 *)(stage_a + lane * 4) = *(const double2 *)src;
-                    *(double2 *)(stage_a + lane * 4 + 2) = *(const double2 *)(src + 2);
-                    int m = m_lo;
+                    int m = m_lo;                            // the segment of the lane's row of the block
                     while (m < m_hi && s_b[m + 1] <= t0 + lane) m++;
                     s_seg_of[lane] = (unsigned char)m;
                 }
-#pragma unroll 1
-                for (int i = lane; i < nq; i += kSchedLanes) {
-                    const double *src = po + (size_t)sched_clampl(t0 + (long)k0 * q + i, 0, n_o - 1) * 4;
-                    *(double2 *)(stage_o + (size_t)i * 4) = *(const double2 *)src;
-                    *(double2 *)(stage_o + (size_t)i * 4 + 2) = *(const double2 *)(src + 2);
-                }
                 __syncthreads();
-                int m_cur = m_lo;
-                double best = sched_unkey(s_key[m_cur * kSchedLanes + lane]);
-                // the exact pair of `cnt` queued survivors, a lane each; afterwards every lane's running minimum is current
-                auto flush = [&](int cnt) {
-                    __syncthreads();
-                    if (lane < cnt) {
-                        const int e = s_queue[(head + lane) & (kSchedQueue - 1)];
-                        const int tt = e & 63, l = e >> 6;
-                        const double c = sched_pair(sfa, na, sfo, no, stage_a + tt * 4, stage_o + (size_t)(tt + l * q) * 4);
-                        if (c == c) atomicMin(&s_key[s_seg_of[tt] * kSchedLanes + l], sched_key(c));   // NaN takes part in nothing
-                    }
-                    __syncthreads();
-                    best = sched_unkey(s_key[m_cur * kSchedLanes + lane]);
-                };
+                int m_cur = m_lo;                            // the segment the walk is in (uniform)
+                SweepQueue queue{sfa, sfo, stage_a, stage_o, s_queue, na, no, lane};
+                // entry (tt, l): lane l's partner row of block row tt sits at stage slot tt + l q; the key of tt's segment;
+                // the lane's minimum of the segment the walk is in
+                const auto slot_of = [&](int tt, int l) { return tt + l * q; };
+                const auto key_of = [&](int tt, int l) { return &s_key[s_seg_of[tt] * kSweepLanes + l]; };
+                const auto own_min = [&]() { return conf_unkey(s_key[m_cur * kSweepLanes + lane]); };
+                double best = own_min();
 #pragma unroll 1
                 for (int tt = 0; tt < hi; tt++) {
                     const int m = s_seg_of[tt];
                     if (m != m_cur) {                        // uniform: the walk passes a segment boundary
                         m_cur = m;
-                        best = sched_unkey(s_key[m_cur * kSchedLanes + lane]);
+                        best = own_min();
                     }
                     bool cand = live;
                     if (cand && g.cull) {
                         const double2 a01 = *(const double2 *)(stage_a + tt * 4);
                         const double2 o01 = *(const double2 *)(stage_o + (size_t)(tt + off_o) * 4);
-                        const double slack = g.slack + kCullSlack * (fabs(a01.x) + fabs(a01.y) + fabs(o01.x) + fabs(o01.y));
-                        cand = !conf_culled(best + slack + radii, o01.x - a01.x, o01.y - a01.y);
+                        cand = !row_culled(g, radii, best, a01.x, a01.y, o01.x, o01.y);
                     }
-                    const unsigned long long mask = __ballot(cand);
-                    if (mask) {
-                        if (cand) {
-                            const int pos = head + qn + __popcll(mask & ((1ull << lane) - 1ull));
-                            s_queue[pos & (kSchedQueue - 1)] = (unsigned short)(tt | (lane << 6));
-                        }
-                        qn += __popcll(mask);
-                        if (qn >= kSchedLanes) {
-                            flush(kSchedLanes);
-                            head = (head + kSchedLanes) & (kSchedQueue - 1);
-                            qn -= kSchedLanes;
-                        }
-                    }
+                    queue.push(cand, tt, best, slot_of, key_of, own_min);
                 }
-                flush(qn);                                   // the rows leave LDS with this block; also the barrier
-                head = 0;
-                qn = 0;
+                queue.close(best, slot_of, key_of, own_min);
             }
             // the tail: parked at row n - 1 against partner rows n + k q .. n_o - 1, each tested once per band
             const long j_lo = n + (long)k0 * q;
             if (j_lo < n_o) {
                 const double *ra = pa + (size_t)(n - 1) * 4;
                 const double ax = ra[0], ay = ra[1];
-                unsigned long long *key = s_key + (S - 1) * kSchedLanes + lane;
+                unsigned long long *key = s_key + (S - 1) * kSweepLanes + lane;
 #pragma unroll 1
-                for (long j0 = j_lo; j0 < n_o; j0 += kSchedLanes) {
+                for (long j0 = j_lo; j0 < n_o; j0 += kSweepLanes) {
                     const long j = j0 + lane;
-                    const double thr = sched_wave_max(live ? sched_unkey(*key) : -INFINITY);
+                    const double thr = wave_max(live ? conf_unkey(*key) : -INFINITY);
                     double c = INFINITY;
                     if (j < n_o) {
                         const double *ro = po + (size_t)j * 4;
-                        bool test = true;
-                        if (g.cull) {
-                            const double slack = g.slack + kCullSlack * (fabs(ax) + fabs(ay) + fabs(ro[0]) + fabs(ro[1]));
-                            test = !conf_culled(thr + slack + radii, ro[0] - ax, ro[1] - ay);
-                        }
+                        const bool test = !g.cull || !row_culled(g, radii, thr, ax, ay, ro[0], ro[1]);
                         if (test) {
-                            const double e = sched_pair(sfa, na, sfo, no, ra, ro);
+                            const double e = pair_at(sfa, na, sfo, no, ra, ro);
                             if (e == e) c = e;
                         }
                     }
 #pragma unroll
-                    for (int off = 1; off < kSchedLanes; off <<= 1) {    // c = the minimum over lanes lane .. 63
+                    for (int off = 1; off < kSweepLanes; off <<= 1) {    // c = the minimum over lanes lane .. 63
                         const double o = __shfl_down(c, off);
-                        if (lane + off < kSchedLanes && o < c) c = o;
+                        if (lane + off < kSweepLanes && o < c) c = o;
                     }
                     __syncthreads();
                     s_suf[lane] = c;
                     __syncthreads();
                     const long st = n + kq - j0;             // where the lane's range starts inside this chunk
-                    if (live && st < kSchedLanes) {
+                    if (live && st < kSweepLanes) {
                         const double v = s_suf[st > 0 ? st : 0];
-                        if (v < sched_unkey(*key)) *key = sched_key(v);
+                        if (v < conf_unkey(*key)) *key = conf_key(v);
                     }
                 }
             }
@@ -313,7 +223,7 @@ __global__ __launch_bounds__(kSchedLanes) void k_schedule_sweep(ConfFoot fa, Con
         }
         if (live)
             for (int m = 0; m < M; m++) {
-                const double v = m < S ? sched_unkey(s_key[m * kSchedLanes + lane]) : INFINITY;
+                const double v = m < S ? conf_unkey(s_key[m * kSweepLanes + lane]) : INFINITY;
                 g.move[out0 + (size_t)m * g.C] = v != INFINITY ? v : NAN;
             }
     }
@@ -334,13 +244,9 @@ __global__ __launch_bounds__(kSchedLanes) void k_schedule_sweep(ConfFoot fa, Con
 #pragma unroll 1
                     for (long t = b + kq, te = t + q; t < te; t++) {
                         const double *ro = po + (size_t)(t < n_o - 1 ? t : n_o - 1) * 4;
-                        bool test = true;
-                        if (g.cull) {
-                            const double slack = g.slack + kCullSlack * (fabs(ax) + fabs(ay) + fabs(ro[0]) + fabs(ro[1]));
-                            test = !conf_culled(best + slack + radii, ro[0] - ax, ro[1] - ay);
-                        }
+                        const bool test = !g.cull || !row_culled(g, radii, best, ax, ay, ro[0], ro[1]);
                         if (test) {
-                            const double c = sched_pair(sfa, na, sfo, no, ra, ro);
+                            const double c = pair_at(sfa, na, sfo, no, ra, ro);
                             if (c < best) best = c;          // false for NaN
                         }
                         if (t >= n_o - 1) break;             // the partner is parked: the instants behind repeat this pose
@@ -469,7 +375,7 @@ __global__ __launch_bounds__(64) void k_schedule_solve(int M, int C, int q, doub
     if (delay_rows)
         for (int m = (have ? S : 0) + lane; m < M; m += 64) delay_rows[(size_t)r * M + m] = have ? 0 : -1;
     if (clearance) {
-        best = sched_wave_min(best);
+        best = wave_min(best);
         if (lane == 0) clearance[r] = best != INFINITY ? best : NAN;
     }
 }
@@ -486,16 +392,12 @@ int vap_schedule_tables(vap_ctx *ctx, int n_delays, int delay_step,
                         double *d_move, double *d_wait, int *d_n_seg, uint32_t *d_flags)
 {
     using namespace vap;
+    const ConfInput a{R, cap_a, d_rows_a, d_counts_a, stride_a, n_foot_a, h_foot_a}, o{Bo, cap_o, d_rows_o, d_counts_o, stride_o, n_foot_o, h_foot_o};
     if (M < 1 || n_delays < 1 || delay_step < 1)
         return vap_fail(VAP_ERR_INVALID, "M, n_delays and delay_step must be >= 1 (got %d, %d, %d)", M, n_delays, delay_step);
-    if (R < 0 || Bo < 0 || cap_a < 0 || cap_o < 0)
-        return vap_fail(VAP_ERR_INVALID, "bad shape R=%d cap_a=%ld Bo=%d cap_o=%ld", R, cap_a, Bo, cap_o);
-    if (stride_a < 1 || stride_o < 1) return vap_fail(VAP_ERR_INVALID, "count strides must be >= 1 (got %d, %d)", stride_a, stride_o);
-    if ((R > 0 && (!d_counts_a || !d_seg_start || (cap_a > 0 && !d_rows_a))) || (R > 0 && Bo > 0 && (!d_counts_o || (cap_o > 0 && !d_rows_o))))
-        return vap_fail(VAP_ERR_INVALID, "null rows / counts / segment starts");
-    if (!h_foot_a || !h_foot_o) return vap_fail(VAP_ERR_INVALID, "null footprint");
-    VAP_TRY(check_convex(h_foot_a, n_foot_a, "footprint", 0));
-    VAP_TRY(check_convex(h_foot_o, n_foot_o, "footprint", 1));
+    VAP_TRY(conf_check_shape("R", a, o));
+    // no pairing and no margin here; without routines nothing of the partners is read
+    VAP_TRY(conf_check_sides(a, o, R > 0 ? Bo : 0, false, 0.0, R > 0 && !d_seg_start, "null rows / counts / segment starts"));
     if (M > VAP_TIMELINE_MAX_LEGS) return vap_fail(VAP_ERR_UNSUPPORTED, "%d slots above VAP_TIMELINE_MAX_LEGS = %d", M, VAP_TIMELINE_MAX_LEGS);
     if (n_delays > VAP_SCHEDULE_MAX_DELAYS)
         return vap_fail(VAP_ERR_UNSUPPORTED, "%d delays above VAP_SCHEDULE_MAX_DELAYS = %d", n_delays, VAP_SCHEDULE_MAX_DELAYS);
@@ -503,61 +405,30 @@ int vap_schedule_tables(vap_ctx *ctx, int n_delays, int delay_step,
         return vap_fail(VAP_ERR_UNSUPPORTED, "a window of %d delays at step %d ends above %d rows", n_delays, delay_step, INT_MAX);
     if (cap_a > INT_MAX || cap_o > INT_MAX)
         return vap_fail(VAP_ERR_UNSUPPORTED, "capacity %ld above %d rows", cap_a > cap_o ? cap_a : cap_o, INT_MAX);
-    const long nblk_a = cap_a > 0 ? (cap_a + kConfBlock - 1) / kConfBlock : 1, nblk_o = cap_o > 0 ? (cap_o + kConfBlock - 1) / kConfBlock : 1;
-    const long Tpa = nblk_a * kConfBlock, Tpo = nblk_o * kConfBlock;
-    const int groups_a = (int)((nblk_a + 3) / 4), groups_o = (int)((nblk_o + 3) / 4);
-    // the band: the most delays, a power of two, whose partner rows fit the stage
-    int band = kSchedLanes;
-    while (band > 1 && kConfBlock + (long)(band - 1) * delay_step > kSchedStageRows) band /= 2;
-    const int nbands = (n_delays + band - 1) / band;
-    const int nb_max = band < n_delays ? band : n_delays;
-    const long grid = (long)R * nbands, grid_pack = (long)R * groups_a > (long)Bo * groups_o ? (long)R * groups_a : (long)Bo * groups_o;
+    const ConfHorizon ha = conf_horizon(cap_a), ho = conf_horizon(cap_o);
+    const SweepBands bands = sweep_bands(n_delays, delay_step, (size_t)M * kSweepLanes * 8);
+    const long grid = (long)R * bands.nbands, grid_pack = (long)R * ha.groups > (long)Bo * ho.groups ? (long)R * ha.groups : (long)Bo * ho.groups;
     if (grid > INT_MAX || grid_pack > INT_MAX)
         return vap_fail(VAP_ERR_UNSUPPORTED, "%d routines, %d partners, %d delays: too many workgroups for one launch", R, Bo, n_delays);
     VAP_TRY(vap_set_device(ctx));
     if (R == 0) return VAP_OK;
     if (!d_move && !d_wait && !d_n_seg && !d_flags) return VAP_OK;
+    VAP_TRY(sweep_fits(ctx, bands, delay_step, kSchedStaticLds, "delays"));
 
-    VAP_TRY(ctx->ensure(ctx->conf_pack_a, (size_t)R * (size_t)Tpa * 32));
-    VAP_TRY(ctx->ensure(ctx->conf_blk_a, (size_t)R * (size_t)nblk_a * 32));
-    if (Bo > 0) {
-        VAP_TRY(ctx->ensure(ctx->conf_pack_o, (size_t)Bo * (size_t)Tpo * 32));
-        VAP_TRY(ctx->ensure(ctx->conf_blk_o, (size_t)Bo * (size_t)nblk_o * 32));
-    }
     ConfFoot fa, fo;
-    conf_foot(h_foot_a, n_foot_a, fa);
-    conf_foot(h_foot_o, n_foot_o, fo);
     SchedArgs g;
-    g.a = ConfSide{d_rows_a, d_counts_a, cap_a, stride_a, R, 0};
-    g.o = ConfSide{d_rows_o, d_counts_o, cap_o, stride_o, Bo, 0};
-    g.pack_a = (const double *)ctx->conf_pack_a.ptr;
-    g.pack_o = (const double *)ctx->conf_pack_o.ptr;
-    g.blk_a = (const double *)ctx->conf_blk_a.ptr;
-    g.blk_o = (const double *)ctx->conf_blk_o.ptr;
-    g.Tpa = Tpa;
-    g.Tpo = Tpo;
-    g.nblk_a = (int)nblk_a;
-    g.nblk_o = (int)nblk_o;
-    g.cull = ctx->footprint_cull;
+    VAP_TRY(conf_pack_sides(ctx, a, o, 0, ha, ho, fa, fo, g));
     g.seg_start = d_seg_start;
     g.M = M;
     g.C = n_delays;
     g.q = delay_step;
-    g.band = band;
-    g.nbands = nbands;
-    g.slack = kCullSlack * (1.0 + fa.R + fo.R);
+    g.band = bands.band;
+    g.nbands = bands.nbands;
     g.move = d_move;
     g.wait = d_wait;
     g.n_seg = d_n_seg;
     g.flags = d_flags;
-    const size_t lds = (size_t)M * kSchedLanes * 8 + (size_t)(kConfBlock + (long)(nb_max - 1) * delay_step) * 32;
-
-    hipLaunchKernelGGL(k_conflict_pack, dim3((unsigned)((long)R * groups_a)), dim3(256), 0, ctx->stream, g.a, fa.cx, fa.cy, Tpa,
-                       (int)nblk_a, groups_a, (double *)ctx->conf_pack_a.ptr, (double *)ctx->conf_blk_a.ptr);
-    if (Bo > 0)
-        hipLaunchKernelGGL(k_conflict_pack, dim3((unsigned)((long)Bo * groups_o)), dim3(256), 0, ctx->stream, g.o, fo.cx, fo.cy, Tpo,
-                           (int)nblk_o, groups_o, (double *)ctx->conf_pack_o.ptr, (double *)ctx->conf_blk_o.ptr);
-    hipLaunchKernelGGL(k_schedule_sweep, dim3((unsigned)grid), dim3(kSchedLanes), lds, ctx->stream, fa, fo, g);
+    hipLaunchKernelGGL(k_schedule_sweep, dim3((unsigned)grid), dim3(kSweepLanes), bands.lds, ctx->stream, fa, fo, g);
     HIP_TRY(hipGetLastError());
     return VAP_OK;
 }

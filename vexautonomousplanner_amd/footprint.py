@@ -192,6 +192,29 @@ def _ccw_polygon(vertices, what):
 PAIRINGS = {"all": _lib.CONFLICT_ALL_PAIRS, "matched": _lib.CONFLICT_MATCHED}
 
 
+def _two_footprints(footprint_a, footprint_o, pairing="all", names=("footprint_a", "footprint_o")):
+    """Prologue of conflicts, shifts and timeline.schedule, part 1: both polygons (side O's None = side A's), ``pairing``."""
+    foot_a = _ccw_polygon(footprint_a, names[0])
+    foot_o = foot_a if footprint_o is None else _ccw_polygon(footprint_o, names[1])
+    if not isinstance(pairing, str) or pairing not in PAIRINGS:
+        raise ValueError(f"pairing must be 'all' or 'matched' (got {pairing!r})")
+    return foot_a, foot_o
+
+
+def _two_sides(rows_a, counts_a, rows_o, counts_o, device, pairing="all", names=("side A", "side O"), batch=None):
+    """Part 2, behind the wrapper's own scalars so that the errors keep their order: both sides on one device, the matched
+    check, the shapes (Ba, cap_a, Bo, cap_o, P).  ``batch`` names side A's routes where a single trajectory is refused."""
+    given = [r.device for r in (rows_a, rows_o) if isinstance(r, torch.Tensor)]
+    rows_a, counts_a, single, dev = time_rows(rows_a, counts_a, given[0] if given else None, device, names[0])
+    if single and batch:
+        raise ValueError(f"rows must be (R, capacity, 8): a batch of {batch}")
+    rows_o, counts_o, _, _ = time_rows(rows_o, counts_o, dev, device, names[1])
+    Ba, cap_a, Bo, cap_o = int(rows_a.shape[0]), int(rows_a.shape[1]), int(rows_o.shape[0]), int(rows_o.shape[1])
+    if pairing == "matched" and Ba != Bo:
+        raise ValueError(f"matched pairing needs as many routes on both sides (got {Ba} and {Bo})")
+    return rows_a, counts_a, rows_o, counts_o, single, dev, (Ba, cap_a, Bo, cap_o, 1 if pairing == "matched" else Bo)
+
+
 def conflicts(rows_a, counts_a, footprint_a, rows_o, counts_o, footprint_o=None, margin=0.0, shift_rows=0, pairing="all",
               pairs=False, out=None, device=0, ctx=None, cull=True):
     """Robot-to-robot clearance between two batches of time-domain rows (vap_footprint_conflicts): which of side A's
@@ -215,18 +238,9 @@ def conflicts(rows_a, counts_a, footprint_a, rows_o, counts_o, footprint_o=None,
     goes below margin, or -1), first_time, n_conflicts, compatible (n_conflicts == 0).  A route without a valid pair
     (no rows on either side) gets NaN / -1 / 0 (compatible).  A single side-A trajectory gives 0-d tensors ((P,) for the
     pair outputs).  Work runs on torch's current stream and is not synchronised."""
-    foot_a = _ccw_polygon(footprint_a, "footprint_a")
-    foot_o = foot_a if footprint_o is None else _ccw_polygon(footprint_o, "footprint_o")
-    if not isinstance(pairing, str) or pairing not in PAIRINGS:
-        raise ValueError(f"pairing must be 'all' or 'matched' (got {pairing!r})")
+    foot_a, foot_o = _two_footprints(footprint_a, footprint_o, pairing)
     shift_rows = int(shift_rows)
-    given = [r.device for r in (rows_a, rows_o) if isinstance(r, torch.Tensor)]
-    rows_a, counts_a, single, dev = time_rows(rows_a, counts_a, given[0] if given else None, device, "side A")
-    rows_o, counts_o, _, _ = time_rows(rows_o, counts_o, dev, device, "side O")
-    Ba, cap_a, Bo, cap_o = int(rows_a.shape[0]), int(rows_a.shape[1]), int(rows_o.shape[0]), int(rows_o.shape[1])
-    if pairing == "matched" and Ba != Bo:
-        raise ValueError(f"matched pairing needs as many routes on both sides (got {Ba} and {Bo})")
-    P = 1 if pairing == "matched" else Bo
+    rows_a, counts_a, rows_o, counts_o, single, dev, (Ba, cap_a, Bo, cap_o, P) = _two_sides(rows_a, counts_a, rows_o, counts_o, device, pairing)
     shapes = {"min_clearance": ((Ba,), torch.float64), "min_other": ((Ba,), torch.int32), "min_row": ((Ba,), torch.int32),
               "n_conflicts": ((Ba,), torch.int32), "first_row": ((Ba,), torch.int32)}
     if pairs:
@@ -287,25 +301,16 @@ def shifts(rows_a, counts_a, footprint_a, rows_o, counts_o, footprint_o=None, ma
     none), n_safe (unblocked shifts of the window) and first_time (first_shift x the rows' time step; NaN where there is
     none).  A route without rows gets -1 / 0; one with rows and no valid pair is blocked nowhere.  A single side-A
     trajectory gives 0-d tensors.  Work runs on torch's current stream and is not synchronised."""
-    foot_a = _ccw_polygon(footprint_a, "footprint_a")
-    foot_o = foot_a if footprint_o is None else _ccw_polygon(footprint_o, "footprint_o")
-    if not isinstance(pairing, str) or pairing not in PAIRINGS:
-        raise ValueError(f"pairing must be 'all' or 'matched' (got {pairing!r})")
+    foot_a, foot_o = _two_footprints(footprint_a, footprint_o, pairing)
     if not isinstance(scan, str) or scan not in SCANS:
         raise ValueError(f"scan must be 'up' or 'down' (got {scan!r})")
     shift_lo, n_shifts, shift_step, hold, min_run = int(shift_lo), int(n_shifts), int(shift_step), int(hold), int(min_run)
-    given = [r.device for r in (rows_a, rows_o) if isinstance(r, torch.Tensor)]
-    rows_a, counts_a, single, dev = time_rows(rows_a, counts_a, given[0] if given else None, device, "side A")
-    rows_o, counts_o, _, _ = time_rows(rows_o, counts_o, dev, device, "side O")
-    Ba, cap_a, Bo, cap_o = int(rows_a.shape[0]), int(rows_a.shape[1]), int(rows_o.shape[0]), int(rows_o.shape[1])
-    if pairing == "matched" and Ba != Bo:
-        raise ValueError(f"matched pairing needs as many routes on both sides (got {Ba} and {Bo})")
+    rows_a, counts_a, rows_o, counts_o, single, dev, (Ba, cap_a, Bo, cap_o, P) = _two_sides(rows_a, counts_a, rows_o, counts_o, device, pairing)
     if isinstance(base, torch.Tensor) and base.device != dev:
         raise ValueError(f"base is on {base.device}, the rows on {dev}")
     base = device_array(base, dev, torch.int32)
     if base is not None and tuple(base.shape) != (Ba,):
         raise ValueError(f"base must be ({Ba},), got {tuple(base.shape)}")
-    P = 1 if pairing == "matched" else Bo
     n = max(n_shifts, 0)
     shapes = {"first": ((Ba,), torch.int32), "n_safe": ((Ba,), torch.int32)}
     if table:

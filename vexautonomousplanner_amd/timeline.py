@@ -199,8 +199,7 @@ def schedule(tl, footprint, others_rows, others_counts, others_footprint=None, m
     (a multiple of dt, or 0) for the sum to stay exact; the wait in front of slot 0 is not a dwell: shift the routine's start
     by start_delay_rows.  Nothing is read on the host; work runs on torch's current stream and is not synchronised."""
     from . import footprint as fp
-    foot_a = fp._ccw_polygon(footprint, "footprint")
-    foot_o = foot_a if others_footprint is None else fp._ccw_polygon(others_footprint, "others_footprint")
+    foot_a, foot_o = fp._two_footprints(footprint, others_footprint, names=("footprint", "others_footprint"))
     margin, n_delays, delay_step = float(margin), int(n_delays), int(delay_step)
     if not math.isfinite(margin):
         raise ValueError(f"margin must be finite (got {margin!r})")
@@ -215,12 +214,8 @@ def schedule(tl, footprint, others_rows, others_counts, others_footprint=None, m
             rows, counts, seg_start = tl
         except (TypeError, ValueError):
             raise ValueError("tl must be what chain returned or a tuple (rows, counts, seg_start)") from None
-    given = [r.device for r in (rows, others_rows) if isinstance(r, torch.Tensor)]
-    rows, counts, single, dev = time_rows(rows, counts, given[0] if given else None, device, "routines")
-    if single:
-        raise ValueError("rows must be (R, capacity, 8): a batch of routines")
-    o_rows, o_counts, _, _ = time_rows(others_rows, others_counts, dev, device, "others")
-    R, cap, Bo, cap_o = int(rows.shape[0]), int(rows.shape[1]), int(o_rows.shape[0]), int(o_rows.shape[1])
+    rows, counts, o_rows, o_counts, _, dev, (R, cap, Bo, cap_o, _) = fp._two_sides(rows, counts, others_rows, others_counts, device,
+                                                                                   names=("routines", "others"), batch="routines")
     if isinstance(seg_start, torch.Tensor) and seg_start.device != dev:
         raise ValueError(f"seg_start is on {seg_start.device}, the rows on {dev}")
     seg_start = device_array(seg_start, dev, torch.int32)
