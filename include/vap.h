@@ -866,6 +866,67 @@ int vap_rollout_clearance(vap_ctx *ctx, int follower_kind, const void *follower,
                           int *d_clear_rows, double *d_worst_clearance, int *d_worst_clear_rollout, int *d_worst_clear_row,
                           int *d_worst_clear_element, double *d_mean_clearance, int *d_n_colliding, int *d_n_clear_valid);
 
+/* ---- clearance of the disturbed rollouts to the partner's routines --------------------------------------------------
+ * Does a disturbed run still miss my partner?  vap_rollout_clearance answers for the scene; this call answers for the other
+ * robots.  The rollout calls can write every executed row and vap_footprint_conflicts can read them back, once per distinct
+ * start shift; this call runs the K rollouts per route of either follower and takes, for every executed row while it is on
+ * the chip, the clearance to every partner route at the same instant.  No executed rows are written, and side A is never
+ * packed.
+ *
+ *   follower, rollouts   follower_kind, follower, B, capacity, d_rows, d_counts, counts_stride, time_step, K, shared_perturb,
+ *             d_perturb and the follower outputs d_stats .. d_route_status: exactly as vap_rollout_clearance takes and
+ *             writes them (the follower's plain call, bit for bit; d_n_unfinished and d_route_status NULL with
+ *             VAP_FOLLOWER_RAMSETE; the same 16-byte alignment rule).
+ *   sides     n_foot_a, h_foot_a: my robot's footprint.  Side O ("others"): Bo, cap_o, d_rows_o, d_counts_o, stride_o,
+ *             n_foot_o, h_foot_o, and margin, as vap_footprint_conflicts names and validates them.  Bo is 1 ..
+ *             VAP_ROLLOUT_CONFLICT_OTHERS_MAX: Bo = 0 is VAP_ERR_INVALID, above the limit VAP_ERR_UNSUPPORTED.
+ *   shifts    shift_rows (host), d_route_shift [B] or NULL for 0, d_rollout_shift [K] (shared by all routes) or NULL for 0.
+ *             For rollout (b, k) side O starts s = shift_rows + route_shift[b] + rollout_shift[k] rows late, summed in 64
+ *             bits.  shift_rows must lie within +-2^24, else VAP_ERR_INVALID; each device entry is CLAMPED into +-2^24
+ *             before the sum.
+ *   DEFINITION  Let E be that follower's d_exec_rows / d_exec_counts (route b * K + k, counts_stride 2, capacity capacity +
+ *             settle_rows).  For rollout (b, k) with its shift s, one call vap_footprint_conflicts(VAP_CONFLICT_ALL_PAIRS,
+ *             shift_rows = s, margin, Ba = 1: that executed route, h_foot_a; side O as given) defines, bit for bit:
+ *             per pair (optional): d_pair_clearance [B][K][Bo] = that call's d_pair_clearance[o]; d_pair_rows [B][K][Bo][2] =
+ *             its d_pair_row[o], d_pair_first_row[o].
+ *             per rollout: d_conflict [B][K] = its d_min_clearance; d_conflict_rows [B][K][4] = its d_min_other, d_min_row,
+ *             d_n_conflicts, d_first_row (the other at the minimum, its row, the pairs below the margin, the earliest
+ *             first row or -1).
+ *             Everything vap_footprint_conflicts defines is inherited: pose columns 4, 6, 7 and body angle -heading
+ *             (here: what step 3 of the rollout would store, heading = -wrap(phi)); the horizon T = max(n_a, n_o + s, 1)
+ *             with n_a the rollout's executed count; parking at the first or last pose; a NaN pose takes part in nothing;
+ *             an invalid pair (n_a = 0 or n_o = 0) gives NaN, -1, -1; a strictly smaller clearance replaces, the first row
+ *             stays on a tie; the smallest o wins on a tie across pairs.  A rollout without executed rows (n = 0, an
+ *             invalid record, a non-zero pursuit status) gets the outputs of a route without a valid pair: NaN, -1, -1,
+ *             0, -1, and NaN, -1, -1 per pair.
+ *             per route [B], over the route's valid rollouts (conflict row >= 0) in ascending k: d_worst_conflict (the
+ *             smallest per-rollout value; the smallest k on a tie), d_worst_conflict_rollout, d_worst_conflict_other,
+ *             d_worst_conflict_row (that k, its other and its row), d_mean_conflict (one running sum divided by the
+ *             count), d_n_conflicting (valid rollouts below the margin), d_n_conflict_valid.  A route without a valid
+ *             rollout gets NaN, -1, -1, -1, NaN, 0, 0.
+ *             Every output pointer may be NULL.
+ * The check is discrete at time_step.  VAP_OPT_FOOTPRINT_CULL governs culling (the row's bounding circles before the exact
+ * pair); on and off give the same bits.  Every reduction has a fixed order and there are no float atomics: two calls on
+ * the same inputs give the same bits.
+ * VAP_ERR_INVALID: every error of the follower's own call; Bo < 1; shift_rows beyond +-2^24; a negative cap_o; stride_o <
+ * 1; null rows or counts of side O with B > 0; a non-finite margin; a null, clockwise, non-convex or degenerate footprint.
+ * VAP_ERR_UNSUPPORTED: Bo above the limit; capacity + settle_rows or cap_o so large that a row index n + 3 * 2^24 could
+ * pass INT_MAX; too many workgroups for one launch; more LDS than the device gives a workgroup (4 KiB per partner route
+ * beside the kernel's own; the message has the byte count).  The host arguments are checked before the context is touched.
+ * B = 0 is a no-op.  Works on the context's stream and does not synchronise.  Context scratch: side O's packed rows (Bo x
+ * cap_o x 32 B), pure pursuit's status words, and for K > 256 the B x K partials of the summaries; it never grows with
+ * rows x K. */
+#define VAP_ROLLOUT_CONFLICT_OTHERS_MAX 16
+int vap_rollout_conflicts(vap_ctx *ctx, int follower_kind, const void *follower, int B, long capacity, const double *d_rows,
+                          const int *d_counts, int counts_stride, double time_step, int K, int shared_perturb,
+                          const double *d_perturb, int n_foot_a, const double *h_foot_a, int Bo, long cap_o, const double *d_rows_o,
+                          const int *d_counts_o, int stride_o, int n_foot_o, const double *h_foot_o, double margin, int shift_rows,
+                          const int *d_route_shift, const int *d_rollout_shift, double *d_stats, int *d_stat_rows, double *d_worst,
+                          double *d_mean, int *d_worst_rollout, int *d_worst_row, int *d_n_exceeding, int *d_n_unfinished,
+                          int *d_route_status, double *d_pair_clearance, int *d_pair_rows, double *d_conflict, int *d_conflict_rows,
+                          double *d_worst_conflict, int *d_worst_conflict_rollout, int *d_worst_conflict_other,
+                          int *d_worst_conflict_row, double *d_mean_conflict, int *d_n_conflicting, int *d_n_conflict_valid);
+
 /* ---- cross-entropy route search over batches of candidate trajectories --------------------------------------------
  * The calls above judge candidate routes; these two make the candidates and act on the verdicts, so that a search
  *   sample -> vap_profile_batch -> vap_time_profile -> vap_footprint_clearance [-> conflicts, rollouts] -> update

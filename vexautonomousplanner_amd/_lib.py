@@ -78,7 +78,7 @@ EXPORTS = (
     "vap_profile_routes", "vap_time_profile_routes", "vap_time_insert_events", "vap_limit_rows_dtype",
     "vap_closest_points", "vap_route_closest", "vap_footprint_clearance", "vap_footprint_conflicts",
     "vap_conflict_shifts", "vap_schedule_tables", "vap_schedule_solve",
-    "vap_tracking_rollouts", "vap_pursuit_rollouts", "vap_rollout_clearance", "vap_search_sample", "vap_search_update", "vap_plan_grid", "vap_plan_seeds",
+    "vap_tracking_rollouts", "vap_pursuit_rollouts", "vap_rollout_clearance", "vap_rollout_conflicts", "vap_search_sample", "vap_search_update", "vap_plan_grid", "vap_plan_seeds",
     "vap_plan_occupancy", "vap_plan_seeds_occupied", "vap_plan_travel", "vap_plan_order",
     "vap_routine_timeline", "vap_plan_order_timed", "vap_velocity_conditioning",
     "vap_curve_caps", "vap_drive_audit", "vap_range_readings", "vap_odometry_rollouts",
@@ -234,6 +234,9 @@ def lib():
                                        C.c_int, vp] + [vp] * 9 + [C.c_long, vp, vp]
     L.vap_rollout_clearance.argtypes = [vp, C.c_int, vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp,
                                         C.c_int, dp, dp, C.c_int, ip, dp, C.c_int, dp, C.c_double] + [vp] * 18
+    L.vap_rollout_conflicts.argtypes = [vp, C.c_int, vp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp,
+                                        C.c_int, dp, C.c_int, C.c_long, vp, vp, C.c_int, C.c_int, dp, C.c_double, C.c_int, vp, vp] + \
+        [vp] * 20
     L.vap_search_sample.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]
     L.vap_search_update.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double] + [vp] * 5 + \
         [C.POINTER(SearchWeights), C.c_int, C.c_double, C.c_double, C.c_double] + [vp] * 10 + [C.c_int, C.c_uint32]

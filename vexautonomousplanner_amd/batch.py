@@ -625,6 +625,19 @@ class BatchedTrajectoryGenerator:
             raise ValueError(f"rows must be on {self.device}")
         return tracking.rollout_clearance(tp["rows"], tp["counts"], follower, perturbations, footprint, scene, ctx=self.ctx, **kw)
 
+    def rollout_conflicts(self, tp, follower, perturbations, footprint, others, others_footprint=None, **kw):
+        """Clearance of the disturbed rollouts along the rows of ``tp`` to the partner's rows ``others`` — both dicts as
+        ``time_profile`` / ``insert_waits`` return them, on the same time step — without executed rows in memory
+        (vap_rollout_conflicts on this generator's context and torch's current stream; see tracking.rollout_conflicts for
+        margin, shift_rows, route_shift, rollout_shift, pairs, time_step, out, cull and the returned dict).  ``follower``:
+        a tracking.Follower or a tracking.Pursuit; ``footprint``, ``others_footprint``: as in ``footprint_conflicts``."""
+        from . import tracking
+        for d in (tp, others):
+            if d["rows"].device != self.device:
+                raise ValueError(f"rows must be on {self.device}")
+        return tracking.rollout_conflicts(tp["rows"], tp["counts"], follower, perturbations, footprint, others["rows"],
+                                          others["counts"], others_footprint, ctx=self.ctx, **kw)
+
     def refine(self, seeds, sigma0, footprint, scene, **kw):
         """Cross-entropy search for faster routes that still clear ``scene`` (and a partner's routines, and a follower's
         tracking error), starting from ``seeds``: sample, profile, time_profile, clearance checks and the refit run on this

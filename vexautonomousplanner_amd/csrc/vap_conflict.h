@@ -1,7 +1,8 @@
 // vap_conflict.h — what the robot-to-robot calls share: vap_conflict.hip (vap_footprint_conflicts, one start shift),
 // vap_conflict_shifts.hip (vap_conflict_shifts, a window of them) and vap_schedule.hip (vap_schedule_tables, a delay in
 // front of every slot of a routine).
-// Device: the packed footprint and side, the pack kernel (defined in vap_conflict.hip), the exact polygon pair in one
+// Device: the packed footprint and side, the packed pose of a row (conf_pose, which the rollout lanes of
+// vap_rollout_conflicts form on the chip), the pack kernel (defined in vap_conflict.hip), the exact polygon pair in one
 // footprint's body frame (pair_clearance; pair_at on two packed rows), the bounding-circle cull of a row and of a 64-row
 // block (row_culled, block_culled), minima as integer keys (conf_key / conf_unkey), clampl, floordiv64, wave_min / wave_max.
 // Host: ConfInput (a side as an entry point receives it), the shared argument checks (conf_check_shape, conf_check_sides),
@@ -89,6 +90,17 @@ __device__ __forceinline__ T wave_max(T v)
         v = o > v ? o : v;
     }
     return v;
+}
+
+// The packed pose {cx, cy, cos, sin} of a row (heading, x, y): cos and sin of the body angle -heading and the posed centre
+// of the footprint's bounding circle, (fcx, fcy) in the body frame.  The pack kernel and the rollout lanes
+// (vap_rollout_conflicts) both call this, so a pose formed on the chip has the bits of the same row packed from memory.
+__device__ __forceinline__ void conf_pose(double heading, double x, double y, double fcx, double fcy, double &cx, double &cy, double &c,
+                                          double &sn)
+{
+    sincos(-heading, &sn, &c);
+    cx = x + (c * fcx - sn * fcy);
+    cy = y + (sn * fcx + c * fcy);
 }
 
 // pack[b][Tp][4] = {cx, cy, cos, sin} of horizon row r (route row clamp(r - shift, 0, n - 1)); blk[b][nblk][4] = centre,

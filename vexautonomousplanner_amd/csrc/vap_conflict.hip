@@ -56,9 +56,7 @@ __global__ __launch_bounds__(256) void k_conflict_pack(ConfSide s, double fcx, d
         long src = r - s.shift;
         src = src < 0 ? 0 : (src > n - 1 ? n - 1 : src);
         const double *row = s.rows + ((size_t)b * (size_t)s.cap + (size_t)src) * 8;
-        sincos(-row[4], &sn, &c);
-        cx = row[6] + (c * fcx - sn * fcy);
-        cy = row[7] + (sn * fcx + c * fcy);
+        conf_pose(row[4], row[6], row[7], fcx, fcy, cx, cy, c, sn);
     }
     double *o = pack + ((size_t)b * (size_t)Tp + (size_t)r) * 4;
     o[0] = cx;

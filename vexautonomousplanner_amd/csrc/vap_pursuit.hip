@@ -105,11 +105,12 @@ struct PursuitSummary : TrackSummary {
 };
 
 // The rollouts of one workgroup.  MODE: what becomes of the executed row (kTrackPlain, kTrackExec, kTrackClear,
-// kTrackSplit); `c` is read with the last two only.
+// kTrackSplit, kTrackConflict); `c` is read with kTrackClear and kTrackSplit only, `x` and the footprints with kTrackConflict.
 template <int MODE>
-__device__ __forceinline__ void pursuit_rollouts(const PursuitArgs &g, const TrackClear *c)
+__device__ __forceinline__ void pursuit_rollouts(const PursuitArgs &g, const TrackClear *c, const TrackConflict *x = nullptr,
+                                                 const ConfFoot *fa = nullptr, const ConfFoot *fo = nullptr)
 {
-    constexpr bool EXEC = MODE == kTrackExec, SPLIT = MODE == kTrackSplit;
+    constexpr bool EXEC = MODE == kTrackExec, SPLIT = MODE == kTrackSplit, CONF = MODE == kTrackConflict;
     __shared__ double s_e[kTrackThreads];
     __shared__ int s_r[kTrackThreads], s_a[kTrackThreads];
     const int tid = threadIdx.x;
@@ -124,6 +125,8 @@ __device__ __forceinline__ void pursuit_rollouts(const PursuitArgs &g, const Tra
     const int b = b0 + lr;
     const bool inside = producer && lr < R && b < g.B && k < g.K;
     const size_t gi = (size_t)b * g.K + k;            // flattened (b, k)
+    ConflictLane cf;
+    if constexpr (CONF) cf.begin(*x, *fa, *fo, inside, b, k);
     int n = 0;
     if (inside && g.status[b] == 0) n = route_rows(g, b);
     const double *route = g.rows + (size_t)(inside ? b : 0) * (size_t)g.cap * 8;
@@ -252,6 +255,7 @@ __device__ __forceinline__ void pursuit_rollouts(const PursuitArgs &g, const Tra
             if (EXEC) pl.write_row(erow, r, g.dt);
             if (MODE == kTrackClear) acc.take(c->s, c->margin, pl, r);
             if (SPLIT) sl.put(ti, r - rbeg, tid, -track_wrap(pl.phi), pl.x, pl.y);
+            if constexpr (CONF) cf.take(*x, pl, r);
             // 4. arrival
             if (arrived < 0) {
                 const double ex = lastx - pl.x, ey = lasty - pl.y;
@@ -332,8 +336,13 @@ __device__ __forceinline__ void pursuit_rollouts(const PursuitArgs &g, const Tra
         if (SPLIT) __syncthreads();
     }
 
+    // kTrackConflict: the instants after the last executed row, the rollout parked at its pose
+    if constexpr (CONF) cf.tail(*x, my_total);
+
     // the final position error against the last point, and the rollout's outputs
     const bool have = mrow >= 0;
+    double cmin = INFINITY;
+    int crow = -1, cother = -1;
     if (inside) {
         if (g.stats) {
             double2 *o = (double2 *)(g.stats + gi * 6);
@@ -356,6 +365,7 @@ __device__ __forceinline__ void pursuit_rollouts(const PursuitArgs &g, const Tra
         rollout_outputs(g, gi, my_total, maxe, mrow);
         if (g.part_e) g.part_aux[gi] = arrived;
         if (MODE == kTrackClear || SPLIT) acc.store(*c, gi);
+        if constexpr (CONF) cf.finish(*x, gi, cmin, crow, cother);
     }
     if (g.wpr > 1) return;                              // the route's summary: k_pursuit_reduce
     if (producer) {
@@ -385,6 +395,14 @@ __device__ __forceinline__ void pursuit_rollouts(const PursuitArgs &g, const Tra
             cs.store(*c, b);
         }
     }
+    if constexpr (CONF) {                               // the conflict summary, over the same three columns
+        __syncthreads();
+        s_e[tid] = cmin;
+        s_r[tid] = crow;
+        s_a[tid] = cother;
+        __syncthreads();
+        if (inside && k == 0 && x->summary()) route_walk<ConflictSummary>(s_e + tid, s_r + tid, s_a + tid, g.K, x->margin).store(*x, b);
+    }
 }
 
 template <bool EXEC>
@@ -403,6 +421,13 @@ __global__ __launch_bounds__(kTrackThreads) void k_pursuit_clearance(PursuitArgs
 __global__ __launch_bounds__(kSplitThreads) void k_pursuit_clearance_split(PursuitArgs g, TrackClear c)
 {
     pursuit_rollouts<kTrackSplit>(g, &c);
+}
+
+// vap_rollout_conflicts: the same march, the clearance of every executed row to the partner's routes taken in the lane
+// that made it, and the parked instants after the march
+__global__ __launch_bounds__(kTrackThreads) void k_pursuit_conflicts(PursuitArgs g, TrackConflict x, ConfFoot fa, ConfFoot fo)
+{
+    pursuit_rollouts<kTrackConflict>(g, nullptr, &x, &fa, &fo);
 }
 
 int pursuit_setup(const RolloutCall &c, const vap_pursuit *f, PursuitArgs &g)
@@ -425,16 +450,17 @@ int pursuit_setup(const RolloutCall &c, const vap_pursuit *f, PursuitArgs &g)
     return VAP_OK;
 }
 
-int pursuit_launch(vap_ctx *ctx, PursuitArgs &g, TrackClear *clear)
+int pursuit_launch(vap_ctx *ctx, PursuitArgs &g, TrackClear *clear, ConflictCall *conf)
 {
     // context scratch: the routes' status words, then the partials
     long grid;
-    VAP_TRY(rollout_place(ctx, g, g.summary(), 2, (((size_t)g.B * sizeof(int)) + 15) & ~(size_t)15, clear, grid));
+    VAP_TRY(rollout_place(ctx, g, g.summary(), 2, (((size_t)g.B * sizeof(int)) + 15) & ~(size_t)15, clear, grid, conf ? &conf->x : nullptr));
     g.status = (int *)ctx->track_part.ptr;
     hipLaunchKernelGGL(k_pursuit_check, dim3((unsigned)g.B), dim3(kCheckThreads), 0, ctx->stream, g);
     return rollout_run<PursuitSummary>(ctx, g, clear, grid,
                                        RolloutKernels<PursuitArgs>{k_pursuit_rollouts<false>, k_pursuit_rollouts<true>, k_pursuit_clearance,
-                                                                   k_pursuit_clearance_split});
+                                                                   k_pursuit_clearance_split, k_pursuit_conflicts},
+                                       conf);
 }
 
 }  // namespace vap

@@ -2,7 +2,8 @@
 // RolloutCall from its parameters; the follower's *_setup checks its own struct and calls rollout_check for everything the
 // followers share (no device call up to here); rollout_place sizes the grid and the context scratch; rollout_run picks the
 // kernel of the mode and launches it with the reduce kernels K > 256 needs.  vap_tracking.hip and vap_pursuit.hip define
-// the *_setup / *_launch pairs below, so that vap_rollout_clearance and vap_odometry_rollouts run the same code.
+// the *_setup / *_launch pairs below, so that vap_rollout_clearance, vap_rollout_conflicts and vap_odometry_rollouts run the
+// same code.
 #pragma once
 #include <climits>
 #include <cmath>
@@ -63,9 +64,10 @@ int rollout_check(const RolloutCall &c, const char *who, const F &f, Args &g)
 
 // The launch shape (vap_track_common.h, the lane) and the context scratch: `head` bytes of the follower's own, then, for
 // K > 256 with a summary, the rollouts' partials [B][K] of a double and part_ints ints (1: the row; 2: a third column
-// too) rounded up to 16 bytes, then those of the clearance summary.  Fills g.R, g.wpr and the partials' pointers.
+// too) rounded up to 16 bytes, then those of the clearance summary or of the conflict summary.  Fills g.R, g.wpr and the
+// partials' pointers.
 template <class Args>
-int rollout_place(vap_ctx *ctx, Args &g, bool summary, int part_ints, size_t head, TrackClear *clear, long &grid)
+int rollout_place(vap_ctx *ctx, Args &g, bool summary, int part_ints, size_t head, TrackClear *clear, long &grid, TrackConflict *conf = nullptr)
 {
     const size_t np = (size_t)g.B * (size_t)g.K;
     size_t part_bytes = 0, clear_bytes = 0;
@@ -78,7 +80,7 @@ int rollout_place(vap_ctx *ctx, Args &g, bool summary, int part_ints, size_t hea
         g.wpr = (g.K + kTrackThreads - 1) / kTrackThreads;
         grid = (long)g.B * g.wpr;
         if (summary) part_bytes = (np * (sizeof(double) + (size_t)part_ints * sizeof(int)) + 15) & ~(size_t)15;
-        if (clear && clear->summary()) clear_bytes = np * (sizeof(double) + 2 * sizeof(int));
+        if ((clear && clear->summary()) || (conf && conf->summary())) clear_bytes = np * (sizeof(double) + 2 * sizeof(int));
     }
     if (grid > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "%d routes x %d rollouts: too many workgroups for one launch", g.B, g.K);
     if (head + part_bytes + clear_bytes) VAP_TRY(ctx->ensure(ctx->track_part, head + part_bytes + clear_bytes));
@@ -88,10 +90,15 @@ int rollout_place(vap_ctx *ctx, Args &g, bool summary, int part_ints, size_t hea
         g.part_row = (int *)(g.part_e + np);
         if (part_ints > 1) g.part_aux = g.part_row + np;
     }
-    if (clear_bytes) {
+    if (clear_bytes && clear) {
         clear->part_c = (double *)(base + part_bytes);
         clear->part_row = (int *)(clear->part_c + np);
         clear->part_el = clear->part_row + np;
+    }
+    if (clear_bytes && conf) {
+        conf->part_c = (double *)(base + part_bytes);
+        conf->part_row = (int *)(conf->part_c + np);
+        conf->part_o = conf->part_row + np;
     }
     return VAP_OK;
 }
@@ -124,25 +131,60 @@ inline bool rollout_split(vap_ctx *ctx, const TrackClear *clear, long grid)
     return clear && grid <= track_cus(ctx->device);
 }
 
-// a follower's kernels, one per mode (kTrackPlain, kTrackExec, kTrackClear, kTrackSplit)
+// vap_rollout_conflicts on the host: the kernel block and the two footprints that travel beside it
+struct ConflictCall {
+    TrackConflict x;
+    ConfFoot fa, fo;
+};
+
+// a follower's kernels, one per mode (kTrackPlain, kTrackExec, kTrackClear, kTrackSplit, kTrackConflict)
 template <class Args>
 struct RolloutKernels {
     void (*plain)(Args);
     void (*exec)(Args);
     void (*clear)(Args, TrackClear);
     void (*split)(Args, TrackClear);
+    void (*conflict)(Args, TrackConflict, ConfFoot, ConfFoot);
 };
+
+// The conflict kernels keep a rollout lane's state per partner in dynamic LDS, 4 KiB per partner.  With the kernel's own
+// static LDS up to 64 KiB every device launches it as it is; above, the request has to fit the device's workgroup limit
+// and is put to the runtime first.  Refused here, before anything is launched.
+template <class Kernel>
+int conflict_grant_lds(vap_ctx *ctx, Kernel kernel, int Bo, size_t dyn)
+{
+    hipFuncAttributes attr;
+    HIP_TRY(hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kernel)));
+    const size_t need = dyn + attr.sharedSizeBytes;
+    if (need <= 64 * 1024) return VAP_OK;
+    int lds_max = 0;
+    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess) lds_max = 0;
+    const size_t avail = lds_max > 64 * 1024 ? (size_t)lds_max : (size_t)64 * 1024;
+    if (need > avail)
+        return vap_fail(VAP_ERR_UNSUPPORTED, "rollout conflicts against Bo=%d routes need %zu bytes of LDS; the device gives a workgroup %zu",
+                        Bo, need, avail);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+    if (e != hipSuccess)
+        return vap_fail(VAP_ERR_UNSUPPORTED, "rollout conflicts against Bo=%d routes need %zu bytes of LDS; the device gives a workgroup %zu "
+                        "and the request was not granted (%s)", Bo, need, avail, hipGetErrorString(e));
+    return VAP_OK;
+}
 
 // Enqueues the rollouts of a placed launch and the reduce kernels.  With `clear` the rollouts take the clearance of their
 // executed rows (no executed rows are written then): split off the rollout lanes where every workgroup gets a CU of its own
 // (K = 16 at config 3: one rollout wave per SIMD, which cannot hide the clearance's loads); with more workgroups than CUs
 // the lanes' own clearance, several workgroups to a CU, measured faster
+// With `conf` (and no `clear`) they take the clearance to the partner's routes instead, a lane per rollout.
 template <class Summary, class Args>
-int rollout_run(vap_ctx *ctx, Args &g, TrackClear *clear, long grid, const RolloutKernels<Args> &kn)
+int rollout_run(vap_ctx *ctx, Args &g, TrackClear *clear, long grid, const RolloutKernels<Args> &kn, ConflictCall *conf = nullptr)
 {
     const dim3 blocks((unsigned)grid);
     const auto rollouts = g.exec_rows ? kn.exec : kn.plain;
-    if (rollout_split(ctx, clear, grid)) {
+    if (conf) {
+        const size_t dyn = conflict_lds_bytes(conf->x.p.o.B);
+        VAP_TRY(conflict_grant_lds(ctx, kn.conflict, conf->x.p.o.B, dyn));
+        hipLaunchKernelGGL(kn.conflict, blocks, dim3(kTrackThreads), dyn, ctx->stream, g, conf->x, conf->fa, conf->fo);
+    } else if (rollout_split(ctx, clear, grid)) {
         hipLaunchKernelGGL(kn.split, blocks, dim3(kSplitThreads), 0, ctx->stream, g, *clear);
     } else if (clear)
         hipLaunchKernelGGL(kn.clear, blocks, dim3(kTrackThreads), 0, ctx->stream, g, *clear);
@@ -152,6 +194,9 @@ int rollout_run(vap_ctx *ctx, Args &g, TrackClear *clear, long grid, const Rollo
     if (clear && clear->part_c)
         hipLaunchKernelGGL((k_route_reduce<ClearSummary, TrackClear>), dim3((unsigned)((g.B + 63) / 64)), dim3(64), 0, ctx->stream, *clear,
                            g.B, g.K, (const double *)clear->part_c, (const int *)clear->part_row, (const int *)clear->part_el, clear->margin);
+    if (conf && conf->x.part_c)
+        hipLaunchKernelGGL((k_route_reduce<ConflictSummary, TrackConflict>), dim3((unsigned)((g.B + 63) / 64)), dim3(64), 0, ctx->stream, conf->x,
+                           g.B, g.K, (const double *)conf->x.part_c, (const int *)conf->x.part_row, (const int *)conf->x.part_o, conf->x.margin);
     HIP_TRY(hipGetLastError());
     return VAP_OK;
 }
@@ -159,8 +204,8 @@ int rollout_run(vap_ctx *ctx, Args &g, TrackClear *clear, long grid, const Rollo
 // The two followers' calls in two halves: *_setup checks the host arguments (no device call) and fills the kernel arguments;
 // *_launch sizes the grid and the context scratch and enqueues the kernels.
 int tracking_setup(const RolloutCall &c, const vap_follower *f, TrackArgs &g);
-int tracking_launch(vap_ctx *ctx, TrackArgs &g, TrackClear *clear);
+int tracking_launch(vap_ctx *ctx, TrackArgs &g, TrackClear *clear, ConflictCall *conf = nullptr);
 int pursuit_setup(const RolloutCall &c, const vap_pursuit *f, PursuitArgs &g);
-int pursuit_launch(vap_ctx *ctx, PursuitArgs &g, TrackClear *clear);
+int pursuit_launch(vap_ctx *ctx, PursuitArgs &g, TrackClear *clear, ConflictCall *conf = nullptr);
 
 }  // namespace vap

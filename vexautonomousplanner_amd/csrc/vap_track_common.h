@@ -1,5 +1,6 @@
 // vap_track_common.h — the device side of the closed-loop rollouts (vap_tracking.hip: RAMSETE; vap_pursuit.hip: pure
-// pursuit; vap_odometry.hip: RAMSETE on an estimate; vap_rollout_clearance.hip: two further modes of the first two).
+// pursuit; vap_odometry.hip: RAMSETE on an estimate; vap_rollout_clearance.hip: two further modes of the first two;
+// vap_rollout_conflicts.hip: one more).
 // A follower file holds its march, its statistics and its kernels; everything around the march is here, once (pure pursuit
 // keeps its own lane mapping, record parsing, split schedule and summary walk, see PursuitArgs):
 //   1. the plant           the angle wrap, sinc, the saturation, TrackPlant
@@ -9,12 +10,14 @@
 //                          perturbation record and the plant's start state (PlantRecord)
 //   4. the row stage       RowStage: the routes' rows in double-buffered LDS tiles
 //   5. the clearance       ClearAcc, and SplitLds: the clearance split off the rollout lanes (kTrackSplit)
+//                          ConflictLane: a rollout's clearance to the partner's routes (kTrackConflict; TrackConflict)
 //   6. the outputs         a rollout's common outputs, the fixed-order summaries of a route's rollouts (TrackSummary,
-//                          ClearSummary), the walk over them (route_walk) in LDS or, for K > 256, in k_route_reduce
+//                          ClearSummary, ConflictSummary), the walk over them (route_walk) in LDS or, for K > 256, in k_route_reduce
 // The host side (the argument checks, the grid, the launches) is vap_rollout_host.h.
 #pragma once
 #include <cmath>
 
+#include "vap_conflict.h"
 #include "vap_footprint.h"
 
 namespace vap {
@@ -144,8 +147,9 @@ struct PursuitArgs {
 };
 
 // What a rollout kernel does with the executed row r (include/vap.h, step 3): nothing, write it, take its scene clearance
-// while the pose is in registers, or hand the pose to further lanes of the workgroup that take it (vap_rollout_clearance).
-enum { kTrackPlain = 0, kTrackExec = 1, kTrackClear = 2, kTrackSplit = 3 };
+// while the pose is in registers, or hand the pose to further lanes of the workgroup that take it (vap_rollout_clearance);
+// or take its clearance to the partner's routes at the same instant (vap_rollout_conflicts).
+enum { kTrackPlain = 0, kTrackExec = 1, kTrackClear = 2, kTrackSplit = 3, kTrackConflict = 4 };
 
 // vap_rollout_clearance: the scene, the margin and the clearance outputs beside a follower's own arguments.
 struct TrackClear {
@@ -159,6 +163,31 @@ struct TrackClear {
     int *part_row, *part_el;
     __host__ __device__ bool summary() const { return worst || mean || worst_rollout || worst_row || worst_element || n_colliding || n_valid; }
 };
+
+// vap_rollout_conflicts: the partner's routes (side O, packed once with shift 0), the two footprints' call constants, the
+// shifts and the conflict outputs beside a follower's own arguments.  The footprints' vertex tables travel beside it.
+constexpr int kConflictOthersMax = 16;     // VAP_ROLLOUT_CONFLICT_OTHERS_MAX
+constexpr long kConflictShiftMax = 1L << 24;
+struct TrackConflict {
+    ConfPacked p;             // pack_o, Tpo, o (counts, Bo), slack, cull; side A is the rollout lanes'
+    double fcx, fcy, radii;   // footprint A's bounding-circle centre in the body frame; R_a + R_o
+    int na, no;               // vertices of the two footprints
+    long shift;               // the host's shift_rows
+    const int *route_shift, *rollout_shift;   // [B], [K] or NULL
+    double margin;
+    double *pair_c;           // [B][K][Bo]
+    int *pair_rows;           // [B][K][Bo][2] = first row at the minimum, first row below the margin
+    double *conflict;         // [B][K]
+    int *conflict_rows;       // [B][K][4] = other at the minimum, its row, pairs below the margin, earliest first row
+    double *worst, *mean;     // [B]
+    int *worst_rollout, *worst_other, *worst_row, *n_conflicting, *n_valid;
+    double *part_c;           // K > 256: [B][K] conflict clearance (row < 0: takes no part)
+    int *part_row, *part_o;
+    __host__ __device__ bool summary() const { return worst || mean || worst_rollout || worst_other || worst_row || n_conflicting || n_valid; }
+};
+
+// dynamic LDS of a conflict kernel: a rollout lane's (minimum, its row, first row below the margin) per partner
+inline size_t conflict_lds_bytes(int Bo) { return (size_t)Bo * kTrackThreads * (sizeof(double) + 2 * sizeof(int)); }
 
 // RAMSETE's command from the reference (v_r, omega_r) and the errors in the body frame, before the saturation
 __device__ __forceinline__ void ramsete_command(const TrackArgs &g, double vr, double wref, double ex, double ey, double eph, double &cl, double &cr)
@@ -434,6 +463,134 @@ struct SplitLds {
     }
 };
 
+// The clearance of a rollout to the partner's routes (kTrackConflict), by vap_footprint_conflicts' rules for the pairs
+// (this rollout's executed rows, partner o), o = 0 .. Bo - 1, side O starting s rows late: at horizon row r the partner is
+// at its row clamp(r - s, 0, n_o - 1), and the pair is examined up to T = max(n_a, n_o + s, 1).  The lane forms its packed
+// pose with the pack kernel's own function (conf_pose) and reads O's packed rows, so every clearance has the bits the pair
+// of calls computes.  Per partner the lane keeps (minimum, first row at it, first row below the margin) in dynamic LDS,
+// [o][lane]: rows ascend in a lane, so a strictly smaller value replaces and nothing is tie-broken across lanes.  A row is
+// culled against the pair's own threshold as k_conflict_pairs forms it.
+struct ConflictLane {
+    const double *sfa, *sfo;  // LDS: the footprints' vertex tables
+    const int *no_rows;       // LDS [Bo]: the partners' counts
+    double *best;             // LDS [Bo][kTrackThreads]
+    int *row, *first;
+    long s = 0;               // this rollout's shift
+    double ax = 0.0, ay = 0.0, ac = 1.0, as = 0.0;      // the packed pose of the last executed row
+
+    // every thread of the workgroup; ends behind a barrier.  (b, k): the lane's rollout, read where `inside`
+    __device__ __forceinline__ void begin(const TrackConflict &x, const ConfFoot &fa, const ConfFoot &fo, bool inside, int b, int k)
+    {
+        extern __shared__ __attribute__((aligned(16))) double s_conflict[];
+        __shared__ double s_fa[kFootMaxVerts * 8], s_fo[kFootMaxVerts * 8];
+        __shared__ int s_no[kConflictOthersMax];
+        const int tid = threadIdx.x, Bo = x.p.o.B;
+        sfa = s_fa, sfo = s_fo, no_rows = s_no;
+        best = s_conflict + tid;
+        row = (int *)(s_conflict + (size_t)Bo * kTrackThreads) + tid;
+        first = row + (size_t)Bo * kTrackThreads;
+        if (tid < kFootMaxVerts * 8) {
+            s_fa[tid] = fa.v[tid];
+            s_fo[tid] = fo.v[tid];
+        }
+        if (tid < Bo) s_no[tid] = (int)conf_count(x.p.o, tid);
+#pragma unroll 1
+        for (int o = 0; o < Bo; o++) {
+            best[o * kTrackThreads] = INFINITY;
+            row[o * kTrackThreads] = -1;
+            first[o * kTrackThreads] = -1;
+        }
+        if (inside) {
+            s = x.shift;
+            if (x.route_shift) s += clampl(x.route_shift[b], -kConflictShiftMax, kConflictShiftMax);
+            if (x.rollout_shift) s += clampl(x.rollout_shift[k], -kConflictShiftMax, kConflictShiftMax);
+        }
+        __syncthreads();
+    }
+    // horizon row r of the pair with partner o, the lane's own pose being (ax, ay, ac, as)
+    __device__ __forceinline__ void pair(const TrackConflict &x, int o, long r)
+    {
+        const long n_o = no_rows[o];
+        if (n_o <= 0) return;                               // an invalid pair
+        const double *q = x.p.pack_o + ((size_t)o * (size_t)x.p.Tpo + (size_t)clampl(r - s, 0, n_o - 1)) * 4;
+        const double2 o01 = *(const double2 *)q;
+        const double bo = best[o * kTrackThreads];
+        const int fo = first[o * kTrackThreads];
+        if (x.p.cull && row_culled(x.p, x.radii, fo >= 0 ? bo : fmax(bo, x.margin), ax, ay, o01.x, o01.y)) return;
+        const double2 o23 = *(const double2 *)(q + 2);
+        const double c = pair_clearance(sfa, x.na, sfo, x.no, ax, ay, ac, as, o01.x, o01.y, o23.x, o23.y);
+        if (c == c) {                                       // a NaN clearance takes part in nothing
+            if (c < x.margin && fo < 0) first[o * kTrackThreads] = (int)r;
+            if (c < bo) {
+                best[o * kTrackThreads] = c;
+                row[o * kTrackThreads] = (int)r;
+            }
+        }
+    }
+    // executed row r: the pose is what TrackPlant::write_row stores, heading = -wrap(phi), x, y
+    __device__ __forceinline__ void take(const TrackConflict &x, const TrackPlant &pl, int r)
+    {
+        conf_pose(-track_wrap(pl.phi), pl.x, pl.y, x.fcx, x.fcy, ax, ay, ac, as);
+#pragma unroll 1
+        for (int o = 0; o < x.p.o.B; o++) pair(x, o, r);
+    }
+    // The instants after the rollout's last executed row n_a - 1, at whose pose it stays parked, per partner up to n_o + s.
+    // While the partner has not started either (rows in [n_a, s)) nothing moves: the stretch's first row stands for it.
+    // So the loop takes at most n_o + 1 rows, whatever s is.  No barriers.
+    __device__ __forceinline__ void tail(const TrackConflict &x, int n_a)
+    {
+        if (n_a <= 0) return;
+#pragma unroll 1
+        for (int o = 0; o < x.p.o.B; o++) {
+            const long T = (long)no_rows[o] + s;
+            long r = n_a;
+            if (no_rows[o] <= 0 || r >= T) continue;
+            if (s > r) {
+                pair(x, o, r);
+                r = s;
+            }
+#pragma unroll 1
+            for (; r < T; r++) pair(x, o, r);
+        }
+    }
+    // the walk over the partners in ascending o (a strictly smaller minimum replaces: the smallest o stays), the outputs of
+    // rollout gi, and (minimum, its row, its partner) for the route's summary
+    __device__ __forceinline__ void finish(const TrackConflict &x, size_t gi, double &cmin, int &crow, int &cother) const
+    {
+        const int Bo = x.p.o.B;
+        double m = INFINITY;
+        int other = -1, mrow = -1, ncon = 0, f0 = -1;
+#pragma unroll 1
+        for (int o = 0; o < Bo; o++) {
+            const double bo = best[o * kTrackThreads];
+            const int ro = row[o * kTrackThreads], fo = first[o * kTrackThreads];
+            if (x.pair_c) x.pair_c[gi * Bo + o] = ro >= 0 ? bo : NAN;
+            if (x.pair_rows) {
+                x.pair_rows[(gi * Bo + o) * 2] = ro;
+                x.pair_rows[(gi * Bo + o) * 2 + 1] = fo;
+            }
+            if (ro < 0) continue;
+            if (bo < m) { m = bo; other = o; mrow = ro; }
+            ncon += bo < x.margin ? 1 : 0;
+            if (fo >= 0 && (f0 < 0 || fo < f0)) f0 = fo;
+        }
+        if (x.conflict) x.conflict[gi] = other >= 0 ? m : NAN;
+        if (x.conflict_rows) {
+            int *q = x.conflict_rows + gi * 4;
+            q[0] = other;
+            q[1] = mrow;
+            q[2] = ncon;
+            q[3] = f0;
+        }
+        if (x.part_c) {
+            x.part_c[gi] = m;
+            x.part_row[gi] = mrow;
+            x.part_o[gi] = other;
+        }
+        cmin = m, crow = mrow, cother = other;
+    }
+};
+
 // ---- 6. the outputs -----------------------------------------------------------------------------------------------------
 // what every follower writes per rollout beside its own statistics: the executed rows' count and, for K > 256, the
 // summary's partials
@@ -497,6 +654,20 @@ struct ClearSummary {
         if (c.worst_element) c.worst_element[b] = k >= 0 ? el : -1;
         if (c.n_colliding) c.n_colliding[b] = ncol;
         if (c.n_valid) c.n_valid[b] = cnt;
+    }
+};
+
+// vap_rollout_conflicts' route summary: ClearSummary's walk, the third column being the partner at the minimum
+struct ConflictSummary : ClearSummary {
+    __device__ void store(const TrackConflict &x, int b) const
+    {
+        if (x.worst) x.worst[b] = cnt ? worst : NAN;
+        if (x.mean) x.mean[b] = cnt ? sum / (double)cnt : NAN;
+        if (x.worst_rollout) x.worst_rollout[b] = k;
+        if (x.worst_other) x.worst_other[b] = k >= 0 ? el : -1;
+        if (x.worst_row) x.worst_row[b] = row;
+        if (x.n_conflicting) x.n_conflicting[b] = ncol;
+        if (x.n_valid) x.n_valid[b] = cnt;
     }
 };
 

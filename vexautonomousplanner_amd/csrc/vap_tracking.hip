@@ -23,23 +23,28 @@
 //            (k_tracking_rollouts<false / true>), or with the scene clearance of every executed row taken where it would
 //            be written (k_tracking_clearance) or by further lanes of the workgroup a tile later
 //            (k_tracking_clearance_split, SplitLds); the last two for vap_rollout_clearance.hip, through tracking_setup /
-//            tracking_launch.
+//            tracking_launch.  k_tracking_conflicts takes, at the same place, the row's clearance to the partner's routes
+//            (ConflictLane) for vap_rollout_conflicts.hip.
 #include "vap_rollout_host.h"
 
 namespace vap {
 
 // The rollouts of one workgroup.  MODE: what becomes of the executed row (kTrackPlain, kTrackExec, kTrackClear,
-// kTrackSplit); `c` is read with the last two only.
+// kTrackSplit, kTrackConflict); `c` is read with kTrackClear and kTrackSplit only, `x` and the footprints with kTrackConflict.
 template <int MODE>
-__device__ __forceinline__ void tracking_rollouts(const TrackArgs &g, const TrackClear *c)
+__device__ __forceinline__ void tracking_rollouts(const TrackArgs &g, const TrackClear *c, const TrackConflict *x = nullptr,
+                                                  const ConfFoot *fa = nullptr, const ConfFoot *fo = nullptr)
 {
     constexpr bool EXEC = MODE == kTrackExec, SPLIT = MODE == kTrackSplit, CLEAR = MODE == kTrackClear || SPLIT;
+    constexpr bool CONF = MODE == kTrackConflict;
     const int tid = threadIdx.x;
     const int R = g.R, tile = g.tile;
     const bool producer = !SPLIT || tid < kTrackThreads;     // SPLIT: the threads behind the rollout lanes take clearances
     SplitLds sl;
     if constexpr (SPLIT) sl.begin();
     const RolloutLane ln(g, producer);
+    ConflictLane cf;
+    if constexpr (CONF) cf.begin(*x, *fa, *fo, ln.inside, ln.b, ln.k);
     RowStage st;
     st.begin(g, ln.b0, producer);
     const int wg_total = st.total;
@@ -94,6 +99,7 @@ __device__ __forceinline__ void tracking_rollouts(const TrackArgs &g, const Trac
                 if (EXEC) pl.write_row(erow, r, g.dt);
                 if (MODE == kTrackClear) acc.take(c->s, c->margin, pl, r);
                 if (SPLIT) sl.put(ti, t, tid, -track_wrap(pl.phi), pl.x, pl.y);
+                if constexpr (CONF) cf.take(*x, pl, r);
                 // 4. RAMSETE, 5. saturation, keeping c_L : c_R
                 double cl, cr;
                 ramsete_command(g, vr, wref, ex, ey, eph, cl, cr);
@@ -106,8 +112,13 @@ __device__ __forceinline__ void tracking_rollouts(const TrackArgs &g, const Trac
         __syncthreads();
     }
 
+    // kTrackConflict: the instants after the last executed row, the rollout parked at its pose
+    if constexpr (CONF) cf.tail(*x, my_total);
+
     // 7. final errors against row n - 1, and the rollout's outputs
     const bool have = mrow >= 0;
+    double cmin = INFINITY;
+    int crow = -1, cother = -1;
     if (ln.inside) {
         double fpos = NAN, fphi = NAN;
         if (have) {
@@ -127,6 +138,7 @@ __device__ __forceinline__ void tracking_rollouts(const TrackArgs &g, const Trac
         }
         rollout_outputs(g, gi, my_total, maxe, mrow);
         if (CLEAR) acc.store(*c, gi);
+        if constexpr (CONF) cf.finish(*x, gi, cmin, crow, cother);
     }
     if (g.wpr > 1) return;                              // the route's summary: k_route_reduce
     // the route's summary inside the workgroup: the stage buffers are free (the last barrier is behind every thread)
@@ -145,8 +157,15 @@ __device__ __forceinline__ void tracking_rollouts(const TrackArgs &g, const Trac
         s_cr[tid] = ln.inside ? acc.row : -1;
         s_ce[tid] = acc.el;
     }
+    if (CONF && producer) {
+        s_c[tid] = cmin;
+        s_cr[tid] = crow;
+        s_ce[tid] = cother;
+    }
     __syncthreads();
     route_summary<TrackSummary>(g, ln, g.K, s_e, s_r, nullptr, g.tol);
+    if constexpr (CONF)
+        if (x->summary()) route_summary<ConflictSummary>(*x, ln, g.K, s_c, s_cr, s_ce, x->margin);
     if (CLEAR && c->summary()) route_summary<ClearSummary>(*c, ln, g.K, s_c, s_cr, s_ce, c->margin);
 }
 
@@ -183,14 +202,22 @@ int tracking_setup(const RolloutCall &c, const vap_follower *f, TrackArgs &g)
     return VAP_OK;
 }
 
-int tracking_launch(vap_ctx *ctx, TrackArgs &g, TrackClear *clear)
+// vap_rollout_conflicts: the same march, the clearance of every executed row to the partner's routes taken in the lane
+// that made it, and the parked instants after the march
+__global__ __launch_bounds__(kTrackThreads) void k_tracking_conflicts(TrackArgs g, TrackConflict x, ConfFoot fa, ConfFoot fo)
+{
+    tracking_rollouts<kTrackConflict>(g, nullptr, &x, &fa, &fo);
+}
+
+int tracking_launch(vap_ctx *ctx, TrackArgs &g, TrackClear *clear, ConflictCall *conf)
 {
     long grid;
-    VAP_TRY(rollout_place(ctx, g, g.summary(), 1, 0, clear, grid));
+    VAP_TRY(rollout_place(ctx, g, g.summary(), 1, 0, clear, grid, conf ? &conf->x : nullptr));
     g.tile = stage_tile(g.R, rollout_split(ctx, clear, grid));
     return rollout_run<TrackSummary>(ctx, g, clear, grid,
                                      RolloutKernels<TrackArgs>{k_tracking_rollouts<false>, k_tracking_rollouts<true>, k_tracking_clearance,
-                                                               k_tracking_clearance_split});
+                                                               k_tracking_clearance_split, k_tracking_conflicts},
+                                     conf);
 }
 
 }  // namespace vap

@@ -238,7 +238,8 @@ def _sigma0(sigma0, R, W, pinned, pin_ends):
 
 def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS, samples=None, dd=None, dt=0.01,
            capacity_rows=None, others=None, others_footprint=None, follower=None, perturbations=None, config=None,
-           pinned=None, pin_ends=True, capacity=None, first_problem=0, curve_caps=None, robust_clearance=False):
+           pinned=None, pin_ends=True, capacity=None, first_problem=0, curve_caps=None, robust_clearance=False,
+           robust_conflicts=False, others_shift_rows=0, others_start_jitter=None):
     """Refine R routes by cross-entropy search on ``gen``'s device (a BatchedTrajectoryGenerator; its dtype is the
     waypoints').
 
@@ -260,6 +261,15 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
                      and the worst clearance of its disturbed rollouts (the planned one alone where no rollout has rows),
                      so a route that clears the scene only when driven perfectly is no longer feasible.  The tracking term
                      is unchanged.  False: the sequence without it
+      others_shift_rows   the partner starts that many rows late (any sign): passed to ``footprint.conflicts`` and to the
+                     rollouts of ``robust_conflicts`` alike
+      robust_conflicts   needs ``follower`` and ``others``: every iteration runs ``tracking.rollout_conflicts`` (where it ran
+                     ``tracking.rollouts``; beside ``tracking.rollout_clearance`` with ``robust_clearance`` too, so the
+                     rollouts then run twice), and a candidate's conflict term is the smaller of its planned rows' conflict
+                     clearance and the worst of its disturbed rollouts (the planned one alone where no rollout has a valid
+                     pair), so a route that passes the partner only when driven perfectly is no longer feasible
+      others_start_jitter   with ``robust_conflicts``: (K,) int rows, rollout k meets a partner that starts
+                     others_shift_rows + jitter[k] rows late (``rollout_shift``)
       config         a SearchConfig
       curve_caps     a drive.CurveCaps: every iteration's velocity rows are recomputed under these caps
                      (``gen.apply_curve_caps``) between ``profile`` and ``time_profile``; None: the sequence without it
@@ -282,6 +292,15 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
         raise ValueError("follower needs perturbations (tracking.sample_perturbations)")
     if robust_clearance and follower is None:
         raise ValueError("robust_clearance needs a follower (and perturbations): it scores the rollouts' clearance")
+    if robust_conflicts and follower is None:
+        raise ValueError("robust_conflicts needs a follower (and perturbations): it scores the rollouts' clearance to the partner")
+    if robust_conflicts and others is None:
+        raise ValueError("robust_conflicts needs others: the partner's routines the rollouts are checked against")
+    if others_start_jitter is not None and not robust_conflicts:
+        raise ValueError("others_start_jitter is the rollouts' start jitter: it needs robust_conflicts=True")
+    if int(others_shift_rows) != others_shift_rows:
+        raise ValueError(f"others_shift_rows must be an int (got {others_shift_rows!r})")
+    others_shift_rows = int(others_shift_rows)
     dev = gen.device
     s = np.asarray(seeds.detach().cpu().numpy() if isinstance(seeds, torch.Tensor) else seeds, dtype=np.float64)
     if s.ndim == 2:
@@ -301,7 +320,7 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
     n_feas = torch.zeros((iters, R), dtype=torch.int32, device=dev)
     if perturbations is not None and not isinstance(perturbations, torch.Tensor):
         perturbations = torch.as_tensor(np.ascontiguousarray(perturbations, dtype=np.float64), device=dev)
-    prof, tp, clr, conf, trk, upd = None, {}, {}, {}, {}, {}
+    prof, tp, clr, conf, trk, upd, rcf = None, {}, {}, {}, {}, {}, {}
     pursuit = isinstance(follower, tracking.Pursuit)
     inf = torch.full((), float("inf"), dtype=torch.float64, device=dev)
     kw = {"samples": samples} if samples is not None else {"dd": dd, "capacity": capacity}
@@ -316,14 +335,22 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
         terms = {"clearance": clr["min_clearance"]}
         if others is not None:
             fp.conflicts(tp["rows"], tp["counts"], footprint, others["rows"], others["counts"], others_footprint,
-                         margin=wts.conflict_margin, out=conf, ctx=gen.ctx)
+                         margin=wts.conflict_margin, shift_rows=others_shift_rows, out=conf, ctx=gen.ctx)
             terms["conflict_clearance"] = conf["min_clearance"]
+        if robust_conflicts:
+            tracking.rollout_conflicts(tp["rows"], tp["counts"], follower, perturbations, footprint, others["rows"], others["counts"],
+                                       others_footprint, margin=wts.conflict_margin, shift_rows=others_shift_rows,
+                                       rollout_shift=others_start_jitter, time_step=dt, out=rcf, ctx=gen.ctx)
+            wc = rcf["worst_conflict"]
+            terms["conflict_clearance"] = torch.where(torch.isnan(wc), conf["min_clearance"], torch.minimum(conf["min_clearance"], wc))
+            if not robust_clearance:
+                trk = rcf                                  # the follower's own outputs are those of its plain call
         if robust_clearance:
             tracking.rollout_clearance(tp["rows"], tp["counts"], follower, perturbations, footprint, scene,
                                        margin=wts.clearance_margin, time_step=dt, out=trk, ctx=gen.ctx)
             wc = trk["worst_clearance"]
             terms["clearance"] = torch.where(torch.isnan(wc), clr["min_clearance"], torch.minimum(clr["min_clearance"], wc))
-        elif follower is not None:
+        elif follower is not None and not robust_conflicts:
             tracking.rollouts(tp["rows"], tp["counts"], follower, perturbations, time_step=dt, out=trk, ctx=gen.ctx)
         if follower is not None:
             # a pure-pursuit candidate whose rollouts do not all arrive is never an elite: its tracking term is +inf
@@ -339,4 +366,6 @@ def refine(gen, seeds, sigma0, footprint, scene, constraints=DEFAULT_CONSTRAINTS
         out["n_unfinished"] = trk["n_unfinished"].view(R, N)
     if robust_clearance:
         out["n_colliding"] = trk["n_colliding"].view(R, N)
+    if robust_conflicts:
+        out["n_conflicting"] = rcf["n_conflicting"].view(R, N)
     return out

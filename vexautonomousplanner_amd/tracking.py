@@ -317,3 +317,99 @@ def rollout_clearance(rows, counts, follower, perturbations, footprint, scene, m
     for i, name in enumerate(CLEAR_ROW_COLUMNS):
         res[name] = res["clear_rows"][..., i]
     return _single(res) if single else res
+
+
+CONFLICT_ROW_COLUMNS = ("conflict_other", "conflict_row", "conflict_n", "conflict_first_row")
+CONFLICT_OTHERS_MAX = 16
+CONFLICT_SHIFT_MAX = 1 << 24
+
+
+def _shift_array(a, n, name, dev):
+    """A per-route or per-rollout start shift as an (n,) int32 tensor on ``dev``; None stays None."""
+    if a is None:
+        return None
+    if not isinstance(a, torch.Tensor):
+        a = np.asarray(a)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"{name} must be integer rows (got dtype {a.dtype})")
+    elif a.dtype.is_floating_point or a.dtype == torch.bool:
+        raise ValueError(f"{name} must be integer rows (got dtype {a.dtype})")
+    if tuple(a.shape) != (n,):
+        raise ValueError(f"{name} must be ({n},), got {tuple(a.shape)}")
+    return device_array(a, dev, torch.int32)
+
+
+def rollout_conflicts(rows, counts, follower, perturbations, footprint, others_rows, others_counts, others_footprint=None,
+                      margin=0.0, shift_rows=0, route_shift=None, rollout_shift=None, pairs=False, time_step=0.01, out=None,
+                      device=0, ctx=None, cull=True):
+    """Clearance of the disturbed rollouts to the partner's routines (vap_rollout_conflicts): does a disturbed run still
+    miss my partner, whose start time is as uncertain as my own drive?  ``rollouts(executed=True)`` followed by
+    ``footprint.conflicts`` answers that through every executed row in memory, packed a second time, one conflicts call
+    per distinct shift; this call runs the same rollouts and takes the clearance to every partner route while the
+    executed row is on the chip.  No executed rows exist.
+
+      rows, counts, follower, perturbations, time_step   as in ``rollouts`` (a Follower or a Pursuit)
+      footprint                     my robot's (n, 2) body-frame polygon, counter-clockwise
+      others_rows, others_counts    side O as in ``footprint.conflicts``: (Bo, cap_o, 8) rows with (Bo, k) / (Bo,) counts, or
+                                    one (n, 8) trajectory with counts None; 1 .. 16 routes, on the same time step
+      others_footprint              side O's robot; None = the same as mine
+      margin                        a pair whose clearance is below it conflicts
+      shift_rows, route_shift, rollout_shift   side O starts shift_rows + route_shift[b] + rollout_shift[k] rows late for
+                                    rollout (b, k): an int within +-2^24, (B,) ints or None, (K,) ints (shared by all
+                                    routes) or None; the array entries are clamped into +-2^24
+      pairs                         also return pair_clearance (B, K, Bo) and pair_rows (B, K, Bo, 2) = the first row at the
+                                    pair's minimum, its first row below ``margin``
+      out, ctx, cull                as in ``rollout_clearance``
+    Returns everything ``rollouts`` returns for that follower (the same bits), and: conflict (B, K), the smallest clearance
+    over the rollout's pairs and instants; conflict_rows (B, K, 4) with views conflict_other (the smallest o there),
+    conflict_row, conflict_n (pairs below ``margin``), conflict_first_row (the earliest row any pair goes below it, -1:
+    none); per route (B,) worst_conflict (the smallest over k; the smallest k on a tie), worst_conflict_rollout,
+    worst_conflict_other, worst_conflict_row, mean_conflict, n_conflicting (rollouts below ``margin``) and n_conflict_valid.
+    Per rollout these are the numbers ``footprint.conflicts`` gives for that executed route of ``rollouts(executed=True)``
+    at that rollout's shift, bit for bit: instants run to max(n_a, n_o + s, 1), each robot parked at its first or last pose
+    outside its own rows.  A rollout without rows gives NaN / -1 / 0, a route without one NaN / -1 / 0 / 0.  A single
+    trajectory gives (K, ...) and 0-d tensors.  Work runs on torch's current stream and is not synchronised."""
+    from . import footprint as fp
+    pursuit, time_step = _checked(follower, time_step)
+    foot_a, foot_o = fp._two_footprints(footprint, others_footprint, "all", names=("footprint", "others_footprint"))
+    margin = float(margin)
+    if not np.isfinite(margin):
+        raise ValueError(f"margin must be finite (got {margin!r})")
+    if int(shift_rows) != shift_rows or abs(int(shift_rows)) > CONFLICT_SHIFT_MAX:
+        raise ValueError(f"shift_rows must be an int within +-{CONFLICT_SHIFT_MAX} (got {shift_rows!r})")
+    shift_rows = int(shift_rows)
+    rows, counts, single, dev = time_rows(rows, counts, None, device)
+    B, cap = int(rows.shape[0]), int(rows.shape[1])
+    pert, shared, K = _records(perturbations, B, dev)
+    rows_o, counts_o, _, _ = time_rows(others_rows, others_counts, dev, device)
+    Bo, cap_o = int(rows_o.shape[0]), int(rows_o.shape[1])
+    if not 1 <= Bo <= CONFLICT_OTHERS_MAX:
+        raise ValueError(f"others: {Bo} routes (1..{CONFLICT_OTHERS_MAX})")
+    route_shift = _shift_array(route_shift, B, "route_shift", dev)
+    rollout_shift = _shift_array(rollout_shift, K, "rollout_shift", dev)
+    shapes = _follower_shapes(B, K, pursuit)
+    shapes.update(conflict=((B, K), torch.float64), conflict_rows=((B, K, 4), torch.int32), worst_conflict=((B,), torch.float64),
+                  worst_conflict_rollout=((B,), torch.int32), worst_conflict_other=((B,), torch.int32),
+                  worst_conflict_row=((B,), torch.int32), mean_conflict=((B,), torch.float64), n_conflicting=((B,), torch.int32),
+                  n_conflict_valid=((B,), torch.int32))
+    if pairs:
+        shapes.update(pair_clearance=((B, K, Bo), torch.float64), pair_rows=((B, K, Bo, 2), torch.int32))
+    bufs = buffers(out, shapes, dev)       # the call's buffers; the returned dict is built apart from it
+    res = {k: bufs[k] for k in shapes}
+    ctx = context_for(dev, ctx)
+    ctx.set_option(_lib.OPT_FOOTPRINT_CULL, 1 if cull else 0)
+    fs = follower.as_struct()
+    _lib.check(ctx._L.vap_rollout_conflicts(
+        ctx.handle, _lib.FOLLOWER_PURSUIT if pursuit else _lib.FOLLOWER_RAMSETE, C.cast(C.pointer(fs), C.c_void_p), B, cap,
+        ptr(rows), ptr(counts), int(counts.shape[1]), time_step, K, int(shared), ptr(pert), len(foot_a), dptr(foot_a),
+        Bo, cap_o, ptr(rows_o), ptr(counts_o), int(counts_o.shape[1]), len(foot_o), dptr(foot_o), margin, shift_rows,
+        ptr(route_shift), ptr(rollout_shift), ptr(res["stats"]), ptr(res["stat_rows"]), ptr(res["worst"]), ptr(res["mean"]),
+        ptr(res["worst_rollout"]), ptr(res["worst_row"]), ptr(res["n_exceeding"]), ptr(res.get("n_unfinished")),
+        ptr(res.get("route_status")), ptr(res.get("pair_clearance")), ptr(res.get("pair_rows")), ptr(res["conflict"]),
+        ptr(res["conflict_rows"]), ptr(res["worst_conflict"]), ptr(res["worst_conflict_rollout"]), ptr(res["worst_conflict_other"]),
+        ptr(res["worst_conflict_row"]), ptr(res["mean_conflict"]), ptr(res["n_conflicting"]), ptr(res["n_conflict_valid"])),
+        "vap_rollout_conflicts")
+    _follower_views(res, pursuit)
+    for i, name in enumerate(CONFLICT_ROW_COLUMNS):
+        res[name] = res["conflict_rows"][..., i]
+    return _single(res) if single else res
