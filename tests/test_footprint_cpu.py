@@ -147,3 +147,24 @@ def test_reference_against_a_dense_brute_force():
             assert d == pytest.approx(v, abs=5e-3)
         else:
             assert -v <= 0.8 + math.hypot(1.0, 0.75) + 1e-12
+
+
+def test_scene_c_args():
+    """Scene.c_args(): the six scene arguments of the C-ABI in its order, the counts beside their arrays, None for no field and
+    for the empty arrays; poly_start always has its leading 0."""
+    import ctypes as C
+    tri = np.array([[0.0, 0.0], [1.0, 0.0], [0.0, 1.0]])
+    quad = np.array([[2.0, 2.0], [3.0, 2.0], [3.0, 3.0], [2.0, 3.0]])
+    s = fp.Scene(field=(-6.0, -5.0, 6.0, 5.0), polygons=[tri, quad], circles=[(0.5, 0.25, 0.125), (1.0, 2.0, 3.0), (4.0, 4.0, 0.5)])
+    a = s.c_args()
+    assert isinstance(a, tuple) and len(a) == 6
+    field, n_poly, start, xy, n_circle, circles = a
+    assert (n_poly, n_circle) == (2, 3) == (s.n_polygons, s.n_circles)
+    assert [field[i] for i in range(4)] == [-6.0, -5.0, 6.0, 5.0]
+    assert [start[i] for i in range(3)] == [0, 3, 7]
+    assert [xy[i] for i in range(14)] == list(np.concatenate([tri, quad]).ravel())
+    assert [circles[i] for i in range(9)] == [0.5, 0.25, 0.125, 1.0, 2.0, 3.0, 4.0, 4.0, 0.5]
+    assert C.cast(xy, C.c_void_p).value == s.poly_xy.ctypes.data and C.cast(circles, C.c_void_p).value == s.circles.ctypes.data
+    field, n_poly, start, xy, n_circle, circles = fp.Scene(field=None).c_args()
+    assert field is None and xy is None and circles is None and (n_poly, n_circle) == (0, 0) and start[0] == 0
+    assert fp.Scene().c_args()[0][2] == fp.DEFAULT_FIELD[2]

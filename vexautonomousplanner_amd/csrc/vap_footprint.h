@@ -31,7 +31,8 @@ __device__ __forceinline__ double seg_dist2(double px, double py, double ax, dou
 //   foot  [n_foot][8]  body vertex x, y; outward unit normal of the edge to the next vertex nx, ny; that edge ex, ey;
 //                      1 / |e|^2; 0
 //   poly  [n_poly][4]  centre x, y; bounding radius; first vertex * 32 + vertex count (as a double)
-//   pv    [nv][8]      the polygons' vertices, same layout as foot, in world coordinates
+//   pv    [nv][8]      the polygons' vertices, same layout as foot, in world coordinates; slot 7 holds |e| = sqrt(ex ex + ey ey)
+//                      (read by k_plan_clearance only)
 //   circ  [n_circle][4] cx, cy, r, 0
 struct FootScene {
     const double *__restrict__ foot;
@@ -255,8 +256,24 @@ int check_scene(const double *h_field, int n_poly, const int *h_poly_start, cons
 // makes room in ctx->scene; scene_upload copies it on the context's stream.
 int scene_stage(vap_ctx *ctx, size_t bytes, double **h);
 int scene_upload(vap_ctx *ctx, size_t bytes);
-// Pack a validated footprint and scene (check_convex, check_scene give scale and nv), upload the block on the context's
-// stream (scene_stage, scene_upload) and fill `s` for a kernel on that stream.
+// The one packer of the block, for every kernel that reads a scene: where the parts begin (in doubles; the footprint rows, if
+// any, begin at 0) and the block's length.  The staged and uploaded block is bytes() long: one more double behind n_dbl, so
+// that an empty scene is still a block.  scene_fill writes h[0 .. n_dbl) only; that last double is zero because scene_stage
+// clears the whole staged block, and no kernel reads it.
+struct SceneLayout {
+    int o_poly, o_pv, o_circ, n_dbl;
+    size_t bytes() const { return ((size_t)n_dbl + 1) * sizeof(double); }
+};
+// scene_layout and scene_fill are the arithmetic, without a device call: the offsets, and every double of h[0 .. n_dbl) from
+// a validated footprint (n_foot = 0: none) and scene (check_scene gives nv).  scene_block stages, fills and uploads the block
+// on the context's stream (scene_stage, scene_upload: the only device calls); the block is then ctx->scene.ptr.
+SceneLayout scene_layout(int n_foot, int n_poly, int nv, int n_circle);
+void scene_fill(const SceneLayout &b, int n_foot, const double *h_foot, int n_poly, const int *h_poly_start, const double *h_poly_xy,
+                int n_circle, const double *h_circles, double *h);
+int scene_block(vap_ctx *ctx, int n_foot, const double *h_foot, int n_poly, const int *h_poly_start, const double *h_poly_xy,
+                int n_circle, const double *h_circles, int nv, SceneLayout &b);
+// scene_block for a validated footprint and scene (check_convex, check_scene give scale and nv), and `s` filled for a kernel
+// on the context's stream.
 int scene_pack(vap_ctx *ctx, int n_foot, const double *h_footprint, const double *h_field, int n_poly, const int *h_poly_start,
                const double *h_poly_xy, int n_circle, const double *h_circles, double scale, int nv, FootScene &s);
 

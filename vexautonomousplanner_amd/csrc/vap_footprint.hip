@@ -221,34 +221,61 @@ int scene_upload(vap_ctx *ctx, size_t bytes)
     return VAP_OK;
 }
 
+// Where the parts of the packed block begin: foot [n_foot][8] | poly [n_poly][4] | pv [nv][8] | circ [n_circle][4].  No device call.
+SceneLayout scene_layout(int n_foot, int n_poly, int nv, int n_circle)
+{
+    SceneLayout b;
+    b.o_poly = n_foot * 8;
+    b.o_pv = b.o_poly + n_poly * 4;
+    b.o_circ = b.o_pv + nv * 8;
+    b.n_dbl = b.o_circ + n_circle * 4;
+    return b;
+}
+
+// Every double of h[0 .. b.n_dbl) from a validated footprint (or none) and scene, in vap_footprint.h's layouts.  No device call.
+void scene_fill(const SceneLayout &b, int n_foot, const double *h_foot, int n_poly, const int *h_poly_start, const double *h_poly_xy,
+                int n_circle, const double *h_circles, double *h)
+{
+    if (n_foot > 0) pack_polygon(h_foot, n_foot, h);
+    for (int k = 0; k < n_poly; k++) {
+        const int p0 = h_poly_start[k], m = h_poly_start[k + 1] - p0;
+        double *pk = h + b.o_poly + (size_t)k * 4, *rows = h + b.o_pv + (size_t)p0 * 8;
+        bound_polygon(h_poly_xy + 2 * (size_t)p0, m, pk[0], pk[1], pk[2]);
+        pk[3] = (double)(p0 * 32 + m);
+        pack_polygon(h_poly_xy + 2 * (size_t)p0, m, rows);
+        for (int e = 0; e < m; e++) rows[e * 8 + 7] = std::sqrt(rows[e * 8 + 4] * rows[e * 8 + 4] + rows[e * 8 + 5] * rows[e * 8 + 5]);
+    }
+    for (int k = 0; k < n_circle; k++) {
+        double *ck = h + b.o_circ + (size_t)k * 4;
+        for (int j = 0; j < 3; j++) ck[j] = h_circles[3 * (size_t)k + j];
+        ck[3] = 0.0;
+    }
+}
+
+// Stage, fill and upload the block of a validated footprint (n_foot = 0: none) and scene on the context's stream; the block is
+// ctx->scene.ptr.
+int scene_block(vap_ctx *ctx, int n_foot, const double *h_foot, int n_poly, const int *h_poly_start, const double *h_poly_xy,
+                int n_circle, const double *h_circles, int nv, SceneLayout &b)
+{
+    b = scene_layout(n_foot, n_poly, nv, n_circle);
+    double *h = nullptr;
+    VAP_TRY(scene_stage(ctx, b.bytes(), &h));
+    scene_fill(b, n_foot, h_foot, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, h);
+    return scene_upload(ctx, b.bytes());
+}
+
 // The packed scene of a validated footprint and scene on the device, and `s` filled for a kernel on the context's stream.
 int scene_pack(vap_ctx *ctx, int n_foot, const double *h_footprint, const double *h_field, int n_poly, const int *h_poly_start,
                const double *h_poly_xy, int n_circle, const double *h_circles, double scale, int nv, FootScene &s)
 {
-    // pack: foot [n_foot][8] | poly [n_poly][4] | pv [nv][8] | circ [n_circle][4]
-    const size_t o_poly = (size_t)n_foot * 8, o_pv = o_poly + (size_t)n_poly * 4, o_circ = o_pv + (size_t)nv * 8;
-    const size_t n_dbl = o_circ + (size_t)n_circle * 4;
-    const size_t bytes = n_dbl * sizeof(double);
-    double *h = nullptr;
-    VAP_TRY(scene_stage(ctx, bytes, &h));
-    pack_polygon(h_footprint, n_foot, h);
+    SceneLayout b;
+    VAP_TRY(scene_block(ctx, n_foot, h_footprint, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, nv, b));
     bound_polygon(h_footprint, n_foot, s.fcx, s.fcy, s.fR);
-    for (int k = 0; k < n_poly; k++) {
-        const int p0 = h_poly_start[k], m = h_poly_start[k + 1] - p0;
-        double *pk = h + o_poly + (size_t)k * 4;
-        bound_polygon(h_poly_xy + 2 * (size_t)p0, m, pk[0], pk[1], pk[2]);
-        pk[3] = (double)(p0 * 32 + m);
-        pack_polygon(h_poly_xy + 2 * (size_t)p0, m, h + o_pv + (size_t)p0 * 8);
-    }
-    for (int k = 0; k < n_circle; k++)
-        for (int j = 0; j < 3; j++) h[o_circ + (size_t)k * 4 + j] = h_circles[3 * (size_t)k + j];
-    VAP_TRY(scene_upload(ctx, bytes));
-
     const double *d = (const double *)ctx->scene.ptr;
     s.foot = d;
-    s.poly = d + o_poly;
-    s.pv = d + o_pv;
-    s.circ = d + o_circ;
+    s.poly = d + b.o_poly;
+    s.pv = d + b.o_pv;
+    s.circ = d + b.o_circ;
     s.has_field = h_field ? 1 : 0;
     s.xmin = h_field ? h_field[0] : 0.0;
     s.ymin = h_field ? h_field[1] : 0.0;

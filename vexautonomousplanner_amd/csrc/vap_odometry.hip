@@ -296,8 +296,9 @@ int vap_odometry_rollouts(vap_ctx *ctx, int B, long capacity, const double *d_ro
         a.gain = rule->gain;
         std::memcpy(a.sens, h_sensors, (size_t)n_sens * 8 * sizeof(double));
         OdoScene &sc = a.sc;
-        VAP_TRY(ray_scene_upload(ctx, 0, nullptr, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, nv, sc.o_poly, sc.o_pv,
-                                 sc.o_circ, sc.n_dbl));
+        SceneLayout blk;
+        VAP_TRY(scene_block(ctx, 0, nullptr, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, nv, blk));
+        sc.o_poly = blk.o_poly, sc.o_pv = blk.o_pv, sc.o_circ = blk.o_circ, sc.n_dbl = blk.n_dbl;
         sc.block = (const double *)ctx->scene.ptr;
         sc.n_poly = n_poly;
         sc.n_circle = n_circle;

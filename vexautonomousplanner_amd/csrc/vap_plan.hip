@@ -33,9 +33,14 @@
 //                     No float atomics: two calls give the same bits.
 //   k_plan_travel     all ordered pairs of a problem's P points: the same workgroups over the R x P (problem, goal) items.
 //                     An item relaxes its goal's field once and keeps it in LDS while every start is snapped, traced,
-//                     pulled and resampled against it — the stages above, shared as __device__ functions — so the sums
-//                     live in the workgroup's global workspace, in front of its cell list.  The mask and the moves are
-//                     rebuilt only when the workgroup's next item belongs to another problem (and only with an occupancy).
+//                     pulled and resampled against it, so the sums live in the workgroup's global workspace, in front of
+//                     its cell list.  The mask and the moves are rebuilt only when the workgroup's next item belongs to
+//                     another problem (and only with an occupancy).
+// Both kernels run a problem through one core: PlanLds states the dynamic LDS once for the kernels and the
+// host; plan_begin (the carve, the static bits, the moves), plan_problem_mask, plan_admit, plan_goal, plan_start and
+// plan_store_waypoints string the stages together, so a travel entry is the seeds' route by construction.  A kernel keeps
+// its loop, where the sums live and its own outputs.  On the host plan_prepare carries what the two entry points share
+// behind their shape checks, and the scene goes to the device through scene_block (vap_footprint.h) like every other scene.
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -55,9 +60,9 @@ constexpr int kPlanChunkPolys = 32;                                 // polygons 
 constexpr size_t kPlanStaticLds = 512;                              // bound on k_plan_seeds' static LDS
 constexpr double kPlanSqrt2 = 1.4142135623730951;
 
-// Packed scene (fp64), the layouts of vap_footprint.hip:
-//   poly  [n_poly][4]   -, -, -, first vertex * 32 + vertex count (as a double)
-//   pv    [nv][8]       vertex x, y; -, -; the edge to the next vertex ex, ey; 1 / |e|^2; |e| = sqrt(ex ex + ey ey)
+// The parts of scene_block's packed scene (fp64, vap_footprint.h's layouts, no footprint rows) that k_plan_clearance reads:
+//   poly  [n_poly][4]   slot 3: first vertex * 32 + vertex count (as a double); the bounds in slots 0-2 are not read
+//   pv    [nv][8]       vertex x, y (0, 1); the edge to the next vertex ex, ey (4, 5); 1 / |e|^2 (6); |e| = sqrt(ex ex + ey ey) (7)
 //   circ  [n_circle][4] cx, cy, r, 0
 struct PlanScene {
     const double *poly, *pv, *circ;
@@ -262,11 +267,12 @@ __device__ __forceinline__ bool plan_relax(double *d, const uint8_t *mv, const i
             nv[c] = INFINITY;
             if (idx < ncell) {
                 const unsigned m = mv[idx];
+                const double *p = d + idx;                           // the cell's address once, the neighbours off it
                 double best = INFINITY;
                 if (m) {
 #pragma unroll
                     for (int k = 0; k < 8; k++)
-                        if (m & (1u << k)) best = fmin(best, d[idx + off[k]] + (k < 4 ? wa : wd));
+                        if (m & (1u << k)) best = fmin(best, p[off[k]] + (k < 4 ? wa : wd));
                 }
                 nv[c] = best;
             }
@@ -416,99 +422,185 @@ __device__ __forceinline__ bool plan_static_bits(const uint8_t *free_mask, uint3
     return __syncthreads_or(any);
 }
 
+// ---- one problem, as both kernels run it: the stages above strung together once ------------------------------------------
+
+// The dynamic LDS of a planning workgroup, stated once for the kernels and for the host that sizes their launch:
+//   d [nd] the distance field (nd = ncell; at least 2 where the running sums c_0, c_1 of a one-cell grid go where the field was)
+//   | fbs [nwords] the static free bits | fb [nwords] the problem's own mask (with an occupancy; without one fb is fbs)
+//   | mv [ncell up to a multiple of 16] each cell's byte of allowed moves
+struct PlanLds {
+    int ncell, nd, nwords;
+    bool occupied;
+    PlanLds() = default;
+    __host__ __device__ PlanLds(int ncell_, bool occupied_, bool sums_in_lds)
+        : ncell(ncell_), nd(sums_in_lds && ncell_ < 2 ? 2 : ncell_), nwords((ncell_ + 31) / 32), occupied(occupied_) {}
+    __host__ __device__ size_t bytes() const
+    {
+        return (size_t)nd * sizeof(double) + (size_t)(occupied ? 2 : 1) * nwords * sizeof(uint32_t) + (size_t)((ncell + 15) & ~15);
+    }
+    __device__ double *d(unsigned char *lds) const { return reinterpret_cast<double *>(lds); }
+    __device__ uint32_t *fbs(unsigned char *lds) const { return reinterpret_cast<uint32_t *>(d(lds) + nd); }
+    __device__ uint32_t *fb(unsigned char *lds) const { return occupied ? fbs(lds) + nwords : fbs(lds); }
+    __device__ uint8_t *mv(unsigned char *lds) const { return reinterpret_cast<uint8_t *>(fb(lds) + nwords); }
+};
+
+// The static LDS of both kernels: the argmin's partials, and what the tracing lane and the pull hand the workgroup.
+struct PlanShared {
+    double key[kPlanWaves];
+    int idx[kPlanWaves];
+    int n, best, fail;
+};
+
+// What a workgroup's problems share.  `Args` below is SeedArgs or TravelArgs: g, free_mask, path_ws, occ_first, occ_last, windows.
+struct PlanCore {
+    PlanGrid g;
+    PlanLds l;                  // ncell, nwords, occupied, and where the four pieces below begin
+    double *d;
+    uint32_t *fbs, *fb;
+    uint8_t *mv;
+    uint16_t *path;             // the workgroup's cell list
+    PlanShared *sh;
+    int off[8];                 // the eight moves in the header's order, as offsets in the grid
+    double wa, wd;              // the cost of an axis move and of a diagonal one
+    bool any_free;
+};
+
+// Once per workgroup: the carve, the static free bits and, without an occupancy, each free cell's allowed moves.
+template <class Args>
+__device__ __forceinline__ void plan_begin(PlanCore &c, const Args &a, unsigned char *lds, bool sums_in_lds, PlanShared *sh)
+{
+    c.g = a.g;
+    const int nx = c.g.nx, ny = c.g.ny;
+    c.l = PlanLds(nx * ny, a.occ_first != nullptr, sums_in_lds);
+    c.d = c.l.d(lds);
+    c.fbs = c.l.fbs(lds);
+    c.fb = c.l.fb(lds);
+    c.mv = c.l.mv(lds);
+    c.path = a.path_ws + (size_t)blockIdx.x * (size_t)c.l.ncell;
+    c.sh = sh;
+    const int off[8] = {1, nx, -1, -nx, nx + 1, nx - 1, -nx - 1, -nx + 1};
+#pragma unroll
+    for (int k = 0; k < 8; k++) c.off[k] = off[k];
+    c.wa = c.g.cell;
+    c.wd = c.g.cell * kPlanSqrt2;
+    c.any_free = plan_static_bits(a.free_mask, c.fbs, c.l.ncell, c.l.nwords);
+    if (!c.l.occupied) {
+        plan_moves(c.fb, c.mv, nx, ny);
+        __syncthreads();
+    }
+}
+
+// Problem r's own mask and moves under its window: the static bits minus the cells occupied in [t0, t1).  Nothing without an
+// occupancy.  The whole workgroup calls it.
+template <class Args>
+__device__ __forceinline__ void plan_problem_mask(PlanCore &c, const Args &a, int r)
+{
+    if (!c.l.occupied) return;
+    const int t0 = a.windows ? a.windows[(size_t)r * 2] : INT_MIN, t1 = a.windows ? a.windows[(size_t)r * 2 + 1] : INT_MAX;
+    c.any_free = plan_window_mask(c.fbs, c.fb, c.l.nwords, a.occ_first, a.occ_last, t0, t1);
+    plan_moves(c.fb, c.mv, c.g.nx, c.g.ny);
+    __syncthreads();
+}
+
+// Is there anything to plan: four finite coordinates, then a free cell.  The flag of the first that fails.
+__device__ __forceinline__ bool plan_admit(const PlanCore &c, const PlanRoute &rt, uint32_t &flags)
+{
+    if (!(isfinite(rt.sx) && isfinite(rt.sy) && isfinite(rt.gx) && isfinite(rt.gy))) {
+        flags |= VAP_FLAG_DEGENERATE;
+        return false;
+    }
+    if (!c.any_free) {
+        flags |= VAP_PLAN_NO_FREE;
+        return false;
+    }
+    return true;
+}
+
+// the cell of a point, or the free cell nearest to it (`snapped` is raised); every condition is the same in all threads
+__device__ __forceinline__ int plan_snap(const PlanCore &c, double x, double y, uint32_t snapped, uint32_t &flags)
+{
+    const PlanGrid &g = c.g;
+    int cell = plan_cell_of(y, g.ymin, g.cell, g.ny) * g.nx + plan_cell_of(x, g.xmin, g.cell, g.nx);
+    if (!plan_free(c.fb, cell)) {
+        cell = plan_nearest_free(g, c.fb, x, y, c.sh->key, c.sh->idx);
+        flags |= snapped;
+    }
+    return cell;
+}
+
+// The goal's share: its cell, snapped if need be, and the field relaxed from it into c.d.  The whole workgroup calls it, with
+// finite coordinates and a free cell somewhere.
+__device__ __forceinline__ void plan_goal(const PlanCore &c, double gx, double gy, uint32_t &flags)
+{
+    const int gc = plan_snap(c, gx, gy, VAP_PLAN_SNAPPED_GOAL, flags);
+    if (!plan_relax(c.d, c.mv, c.off, c.wa, c.wd, c.l.ncell, gc)) flags |= VAP_FLAG_NOCONVERGE;
+}
+
+// The start's share on a relaxed field: its cell, snapped if need be, the reach test, the trace on one lane, the pull; fills
+// rt.nvtx and leaves the pulled cells in c.path.  The whole workgroup calls it, after plan_admit; false: no route.
+__device__ __forceinline__ bool plan_start(const PlanCore &c, PlanRoute &rt, uint32_t &flags)
+{
+    const int sc = plan_snap(c, rt.sx, rt.sy, VAP_PLAN_SNAPPED_START, flags);
+    if (c.d[sc] == INFINITY) {
+        flags |= VAP_PLAN_UNREACHABLE;
+        return false;
+    }
+    if (threadIdx.x == 0) {
+        int fail;
+        c.sh->n = plan_trace(c.d, c.mv, c.off, c.wa, c.wd, c.l.ncell, sc, c.path, fail);
+        c.sh->fail = fail;
+    }
+    __syncthreads();
+    const int n = c.sh->n;
+    const bool fail = c.sh->fail;
+    __syncthreads();
+    if (fail) {
+        flags |= VAP_FLAG_NOCONVERGE;
+        return false;
+    }
+    const int nv = plan_pull(c.fb, c.g.nx, c.path, n, &c.sh->best);
+    rt.nvtx = n == 1 ? 2 : nv;
+    return true;
+}
+
+// wp [W][2]: the route resampled at equal arcs, NaN without one.  A thread per waypoint.
+__device__ __forceinline__ void plan_store_waypoints(const PlanGrid &g, const PlanRoute &rt, const double *cum, double L, bool ok,
+                                                     int W, double *wp)
+{
+    for (int k = threadIdx.x; k < W; k += kPlanThreads) {
+        double x = NAN, y = NAN;
+        if (ok) plan_waypoint(g, rt, cum, L, k, W, x, y);
+        wp[2 * k] = x;
+        wp[2 * k + 1] = y;
+    }
+}
+
 __global__ __launch_bounds__(kPlanThreads) void k_plan_seeds(SeedArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char plan_lds[];
-    __shared__ double s_key[kPlanWaves];
-    __shared__ int s_idx[kPlanWaves];
-    __shared__ int s_n, s_best, s_fail;
-    const PlanGrid g = a.g;
-    const int tid = threadIdx.x, nx = g.nx, ny = g.ny, ncell = nx * ny, nwords = (ncell + 31) / 32;
-    double *d = reinterpret_cast<double *>(plan_lds);
-    const bool occupied = a.occ_first != nullptr;
-    uint32_t *fbs = reinterpret_cast<uint32_t *>(d + (ncell < 2 ? 2 : ncell));  // the sums c_0, c_1 of a one-cell grid
-    uint32_t *fb = occupied ? fbs + nwords : fbs;                    // the problem's own mask
-    uint8_t *mv = reinterpret_cast<uint8_t *>(fb + nwords);
-    // the eight moves in the header's order: offset in the grid and cost
-    const int off[8] = {1, nx, -1, -nx, nx + 1, nx - 1, -nx - 1, -nx + 1};
-    const double wa = g.cell, wd = g.cell * kPlanSqrt2;
-
-    // once per workgroup: the static free bits; without an occupancy also each free cell's allowed moves
-    bool any_free = plan_static_bits(a.free_mask, fbs, ncell, nwords);
-    if (!occupied) {
-        plan_moves(fb, mv, nx, ny);
-        __syncthreads();
-    }
-
-    uint16_t *path = a.path_ws + (size_t)blockIdx.x * (size_t)ncell;
+    __shared__ PlanShared sh;
+    PlanCore c;
+    plan_begin(c, a, plan_lds, true, &sh);
+    const PlanGrid &g = c.g;
+    const int tid = threadIdx.x, ncell = c.l.ncell;
 #pragma unroll 1
     for (int r = blockIdx.x; r < a.R; r += gridDim.x) {
-        PlanRoute rt{a.starts[(size_t)r * 2], a.starts[(size_t)r * 2 + 1], a.goals[(size_t)r * 2], a.goals[(size_t)r * 2 + 1], path, 0};
+        PlanRoute rt{a.starts[(size_t)r * 2], a.starts[(size_t)r * 2 + 1], a.goals[(size_t)r * 2], a.goals[(size_t)r * 2 + 1], c.path, 0};
         uint32_t flags = 0;
-        bool ok = true;
-        int sc = 0, gc = 0;
-        if (occupied) {                                              // the static bits minus the cells occupied in (t0, t1)
-            const int t0 = a.windows ? a.windows[(size_t)r * 2] : INT_MIN, t1 = a.windows ? a.windows[(size_t)r * 2 + 1] : INT_MAX;
-            any_free = plan_window_mask(fbs, fb, nwords, a.occ_first, a.occ_last, t0, t1);
-            plan_moves(fb, mv, nx, ny);
-            __syncthreads();
-        }
-        if (!(isfinite(rt.sx) && isfinite(rt.sy) && isfinite(rt.gx) && isfinite(rt.gy))) {
-            flags |= VAP_FLAG_DEGENERATE;
-            ok = false;
-        } else if (!any_free) {
-            flags |= VAP_PLAN_NO_FREE;
-            ok = false;
-        }
+        plan_problem_mask(c, a, r);
+        bool ok = plan_admit(c, rt, flags);
         if (!ok && a.distance)                                       // no field: +inf everywhere
             for (int idx = tid; idx < ncell; idx += kPlanThreads) a.distance[(size_t)r * ncell + idx] = INFINITY;
-        if (ok) {                                                    // every condition below is the same in all threads
-            gc = plan_cell_of(rt.gy, g.ymin, g.cell, ny) * nx + plan_cell_of(rt.gx, g.xmin, g.cell, nx);
-            if (!plan_free(fb, gc)) {
-                gc = plan_nearest_free(g, fb, rt.gx, rt.gy, s_key, s_idx);
-                flags |= VAP_PLAN_SNAPPED_GOAL;
-            }
-            sc = plan_cell_of(rt.sy, g.ymin, g.cell, ny) * nx + plan_cell_of(rt.sx, g.xmin, g.cell, nx);
-            if (!plan_free(fb, sc)) {
-                sc = plan_nearest_free(g, fb, rt.sx, rt.sy, s_key, s_idx);
-                flags |= VAP_PLAN_SNAPPED_START;
-            }
-            if (!plan_relax(d, mv, off, wa, wd, ncell, gc)) flags |= VAP_FLAG_NOCONVERGE;
-            if (a.distance)
-                for (int idx = tid; idx < ncell; idx += kPlanThreads) a.distance[(size_t)r * ncell + idx] = d[idx];
-            if (d[sc] == INFINITY) {
-                flags |= VAP_PLAN_UNREACHABLE;
-                ok = false;
-            }
-        }
         if (ok) {
-            if (tid == 0) {
-                int fail;
-                s_n = plan_trace(d, mv, off, wa, wd, ncell, sc, path, fail);
-                s_fail = fail;
-            }
-            __syncthreads();
-            const int n = s_n;
-            if (s_fail) {
-                flags |= VAP_FLAG_NOCONVERGE;
-                ok = false;
-            }
-            __syncthreads();
-            if (ok) {
-                const int nv = plan_pull(fb, nx, path, n, &s_best);
-                rt.nvtx = n == 1 ? 2 : nv;
-            }
+            plan_goal(c, rt.gx, rt.gy, flags);
+            if (a.distance)
+                for (int idx = tid; idx < ncell; idx += kPlanThreads) a.distance[(size_t)r * ncell + idx] = c.d[idx];
+            ok = plan_start(c, rt, flags);
         }
-        double *cum = d;                                             // the field is done with: c_0 .. c_(nvtx-1)
+        double *cum = c.d;                                           // the field is done with: c_0 .. c_(nvtx-1)
         if (ok) plan_lengths(g, rt, cum);
         const double L = ok ? cum[rt.nvtx - 1] : INFINITY;
-        double *wp = a.wp + (size_t)r * a.W * 2;
-        for (int k = tid; k < a.W; k += kPlanThreads) {
-            double x = NAN, y = NAN;
-            if (ok) plan_waypoint(g, rt, cum, L, k, a.W, x, y);
-            wp[2 * k] = x;
-            wp[2 * k + 1] = y;
-        }
+        plan_store_waypoints(g, rt, cum, L, ok, a.W, a.wp + (size_t)r * a.W * 2);
         if (a.vertices) {
             double *vo = a.vertices + (size_t)r * a.max_vertices * 2;
             for (int m = tid; m < a.max_vertices; m += kPlanThreads) {
@@ -543,32 +635,17 @@ struct TravelArgs {
     const int *windows;                // [R][2] (t0, t1), NULL: every instant
 };
 
-// Entry (r, a, b) is k_plan_seeds' problem (start = point a, goal = point b): an item is one (problem, goal), whose field is
-// relaxed once and stays in LDS while every start a != b is snapped, traced, pulled and resampled against it.  The running
-// sums therefore live in the workgroup's global workspace, not where the field is.
+// Entry (r, a, b) is k_plan_seeds' problem (start = point a, goal = point b), by the same functions: an item is one
+// (problem, goal), whose field is relaxed once and stays in LDS while every start a != b is snapped, traced, pulled and
+// resampled against it.  The running sums therefore live in the workgroup's global workspace, not where the field is.
 __global__ __launch_bounds__(kPlanThreads) void k_plan_travel(TravelArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char plan_lds[];
-    __shared__ double s_key[kPlanWaves];
-    __shared__ int s_idx[kPlanWaves];
-    __shared__ int s_n, s_best, s_fail;
-    const PlanGrid g = a.g;
-    const int tid = threadIdx.x, nx = g.nx, ny = g.ny, ncell = nx * ny, nwords = (ncell + 31) / 32, P = a.P;
-    double *d = reinterpret_cast<double *>(plan_lds);
-    const bool occupied = a.occ_first != nullptr;
-    uint32_t *fbs = reinterpret_cast<uint32_t *>(d + ncell);
-    uint32_t *fb = occupied ? fbs + nwords : fbs;                    // the problem's own mask
-    uint8_t *mv = reinterpret_cast<uint8_t *>(fb + nwords);
-    const int off[8] = {1, nx, -1, -nx, nx + 1, nx - 1, -nx - 1, -nx + 1};
-    const double wa = g.cell, wd = g.cell * kPlanSqrt2;
-
-    bool any_free = plan_static_bits(a.free_mask, fbs, ncell, nwords);
-    if (!occupied) {
-        plan_moves(fb, mv, nx, ny);
-        __syncthreads();
-    }
-
-    uint16_t *path = a.path_ws + (size_t)blockIdx.x * (size_t)ncell;
+    __shared__ PlanShared sh;
+    PlanCore c;
+    plan_begin(c, a, plan_lds, false, &sh);
+    const PlanGrid &g = c.g;
+    const int tid = threadIdx.x, ncell = c.l.ncell, P = a.P;
     double *cum = a.cum_ws + (size_t)blockIdx.x * (size_t)(ncell < 2 ? 2 : ncell);
     const int items = a.R * P;
     int built = -1;                                                  // the problem whose mask and moves are in LDS
@@ -577,25 +654,13 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_travel(TravelArgs a)
         const int r = it / P, b = it - r * P;
         const double *pts = a.points + (size_t)r * P * 2;
         const double gx = pts[2 * b], gy = pts[2 * b + 1];
-        if (occupied && r != built) {
-            const int t0 = a.windows ? a.windows[(size_t)r * 2] : INT_MIN, t1 = a.windows ? a.windows[(size_t)r * 2 + 1] : INT_MAX;
-            any_free = plan_window_mask(fbs, fb, nwords, a.occ_first, a.occ_last, t0, t1);
-            plan_moves(fb, mv, nx, ny);
-            __syncthreads();
+        if (r != built) {
+            plan_problem_mask(c, a, r);
             built = r;
         }
         // the goal's share of every pair: its cell and its field
-        const bool goal_ok = isfinite(gx) && isfinite(gy);
         uint32_t gflags = 0;
-        int gc = 0;
-        if (goal_ok && any_free) {
-            gc = plan_cell_of(gy, g.ymin, g.cell, ny) * nx + plan_cell_of(gx, g.xmin, g.cell, nx);
-            if (!plan_free(fb, gc)) {
-                gc = plan_nearest_free(g, fb, gx, gy, s_key, s_idx);
-                gflags |= VAP_PLAN_SNAPPED_GOAL;
-            }
-            if (!plan_relax(d, mv, off, wa, wd, ncell, gc)) gflags |= VAP_FLAG_NOCONVERGE;
-        }
+        if (isfinite(gx) && isfinite(gy) && c.any_free) plan_goal(c, gx, gy, gflags);
 #pragma unroll 1
         for (int s = 0; s < P; s++) {
             const size_t e = ((size_t)r * P + s) * P + b;
@@ -612,54 +677,16 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_travel(TravelArgs a)
                 }
                 continue;
             }
-            PlanRoute rt{pts[2 * s], pts[2 * s + 1], gx, gy, path, 0};
+            PlanRoute rt{pts[2 * s], pts[2 * s + 1], gx, gy, c.path, 0};
             uint32_t flags = 0;
-            bool ok = true;
-            if (!(isfinite(rt.sx) && isfinite(rt.sy) && goal_ok)) {
-                flags |= VAP_FLAG_DEGENERATE;
-                ok = false;
-            } else if (!any_free) {
-                flags |= VAP_PLAN_NO_FREE;
-                ok = false;
-            }
-            if (ok) {                                                // every condition below is the same in all threads
+            bool ok = plan_admit(c, rt, flags);
+            if (ok) {
                 flags = gflags;
-                int sc = plan_cell_of(rt.sy, g.ymin, g.cell, ny) * nx + plan_cell_of(rt.sx, g.xmin, g.cell, nx);
-                if (!plan_free(fb, sc)) {
-                    sc = plan_nearest_free(g, fb, rt.sx, rt.sy, s_key, s_idx);
-                    flags |= VAP_PLAN_SNAPPED_START;
-                }
-                if (d[sc] == INFINITY) {
-                    flags |= VAP_PLAN_UNREACHABLE;
-                    ok = false;
-                }
-                if (ok) {
-                    if (tid == 0) {
-                        int fail;
-                        s_n = plan_trace(d, mv, off, wa, wd, ncell, sc, path, fail);
-                        s_fail = fail;
-                    }
-                    __syncthreads();
-                    const int n = s_n;
-                    if (s_fail) {
-                        flags |= VAP_FLAG_NOCONVERGE;
-                        ok = false;
-                    }
-                    __syncthreads();
-                    if (ok) {
-                        const int nv = plan_pull(fb, nx, path, n, &s_best);
-                        rt.nvtx = n == 1 ? 2 : nv;
-                    }
-                }
+                ok = plan_start(c, rt, flags);
             }
             if (ok) plan_lengths(g, rt, cum);
             const double L = ok ? cum[rt.nvtx - 1] : INFINITY;
-            for (int k = tid; wp && k < a.W; k += kPlanThreads) {
-                double x = NAN, y = NAN;
-                if (ok) plan_waypoint(g, rt, cum, L, k, a.W, x, y);
-                wp[2 * k] = x;
-                wp[2 * k + 1] = y;
-            }
+            if (wp) plan_store_waypoints(g, rt, cum, L, ok, a.W, wp);
             if (tid == 0) {
                 a.travel[e] = L;
                 if (a.flags) a.flags[e] = flags;
@@ -700,28 +727,15 @@ static int plan_check(const double *h_field, int n_poly, const int *h_poly_start
     return plan_grid_of(h_field, cell, g);
 }
 
-// Pack and upload the scene, then the clearance kernel over the grid.
+// Upload the scene's block (scene_block: no footprint rows), then the clearance kernel over the grid.
 static int plan_launch_grid(vap_ctx *ctx, const PlanGrid &g, int nv, int n_poly, const int *h_poly_start, const double *h_poly_xy,
                             int n_circle, const double *h_circles, double radius, double margin, double *d_clearance,
                             uint8_t *d_free)
 {
-    // pack: poly [n_poly][4] | pv [nv][8] | circ [n_circle][4]
-    const size_t o_pv = (size_t)n_poly * 4, o_circ = o_pv + (size_t)nv * 8;
-    const size_t bytes = (o_circ + (size_t)n_circle * 4 + 1) * sizeof(double);
-    double *h = nullptr;
-    VAP_TRY(scene_stage(ctx, bytes, &h));
-    for (int k = 0; k < n_poly; k++) {
-        const int p0 = h_poly_start[k], m = h_poly_start[k + 1] - p0;
-        h[(size_t)k * 4 + 3] = (double)(p0 * 32 + m);
-        double *rows = h + o_pv + (size_t)p0 * 8;
-        pack_polygon(h_poly_xy + 2 * (size_t)p0, m, rows);
-        for (int e = 0; e < m; e++) rows[e * 8 + 7] = std::sqrt(rows[e * 8 + 4] * rows[e * 8 + 4] + rows[e * 8 + 5] * rows[e * 8 + 5]);
-    }
-    for (int k = 0; k < n_circle; k++)
-        for (int j = 0; j < 3; j++) h[o_circ + (size_t)k * 4 + j] = h_circles[3 * (size_t)k + j];
-    VAP_TRY(scene_upload(ctx, bytes));
+    SceneLayout b;
+    VAP_TRY(scene_block(ctx, 0, nullptr, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, nv, b));
     const double *d = (const double *)ctx->scene.ptr;
-    PlanScene s{d, d + o_pv, d + o_circ, n_poly, n_circle};
+    PlanScene s{d + b.o_poly, d + b.o_pv, d + b.o_circ, n_poly, n_circle};
     const int ncell = g.nx * g.ny;
     hipLaunchKernelGGL(k_plan_clearance, dim3((ncell + kPlanGridThreads - 1) / kPlanGridThreads), dim3(kPlanGridThreads), 0,
                        ctx->stream, g, s, radius, margin, d_clearance, d_free);
@@ -740,6 +754,44 @@ static int plan_grant_lds(vap_ctx *ctx, const void *kernel, size_t lds, const Pl
     if (e != hipSuccess || (lds_max > 64 * 1024 && lds + kPlanStaticLds > (size_t)lds_max))
         return vap_fail(VAP_ERR_UNSUPPORTED, "a grid of %d x %d cells needs %zu bytes of LDS; the device gives a workgroup %d (%s)",
                         g.nx, g.ny, lds + kPlanStaticLds, lds_max, hipGetErrorString(e));
+    return VAP_OK;
+}
+
+// What vap_plan_seeds_occupied and vap_plan_travel do between their own shape checks and their launch.
+struct PlanLaunch {
+    PlanGrid g;
+    size_t lds, cum_bytes;          // cum_bytes: every workgroup's running sums in front of the cell lists (0: they are in LDS)
+    int blocks;                     // 0: nothing to launch
+};
+
+static int plan_check_occupancy(const int *d_occ_first, const int *d_occ_last)
+{
+    if ((d_occ_first == nullptr) != (d_occ_last == nullptr))
+        return vap_fail(VAP_ERR_INVALID, "the occupancy needs both its first and its last instants (or neither)");
+    return VAP_OK;
+}
+
+// The shared checks and the grid, the device, the kernel's LDS (PlanLds) and its grant, one workgroup per item up to
+// kPlanMaxBlocks, the free mask and the workspace ([sums, if not in LDS][cell lists]) and the clearance kernel into the mask.
+static int plan_prepare(vap_ctx *ctx, const double *h_field, int n_poly, const int *h_poly_start, const double *h_poly_xy, int n_circle,
+                        const double *h_circles, double cell, double radius, double margin, bool occupied, const void *kernel,
+                        long long items, bool sums_in_lds, PlanLaunch &pl)
+{
+    int nv = 0;
+    pl.blocks = 0;
+    VAP_TRY(plan_check(h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, cell, radius, margin, pl.g, nv));
+    VAP_TRY(vap_set_device(ctx));
+    if (items == 0) return VAP_OK;
+    const size_t ncell = (size_t)pl.g.nx * pl.g.ny;
+    pl.lds = PlanLds((int)ncell, occupied, sums_in_lds).bytes();
+    VAP_TRY(plan_grant_lds(ctx, kernel, pl.lds, pl.g));
+    const int blocks = items < kPlanMaxBlocks ? (int)items : kPlanMaxBlocks;
+    pl.cum_bytes = sums_in_lds ? 0 : (size_t)blocks * (ncell < 2 ? 2 : ncell) * sizeof(double);
+    VAP_TRY(ctx->ensure(ctx->plan_free, ncell));
+    VAP_TRY(ctx->ensure(ctx->plan_path, pl.cum_bytes + (size_t)blocks * ncell * sizeof(uint16_t)));
+    VAP_TRY(plan_launch_grid(ctx, pl.g, nv, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, radius, margin, nullptr,
+                             (uint8_t *)ctx->plan_free.ptr));
+    pl.blocks = blocks;
     return VAP_OK;
 }
 
@@ -779,30 +831,18 @@ int vap_plan_seeds_occupied(vap_ctx *ctx, int R, int W, const double *d_starts, 
                             int *d_n_vertices, double *d_vertices, double *d_distance)
 {
     using namespace vap;
-    if ((d_occ_first == nullptr) != (d_occ_last == nullptr))
-        return vap_fail(VAP_ERR_INVALID, "the occupancy needs both its first and its last instants (or neither)");
+    VAP_TRY(plan_check_occupancy(d_occ_first, d_occ_last));
     if (R < 0) return vap_fail(VAP_ERR_INVALID, "bad shape R=%d", R);
     if (W < 2) return vap_fail(VAP_ERR_INVALID, "W=%d: a route needs at least 2 waypoints", W);
     if (W > kMaxWaypoints) return vap_fail(VAP_ERR_UNSUPPORTED, "W=%d exceeds %d", W, kMaxWaypoints);
     if (d_vertices && max_vertices < 2) return vap_fail(VAP_ERR_INVALID, "max_vertices = %d: the vertex output needs at least 2", max_vertices);
     if (R > 0 && (!d_starts || !d_goals || !d_waypoints)) return vap_fail(VAP_ERR_INVALID, "null starts / goals / waypoints");
-    PlanGrid g{};
-    int nv = 0;
-    VAP_TRY(plan_check(h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, cell, radius, margin, g, nv));
-    VAP_TRY(vap_set_device(ctx));
-    if (R == 0) return VAP_OK;
-
-    const size_t ncell = (size_t)g.nx * g.ny, nwords = (ncell + 31) / 32;
-    const size_t lds = (ncell < 2 ? 2 : ncell) * sizeof(double) + (d_occ_first ? 2 : 1) * nwords * sizeof(uint32_t) +
-                       ((ncell + 15) & ~(size_t)15);
-    VAP_TRY(plan_grant_lds(ctx, reinterpret_cast<const void *>(k_plan_seeds), lds, g));
-    const int blocks = R < kPlanMaxBlocks ? R : kPlanMaxBlocks;
-    VAP_TRY(ctx->ensure(ctx->plan_free, ncell));
-    VAP_TRY(ctx->ensure(ctx->plan_path, (size_t)blocks * ncell * sizeof(uint16_t)));
-    VAP_TRY(plan_launch_grid(ctx, g, nv, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, radius, margin, nullptr,
-                             (uint8_t *)ctx->plan_free.ptr));
+    PlanLaunch pl{};
+    VAP_TRY(plan_prepare(ctx, h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, cell, radius, margin, d_occ_first != nullptr,
+                         reinterpret_cast<const void *>(k_plan_seeds), R, true, pl));
+    if (!pl.blocks) return VAP_OK;
     SeedArgs a{};
-    a.g = g;
+    a.g = pl.g;
     a.R = R;
     a.W = W;
     a.max_vertices = max_vertices;
@@ -819,7 +859,7 @@ int vap_plan_seeds_occupied(vap_ctx *ctx, int R, int W, const double *d_starts, 
     a.occ_first = d_occ_first;
     a.occ_last = d_occ_last;
     a.windows = d_occ_first ? d_windows : nullptr;
-    hipLaunchKernelGGL(k_plan_seeds, dim3((unsigned)blocks), dim3(kPlanThreads), lds, ctx->stream, a);
+    hipLaunchKernelGGL(k_plan_seeds, dim3((unsigned)pl.blocks), dim3(kPlanThreads), pl.lds, ctx->stream, a);
     HIP_TRY(hipGetLastError());
     return VAP_OK;
 }
@@ -831,40 +871,26 @@ int vap_plan_travel(vap_ctx *ctx, int R, int P, int W, const double *d_points, c
 {
     using namespace vap;
     (void)max_vertices;                                              // no output of this call is cut to it
-    if ((d_occ_first == nullptr) != (d_occ_last == nullptr))
-        return vap_fail(VAP_ERR_INVALID, "the occupancy needs both its first and its last instants (or neither)");
+    VAP_TRY(plan_check_occupancy(d_occ_first, d_occ_last));
     if (R < 0 || P < 2) return vap_fail(VAP_ERR_INVALID, "bad shape R=%d P=%d", R, P);
     if (P > VAP_PLAN_TRAVEL_MAX_POINTS) return vap_fail(VAP_ERR_UNSUPPORTED, "P=%d exceeds %d", P, VAP_PLAN_TRAVEL_MAX_POINTS);
     if (d_waypoints && W < 2) return vap_fail(VAP_ERR_INVALID, "W=%d: a route needs at least 2 waypoints", W);
     if (d_waypoints && W > kMaxWaypoints) return vap_fail(VAP_ERR_UNSUPPORTED, "W=%d exceeds %d", W, kMaxWaypoints);
     if (R > 0 && (!d_points || !d_travel)) return vap_fail(VAP_ERR_INVALID, "null points / travel");
     if ((long long)R * P > INT_MAX) return vap_fail(VAP_ERR_UNSUPPORTED, "R=%d problems of P=%d points exceed %d goals", R, P, INT_MAX);
-    PlanGrid g{};
-    int nv = 0;
-    VAP_TRY(plan_check(h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, cell, radius, margin, g, nv));
-    VAP_TRY(vap_set_device(ctx));
-    if (R == 0) return VAP_OK;
-
-    const size_t ncell = (size_t)g.nx * g.ny, nwords = (ncell + 31) / 32, ncum = ncell < 2 ? 2 : ncell;
-    const size_t lds = ncell * sizeof(double) + (d_occ_first ? 2 : 1) * nwords * sizeof(uint32_t) + ((ncell + 15) & ~(size_t)15);
-    VAP_TRY(plan_grant_lds(ctx, reinterpret_cast<const void *>(k_plan_travel), lds, g));
-    const long long items = (long long)R * P;
-    const int blocks = items < kPlanMaxBlocks ? (int)items : kPlanMaxBlocks;
-    // the workspace: every workgroup's running sums, then its cell list
-    const size_t cum_bytes = (size_t)blocks * ncum * sizeof(double);
-    VAP_TRY(ctx->ensure(ctx->plan_free, ncell));
-    VAP_TRY(ctx->ensure(ctx->plan_path, cum_bytes + (size_t)blocks * ncell * sizeof(uint16_t)));
-    VAP_TRY(plan_launch_grid(ctx, g, nv, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, radius, margin, nullptr,
-                             (uint8_t *)ctx->plan_free.ptr));
+    PlanLaunch pl{};
+    VAP_TRY(plan_prepare(ctx, h_field, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, cell, radius, margin, d_occ_first != nullptr,
+                         reinterpret_cast<const void *>(k_plan_travel), (long long)R * P, false, pl));
+    if (!pl.blocks) return VAP_OK;
     TravelArgs a{};
-    a.g = g;
+    a.g = pl.g;
     a.R = R;
     a.P = P;
     a.W = W;
     a.points = d_points;
     a.free_mask = (const uint8_t *)ctx->plan_free.ptr;
     a.cum_ws = (double *)ctx->plan_path.ptr;
-    a.path_ws = (uint16_t *)((char *)ctx->plan_path.ptr + cum_bytes);
+    a.path_ws = (uint16_t *)((char *)ctx->plan_path.ptr + pl.cum_bytes);
     a.travel = d_travel;
     a.flags = d_flags;
     a.n_vertices = d_n_vertices;
@@ -872,7 +898,7 @@ int vap_plan_travel(vap_ctx *ctx, int R, int P, int W, const double *d_points, c
     a.occ_first = d_occ_first;
     a.occ_last = d_occ_last;
     a.windows = d_occ_first ? d_windows : nullptr;
-    hipLaunchKernelGGL(k_plan_travel, dim3((unsigned)blocks), dim3(kPlanThreads), lds, ctx->stream, a);
+    hipLaunchKernelGGL(k_plan_travel, dim3((unsigned)pl.blocks), dim3(kPlanThreads), pl.lds, ctx->stream, a);
     HIP_TRY(hipGetLastError());
     return VAP_OK;
 }

@@ -380,9 +380,9 @@ int vap_range_readings(vap_ctx *ctx, int B, long capacity, const double *d_rows,
     g.cap = (int)capacity;
     g.n_sens = n_sens;
     std::memcpy(g.sens, h_sensors, (size_t)n_sens * 8 * sizeof(double));
-    // pack: foot [n_foot_o][8] | poly [n_poly][4] | pv [nv][8] | circ [n_circle][4]
-    VAP_TRY(ray_scene_upload(ctx, n_foot_o, h_foot_o, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, nv, g.o_poly, g.o_pv,
-                             g.o_circ, g.n_dbl));
+    SceneLayout blk;                                   // the partners' footprint rows in front (vap_footprint.h)
+    VAP_TRY(scene_block(ctx, n_foot_o, h_foot_o, n_poly, h_poly_start, h_poly_xy, n_circle, h_circles, nv, blk));
+    g.o_poly = blk.o_poly, g.o_pv = blk.o_pv, g.o_circ = blk.o_circ, g.n_dbl = blk.n_dbl;
     double far = 0.0;
     for (int i = 0; i < n_foot_o; i++) far = std::fmax(far, std::hypot(h_foot_o[2 * i], h_foot_o[2 * i + 1]));
     g.scene = (const double *)ctx->scene.ptr;

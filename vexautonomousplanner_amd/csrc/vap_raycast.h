@@ -1,12 +1,12 @@
 // vap_raycast.h — the ray cast two files share: vap_range.hip (what a range sensor reads along given rows) and
 // vap_odometry.hip (the same reading taken inside a rollout, on the pose while it is in registers).  One ray against the
 // field walls, the packed scene's convex polygons and its circles, by the rules of vap_range_readings (include/vap.h,
-// candidates 1-3); the sensors' host-side checks and the packing of the scene block.  Both files compile these definitions,
+// candidates 1-3), and the sensors' host-side checks.  Both files compile these definitions,
 // so a reading is the same bits in both.
 //
 // `Args` in the templates below is any struct with the members
 //     int o_poly, o_pv, o_circ, n_poly, n_circle, has_field, cull;  double xmin, ymin, xmax, ymax, slack;
-// (RangeArgs, OdoScene), and S the packed block, in LDS or global memory:
+// (RangeArgs, OdoScene; the offsets are scene_block's), and S the packed block, in LDS or global memory:
 //     foot [n_foot_o][8] (vap_range.hip's partners; none elsewhere) | poly [n_poly][4] | pv [nv][8] | circ [n_circle][4]
 // in vap_footprint.h's layouts.
 #pragma once
@@ -140,32 +140,6 @@ inline int check_sensor_rows(int n_sens, const double *h_sensors)
         if (!(0.0 <= q[6] && q[6] <= 1.0)) return vap_fail(VAP_ERR_INVALID, "sensor %d: min_cos %g outside [0, 1]", s, q[6]);
     }
     return VAP_OK;
-}
-
-// Pack a validated scene (check_scene gives nv) behind n_foot_o rows of a partner footprint (or none) and upload the block on
-// the context's stream; the block is ctx->scene.ptr.  o_*: where the parts begin, in doubles; n_dbl: the block's length.
-inline int ray_scene_upload(vap_ctx *ctx, int n_foot_o, const double *h_foot_o, int n_poly, const int *h_poly_start,
-                            const double *h_poly_xy, int n_circle, const double *h_circles, int nv, int &o_poly, int &o_pv,
-                            int &o_circ, int &n_dbl)
-{
-    o_poly = n_foot_o * 8;
-    o_pv = o_poly + n_poly * 4;
-    o_circ = o_pv + nv * 8;
-    n_dbl = o_circ + n_circle * 4;
-    const size_t bytes = (size_t)(n_dbl > 0 ? n_dbl : 1) * sizeof(double);
-    double *h = nullptr;
-    VAP_TRY(scene_stage(ctx, bytes, &h));
-    if (n_foot_o > 0) pack_polygon(h_foot_o, n_foot_o, h);
-    for (int k = 0; k < n_poly; k++) {
-        const int p0 = h_poly_start[k], m = h_poly_start[k + 1] - p0;
-        double *pk = h + o_poly + (size_t)k * 4;
-        bound_polygon(h_poly_xy + 2 * (size_t)p0, m, pk[0], pk[1], pk[2]);
-        pk[3] = (double)(p0 * 32 + m);
-        pack_polygon(h_poly_xy + 2 * (size_t)p0, m, h + o_pv + (size_t)p0 * 8);
-    }
-    for (int k = 0; k < n_circle; k++)
-        for (int j = 0; j < 3; j++) h[o_circ + (size_t)k * 4 + j] = h_circles[3 * (size_t)k + j];
-    return scene_upload(ctx, bytes);
 }
 
 }  // namespace vap

@@ -124,6 +124,12 @@ class Scene:
     def n_circles(self):
         return len(self.circles)
 
+    def c_args(self):
+        """The six scene arguments of the C-ABI as a tuple: field, n_poly, poly_start, poly_xy, n_circle, circles (None for
+        no field and for the empty arrays)."""
+        return (dptr(self.field), self.n_polygons, self.poly_start.ctypes.data_as(_lib.ip), dptr(self.poly_xy), self.n_circles,
+                dptr(self.circles))
+
     def element_name(self, eid):
         """'wall', 'polygon k' or 'circle k' for an element id."""
         eid = int(eid)
@@ -167,8 +173,7 @@ def clearance(rows, counts, footprint, scene, margin=0.0, per_row=False, out=Non
     ctx.set_option(_lib.OPT_FOOTPRINT_CULL, 1 if cull else 0)
     _lib.check(ctx._L.vap_footprint_clearance(
         ctx.handle, B, cap, ptr(rows), ptr(counts), int(counts.shape[1]), len(foot), dptr(foot),
-        dptr(scene.field), scene.n_polygons, scene.poly_start.ctypes.data_as(_lib.ip), dptr(scene.poly_xy), scene.n_circles,
-        dptr(scene.circles), float(margin), ptr(res.get("row_clearance") if per_row else None), ptr(res["min_clearance"]),
+        *scene.c_args(), float(margin), ptr(res.get("row_clearance") if per_row else None), ptr(res["min_clearance"]),
         ptr(res["min_row"]), ptr(res["min_element"]), ptr(res["first_row"]), ptr(res["n_below"])), "vap_footprint_clearance")
     res["feasible"] = res["n_below"] == 0
     res["min_time"] = _time_at(rows, res["min_row"])

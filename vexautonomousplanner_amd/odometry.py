@@ -168,12 +168,10 @@ def rollouts(rows, counts, follower, perturbations, records, sensors=None, scene
     ctx.set_option(_lib.OPT_FOOTPRINT_CULL, 1 if cull else 0)
     fs = follower.as_struct()
     rs = rule.as_struct() if ns else None
-    sc = scene if ns else None
     _lib.check(ctx._L.vap_odometry_rollouts(
         ctx.handle, B, cap, ptr(rows), ptr(counts), int(counts.shape[1]), time_step, C.byref(fs), K, int(shared), ptr(pert),
         int(shared_odo), ptr(odo), ns, dptr(sens), C.byref(rs) if ns else None,
-        dptr(sc.field) if ns else None, sc.n_polygons if ns else 0, sc.poly_start.ctypes.data_as(_lib.ip) if ns else None,
-        dptr(sc.poly_xy) if ns else None, sc.n_circles if ns else 0, dptr(sc.circles) if ns else None,
+        *(scene.c_args() if ns else (None, 0, None, None, 0, None)),
         ptr(res["stats"]), ptr(res["stat_rows"]), ptr(res["worst"]), ptr(res["mean"]), ptr(res["worst_rollout"]),
         ptr(res["worst_row"]), ptr(res["n_exceeding"]), cap_exec, ptr(res.get("rows")), ptr(res.get("counts")),
         ptr(res.get("estimate_rows"))), "vap_odometry_rollouts")

@@ -87,9 +87,7 @@ def _check(scene, cell, radius, margin):
     nx, ny = int(np.ceil((f[2] - f[0]) / cell)), int(np.ceil((f[3] - f[1]) / cell))
     if nx * ny > MAX_CELLS:
         raise ValueError(f"a grid of {nx} x {ny} cells: at most {MAX_CELLS} cells (use a larger cell)")
-    args = (dptr(f), scene.n_polygons, scene.poly_start.ctypes.data_as(_lib.ip), dptr(scene.poly_xy), scene.n_circles,
-            dptr(scene.circles), cell, radius, margin)
-    return ny, nx, args
+    return ny, nx, scene.c_args() + (cell, radius, margin)
 
 
 def clearance_grid(scene, cell, radius, margin=0.0, out=None, device=0, ctx=None):

@@ -173,8 +173,7 @@ def readings(rows, counts, sensors, scene, others=None, others_counts=None, othe
     none = Bo == 0 or cap_o == 0
     _lib.check(ctx._L.vap_range_readings(
         ctx.handle, B, cap, ptr(rows), ptr(counts), int(counts.shape[1]), ns, dptr(sens),
-        dptr(scene.field), scene.n_polygons, scene.poly_start.ctypes.data_as(_lib.ip), dptr(scene.poly_xy), scene.n_circles,
-        dptr(scene.circles), 0 if none else Bo, 0 if none else cap_o, None if none else ptr(others), None if none else ptr(others_counts),
+        *scene.c_args(), 0 if none else Bo, 0 if none else cap_o, None if none else ptr(others), None if none else ptr(others_counts),
         1 if none else int(others_counts.shape[1]), 0 if none else len(foot_o), None if none else dptr(foot_o), shift_rows,
         want("range"), want("cos_incidence"), want("code"), ptr(res["status_counts"]), ptr(res["range_minmax"]),
         ptr(res["channels"])), "vap_range_readings")

@@ -307,8 +307,7 @@ def rollout_clearance(rows, counts, follower, perturbations, footprint, scene, m
     _lib.check(ctx._L.vap_rollout_clearance(
         ctx.handle, _lib.FOLLOWER_PURSUIT if pursuit else _lib.FOLLOWER_RAMSETE, C.cast(C.pointer(fs), C.c_void_p), B, cap,
         ptr(rows), ptr(counts), int(counts.shape[1]), time_step, K, int(shared), ptr(pert), len(foot), dptr(foot),
-        dptr(scene.field), scene.n_polygons, scene.poly_start.ctypes.data_as(_lib.ip), dptr(scene.poly_xy), scene.n_circles,
-        dptr(scene.circles), margin, ptr(res["stats"]), ptr(res["stat_rows"]), ptr(res["worst"]), ptr(res["mean"]),
+        *scene.c_args(), margin, ptr(res["stats"]), ptr(res["stat_rows"]), ptr(res["worst"]), ptr(res["mean"]),
         ptr(res["worst_rollout"]), ptr(res["worst_row"]), ptr(res["n_exceeding"]), ptr(res.get("n_unfinished")),
         ptr(res.get("route_status")), ptr(res["clearance"]), ptr(res["clear_rows"]), ptr(res["worst_clearance"]),
         ptr(res["worst_clear_rollout"]), ptr(res["worst_clear_row"]), ptr(res["worst_clear_element"]), ptr(res["mean_clearance"]),
