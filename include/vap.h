@@ -1080,7 +1080,8 @@ int vap_plan_seeds(vap_ctx *ctx, int R, int W, const double *d_starts, const dou
  *             e.y e.y)) clamped to [0, 1]; else the largest s), minus radius.  The row COVERS the cell iff clearance <
  *             margin: a cell is covered exactly when vap_plan_grid with the posed footprint as a scene polygon would not
  *             call it free on the polygon's account.  A row with a non-finite pose covers nothing and takes no part in
- *             the minimum.  No FMA.
+ *             the minimum; nor does a row with a COLLAPSED pose: one so large (|x| or |y| beyond about 2^53 times the
+ *             footprint's size) that some posed edge has e.x e.x + e.y e.y equal to zero, or not finite.  No FMA.
  *   instants  row r stands at instant r + shift_rows (any sign).
  *   outputs   per cell [ny][nx], over all B routes, any pointer may be NULL:
  *             d_first  int32, the smallest covering instant; INT_MAX if never covered;

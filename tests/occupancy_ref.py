@@ -36,8 +36,9 @@ def pose(rows, footprint, ftype=np.float64):
     return np.stack([x + (c * v[None, :, 0] - s * v[None, :, 1]), y + (s * v[None, :, 0] + c * v[None, :, 1])], axis=2)
 
 
-def row_clearance(P, px, py, radius, ftype=np.float64):
-    """(n, ny, nx): plan_ref.polygon_distance of the cell centres against each posed polygon P[r], minus radius."""
+def row_parts(P, px, py, ftype=np.float64):
+    """(smax, d2), each (n, ny, nx): over the edges of each posed polygon P[r] the largest signed distance of the cell centres
+    to an edge's line and the smallest squared point-to-segment distance (plan_ref.polygon_distance's two running values)."""
     n, m = P.shape[:2]
     px, py = px[None], py[None]
     smax = np.full((n,) + px.shape[1:], -np.inf, dtype=ftype)
@@ -51,7 +52,26 @@ def row_clearance(P, px, py, radius, ftype=np.float64):
         t = np.minimum(np.maximum((wx * ex + wy * ey) * (ftype(1) / ll), ftype(0)), ftype(1))
         dx, dy = wx - t * ex, wy - t * ey
         d2 = np.minimum(d2, dx * dx + dy * dy)
+    return smax, d2
+
+
+def row_clearance(P, px, py, radius, ftype=np.float64):
+    """(n, ny, nx): plan_ref.polygon_distance of the cell centres against each posed polygon P[r], minus radius."""
+    smax, d2 = row_parts(P, px, py, ftype)
     return np.where(smax > 0, np.sqrt(d2), smax) - ftype(radius)
+
+
+def taking_part(rows, footprint):
+    """(n,) bool: the rows that take part.  A row with a non-finite pose covers nothing and is no part of the minimum; nor is a
+    row whose pose is so large that a posed edge has a squared length of zero (or a non-finite one): the posed vertices are
+    taken in fp64 as the device takes them, whatever precision the clearance then runs in."""
+    r = np.asarray(rows, dtype=np.float64)
+    keep = np.isfinite(r[:, [4, 6, 7]]).all(axis=1)
+    with np.errstate(all="ignore"):
+        V = pose(r, footprint)
+        e = np.roll(V, -1, axis=1) - V
+        ll = e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]
+    return keep & ((ll > 0) & np.isfinite(ll)).all(axis=1)
 
 
 def occupancy(rows, counts, footprint, field, cell, radius, margin=0.0, shift_rows=0, hold_first=False, hold_last=True,
@@ -71,7 +91,7 @@ def occupancy(rows, counts, footprint, field, cell, radius, margin=0.0, shift_ro
         r = np.asarray(rows[b], dtype=np.float64)
         n = len(r) if counts is None else int(min(max(int(counts[b]), 0), len(r)))
         r = r[:n]
-        keep = np.isfinite(r[:, [4, 6, 7]]).all(axis=1)              # a non-finite pose covers nothing
+        keep = taking_part(r, footprint)
         for k0 in range(0, n, ROW_BLOCK):
             idx = np.arange(k0, min(k0 + ROW_BLOCK, n))[keep[k0:k0 + ROW_BLOCK]]
             if not len(idx):

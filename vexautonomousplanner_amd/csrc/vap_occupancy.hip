@@ -11,7 +11,8 @@
 //                   w = block, block + grid, ...
 //                     pose    wave 0, a lane per row: sincos once, the posed vertices, then per edge the edge vector,
 //                             1 / |e|^2 and |e| — six doubles an edge in LDS (n_foot x 48 B a row, 12 KB a chunk for a
-//                             rectangle, 48 KB for 16 vertices) — and the row's position and squared reach.  A wave
+//                             rectangle, 48 KB for 16 vertices) — and the row's position and squared reach (NaN for a
+//                             row that takes no part: a non-finite pose, or one so large that an edge has |e|^2 = 0).  A wave
 //                             min / max of (position -+ reach) gives the chunk's box and from it a range of cells.
 //                     test    a thread per cell of that range (of the whole grid when the minimum is asked for), a loop
 //                             over the chunk's rows at wave-uniform LDS addresses (broadcast reads).  A row is skipped
@@ -120,6 +121,7 @@ __global__ __launch_bounds__(kOccThreads) void k_occupancy(OccArgs a)
                 double sn, c;
                 sincos(-heading, &sn, &c);
                 double *e = s_edge + (size_t)tid * nf * kOccEdge;
+                bool posed = isfinite(heading) && isfinite(x) && isfinite(y);
                 for (int i = 0; i < nf; i++) {
                     const double bx = a.foot[2 * i], by = a.foot[2 * i + 1];
                     e[i * kOccEdge + 0] = x + (c * bx - sn * by);
@@ -133,15 +135,15 @@ __global__ __launch_bounds__(kOccThreads) void k_occupancy(OccArgs a)
                     e[i * kOccEdge + 3] = ey;
                     e[i * kOccEdge + 4] = 1.0 / ll;
                     e[i * kOccEdge + 5] = sqrt(ll);
+                    posed = posed && ll > 0.0 && ll < INFINITY;     // a pose so large that the vertices fall together
                 }
                 const double slack = a.slack + kCullSlack * (fabs(x) + fabs(y));
                 const double reach = reach0 + slack;
                 s_row[tid * kOccRow + 0] = x;
                 s_row[tid * kOccRow + 1] = y;
-                const bool finite = isfinite(heading) && isfinite(x) && isfinite(y);
-                s_row[tid * kOccRow + 2] = finite ? (reach >= 0.0 ? reach * reach : -1.0) : NAN;   // NaN: the row is left out
+                s_row[tid * kOccRow + 2] = posed ? (reach >= 0.0 ? reach * reach : -1.0) : NAN;    // NaN: the row is left out
                 s_row[tid * kOccRow + 3] = slack;
-                if (finite) {
+                if (posed) {
                     const double rr = reach >= 0.0 ? reach : 0.0;
                     bx0 = x - rr;
                     bx1 = x + rr;
@@ -194,7 +196,7 @@ __global__ __launch_bounds__(kOccThreads) void k_occupancy(OccArgs a)
 #pragma unroll 1
             for (int k = 0; k < nr; k++) {
                 const double *rw = s_row + k * kOccRow;
-                if (rw[2] != rw[2]) continue;                        // a non-finite pose
+                if (rw[2] != rw[2]) continue;                        // a non-finite or collapsed pose
                 if (a.cull) {
                     const double dx = px - rw[0], dy = py - rw[1], d2c = dx * dx + dy * dy;
                     bool need = d2c <= rw[2];                        // may cover
