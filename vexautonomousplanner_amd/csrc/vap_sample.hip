@@ -7,7 +7,7 @@
 // S <= kSampleChunk, need no such neighbour and are written by all threads).
 // LDS: distance table + interval slopes (16 KB), the path's coefficient blocks when they fit
 // (G <= kLdsCoefSegments; otherwise they are read through L1/L2, where a wavefront's consecutive
-// samples hit one or two blocks), and a 256-entry neighbour exchange.
+// samples hit one or two blocks), and a neighbour exchange of one record per thread.
 // Arithmetic: parameter/index path, derivative evaluation and curvature in fp64 (DESIGN.md
 // §Numerics); no fp64 division on the per-sample path.
 // ------------------------------------------------------------------------------------------------
@@ -23,6 +23,7 @@
 #include "vap_device.h"
 #include "vap_kernels.h"
 
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -35,8 +36,23 @@ static_assert(kGridRunBlockDoubles == kGridRunDoubles, "scratch sizing and run-t
 
 // HI (fp32 outputs only): also write the curvature and |dtheta| rows in fp64 (ok64, odth64) for the fp64
 // velocity recurrence behind fp32 outputs; the fp32 |dtheta| row is then optional (odth may be NULL).
-template <typename OT, bool COEF_LDS, bool HI, int PPB = 1>
-__global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int S, int tile, int tiles_per_block,
+//
+// HALVES: a thread's kSPT samples go through the phases of the tile body kSPT / HALVES at a time.  HALVES = 2 keeps
+// the fp64 derivative values, table entries and exchange values of two samples alive instead of four.  The instantiations
+// it serves (fp32 rows with the fp64 side rows) fit 128 registers without a spill — 117; the four-wide form 120, once the
+// fp32 position values are formed where the tile body says and not after the barrier — and are bound
+// to four waves per SIMD (k_sample_waves; two paths per workgroup are held to three by their 44 KB of LDS whatever their
+// registers).
+// align_bits (launch_sample): bit 0 = the caller's rows take 16-byte stores (row length and row bases), bit 1 = the fp64
+// side rows do.
+constexpr int k_sample_waves(int halves, int ppb) { return halves == 2 && ppb == 1 ? 4 : 3; }
+#ifdef VAP_SAMPLE_STATS   // developer build: in-kernel cycle shares per wave (costs scalar registers the kernel spills)
+#define VAP_STATS_PARAM , long long *__restrict__ stats
+#else
+#define VAP_STATS_PARAM
+#endif
+template <typename OT, bool COEF_LDS, bool HI, int PPB = 1, int HALVES = 1>
+__global__ __launch_bounds__(kSampleThreads, k_sample_waves(HALVES, PPB)) void k_sample(int B, int W, int S, int tile, int tiles_per_block, int align_bits,
                                                            const double *__restrict__ power,
                                                            const double *__restrict__ seg_rows,
                                                            const double *__restrict__ lut,
@@ -47,8 +63,9 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
                                                            OT *__restrict__ ox, OT *__restrict__ oy,
                                                            OT *__restrict__ oh, OT *__restrict__ ok,
                                                            OT *__restrict__ odth, double *__restrict__ ok64,
-                                                           double *__restrict__ odth64, long long *__restrict__ stats)
+                                                           double *__restrict__ odth64 VAP_STATS_PARAM)
 {
+    static_assert(HALVES == 1 || HALVES == 2, "a thread's samples go through the phases all at once or in two halves");
     static_assert(!HI || sizeof(OT) == 4, "the fp64 side rows belong to the fp32 output mode");
     // PPB paths per workgroup (blockIdx.y * PPB + pp).  Rows that are one tile long (config 5: 1024 samples) leave a
     // workgroup as much time in staging — a chain of dependent memory round trips: meta, aux, tables, run table — as in
@@ -56,10 +73,13 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
     extern __shared__ __attribute__((aligned(16))) double s_coef[];   // PPB * G * kCoefDoubles when COEF_LDS
     __shared__ double sD_all[PPB * kLutN], sWt_all[PPB * kLutN];
     // neighbour exchange, double-buffered by tile parity (one barrier per tile)
-    __shared__ double s_dx[2][kSampleThreads], s_dy[2][kSampleThreads];
-    __shared__ int s_j[2][kSampleThreads];
-    __shared__ OT s_th[2][kSampleThreads];
+    // (one record per thread: one LDS address serves the four values; the entry past the last thread is read by the last
+    // thread of a one-tile row, whose last sample has no neighbour, and never used)
+    struct Neighbour { double dx, dy; OT th; int j; };
+    __shared__ Neighbour s_nb[2][kSampleThreads + 1];
+#ifdef VAP_SAMPLE_STATS
     const long long ts0 = stats ? __builtin_amdgcn_s_memtime() : 0;
+#endif
     const int tid = threadIdx.x;
     const int G = W - 1;
     const int tile0 = blockIdx.x * tiles_per_block;
@@ -67,8 +87,9 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
     // tile == kSampleChunk: the whole row is one tile, so the last thread's last sample is the row's last
     // and needs no neighbour — every thread writes
     const bool writer = tile == kSampleChunk || tid < kSampleThreads - 1;
-    constexpr int VW = 16 / sizeof(OT);   // elements per 16-byte store
-    const bool aligned = (S % VW) == 0;   // rows (and tile starts, multiples of kSPT) then start 16-byte aligned
+    // rows (and tile starts, multiples of kSPT) start 16-byte aligned: S % VW == 0 and the row bases, tested once per launch
+    const bool aligned = (align_bits & 1) != 0;
+    const bool aligned_hi = (align_bits & 2) != 0;   // the fp64 side rows: S even and their bases
 
     // per path: the scalars of its grid and tables
     int p_b[PPB], p_N[PPB], p_nruns[PPB];
@@ -212,7 +233,9 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
     }
     __syncthreads();
     asm volatile("" ::"v"(run_touch));
+#ifdef VAP_SAMPLE_STATS
     const long long ts1 = stats ? __builtin_amdgcn_s_memtime() : 0;
+#endif
     const double end_param = (double)(W - 1);
     const int tab_n = W * kSamplesPerNode;
     int tiles_done = 0;   // parity of the neighbour exchange
@@ -267,7 +290,7 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
         };
         auto store_hi = [&](double *dst, const double v[kSPT]) {   // rows of S doubles: 16-byte aligned when S is even
             if (!writer) return;
-            if ((S & 1) == 0 && kbase + kSPT <= S) {
+            if (aligned_hi && kbase + kSPT <= S) {
                 *reinterpret_cast<double2 *>(dst + row + kbase) = make_double2(v[0], v[1]);
                 *reinterpret_cast<double2 *>(dst + row + kbase + 2) = make_double2(v[2], v[3]);
             } else {
@@ -290,6 +313,7 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
         // 16-byte aligned): the same body without the end-of-path selects, chosen per tile — wave-uniform
         auto tile_body = [&](auto interior_tag) {
             constexpr bool INTERIOR = decltype(interior_tag)::value;
+        constexpr int HS = kSPT / HALVES;   // samples that go through a phase side by side
         OT vx[kSPT], vy[kSPT], vh[kSPT], vk[kSPT], vd[kSPT];
         double vd64[HI ? kSPT : 1];
         [[maybe_unused]] double kap_even = 0.0;   // HI: the fp64 curvature row leaves in pairs as soon as a pair exists
@@ -301,24 +325,88 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
         double d1x[kSPT], d1y[kSPT];
         int jjv[kSPT];
         int idx = 0;
-        // Phase A, the four samples' parameters and table entries side by side; the redo of a sample that sits a few ulps
-        // from a decision point (rare) is ONE block after them instead of a divergent branch inside every sample
-        double tA[kSPT], sA[kSPT];
-        int idxA[kSPT];
-        bool redo[kSPT], any_redo = false;
-        // A1: distances and table entries.  The first sample searches the table (fixed halvings, no loop); each following
-        // one walks on from its predecessor's entry, which it passes at most once or twice where a table interval is longer
-        // than dd (config 3: ~10 samples per interval) — two entries in one LDS read, two compare-and-selects.  A sample
-        // that took both steps may have further to go: ONE rarely taken block after the four finishes the walk
-        // (`while (idx < kLutN - 1 && sD[idx] < s) idx++`, the same entry in every case).
-        bool walk_on[kSPT], any_walk = false;
+        const int pb = tiles_done & 1;
+        tiles_done++;
+        // |heading[k+1] - heading[k]| of the reference's raw (un-unwrapped) atan2 values, for the thread's samples GA..GB:
+        // each needs its right-hand neighbour's tangent, table entry and heading — the next sample of the thread, or, for
+        // the thread's last sample, the next thread's first (the exchange: only after the tile's barrier)
+        auto dtheta_range = [&](auto ga_tag, auto gb_tag) {
+            constexpr int GA = decltype(ga_tag)::value, GB = decltype(gb_tag)::value, GN = GB - GA + 1;
+            if constexpr (HI && sizeof(OT) == 4) {
+                // the samples side by side, no branch per sample: the series for all of them, ONE rarely taken block
+                // for samples outside its range, then the 2*pi multiples (the same operations as dtheta_f64)
+                double dl[GN];
+                bool act[GN], gen[GN];
+                double nxv[GN], nyv[GN];
+                OT nthv[GN];
+                bool any_gen = false;
 #pragma unroll
-        for (int i = 0; i < kSPT; i++) {
-            const int k = INTERIOR ? kbase + i : (kbase + i < N - 1 ? kbase + i : N - 1);
-            if (i > 0) sk = sk + dd;
+                for (int q = 0; q < GN; q++) {
+                    const int i = GA + q;
+                    const int k = kbase + i;
+                    nxv[q] = (i + 1 < kSPT) ? d1x[(i + 1) % kSPT] : s_nb[pb][tid + 1].dx;
+                    nyv[q] = (i + 1 < kSPT) ? d1y[(i + 1) % kSPT] : s_nb[pb][tid + 1].dy;
+                    const int nj = (i + 1 < kSPT) ? jjv[(i + 1) % kSPT] : s_nb[pb][tid + 1].j;
+                    nthv[q] = (i + 1 < kSPT) ? vh[(i + 1) % kSPT] : s_nb[pb][tid + 1].th;
+                    act[q] = (INTERIOR || k < N - 1) && nj != jjv[i];
+                    dl[q] = dtheta_f64_series(d1x[i], d1y[i], nxv[q], nyv[q], gen[q]);
+                    gen[q] = gen[q] && act[q];
+                    any_gen |= gen[q];
+                }
+                if (__builtin_expect(any_gen, 0)) {
+#pragma unroll
+                    for (int q = 0; q < GN; q++)
+                        if (gen[q]) dl[q] = dtheta_f64_general(d1x[GA + q], d1y[GA + q], nxv[q], nyv[q]);
+                }
+#pragma unroll
+                for (int q = 0; q < GN; q++) {
+                    const int i = GA + q;
+                    const double v = dtheta_f64_wrap(dl[q], vh[i], nthv[q]);
+                    vd64[i] = act[q] ? v : vd64[i];   // (the fp32 row, where the staged API asks for it: rounded at the store)
+                }
+            } else {
+#pragma unroll
+                for (int i = GA; i <= GB; i++) {
+                    const int k = kbase + i;
+                    if (INTERIOR || k < N - 1) {
+                        const double nx = (i + 1 < kSPT) ? d1x[(i + 1) % kSPT] : s_nb[pb][tid + 1].dx;
+                        const double ny = (i + 1 < kSPT) ? d1y[(i + 1) % kSPT] : s_nb[pb][tid + 1].dy;
+                        const int nj = (i + 1 < kSPT) ? jjv[(i + 1) % kSPT] : s_nb[pb][tid + 1].j;
+                        const OT nth = (i + 1 < kSPT) ? vh[(i + 1) % kSPT] : s_nb[pb][tid + 1].th;
+                        if constexpr (sizeof(OT) == 8) {
+                            vd[i] = fabs(nth - vh[i]);
+                        } else if constexpr (HI) {
+                            if (nj != jjv[i]) vd64[i] = dtheta_f64(d1x[i], d1y[i], nx, ny, vh[i], nth);
+                            vd[i] = (OT)vd64[i];   // (only stored when the staged API asked for the fp32 row as well)
+                        } else {
+                            if (nj != jjv[i]) vd[i] = dtheta_f32(d1x[i], d1y[i], nx, ny, vh[i], nth);
+                        }
+                    }
+                }
+            }
+        };
+#pragma unroll
+        for (int h = 0; h < HALVES; h++) {
+        const int g0 = h * HS;   // the half's first sample of the thread
+        // Phase A, the samples' parameters and table entries side by side; the redo of a sample that sits a few ulps
+        // from a decision point (rare) is ONE block after them instead of a divergent branch inside every sample
+        double tA[HS], sA[HS];
+        int idxA[HS];
+        bool redo[HS], any_redo = false;
+        // A1: distances and table entries.  The thread's first sample searches the table (fixed halvings, no loop); each
+        // following one walks on from its predecessor's entry, which it passes at most once or twice where a table interval
+        // is longer than dd (config 3: ~10 samples per interval) — two entries in one LDS read, two compare-and-selects.  A
+        // sample that took both steps may have further to go: ONE rarely taken block after the side-by-side samples finishes
+        // the walk (`while (idx < kLutN - 1 && sD[idx] < s) idx++`, the same entry in every case).
+        bool walk_on[HS], any_walk = false;
+#pragma unroll
+        for (int i = 0; i < HS; i++) {
+            const int g = g0 + i;
+            const int k = INTERIOR ? kbase + g : (kbase + g < N - 1 ? kbase + g : N - 1);
+            if (g > 0) sk = sk + dd;
             const double s = INTERIOR ? sk : ((k == N - 1) ? total : sk);
             walk_on[i] = false;
-            if (i == 0) {
+            if (g == 0) {
                 idx = lut_search_left_fixed(sD, s);
                 if constexpr (!INTERIOR) idx = idx < 1 ? 1 : idx;
             } else {   // (idx >= 1 already: the walk only moves on)
@@ -335,7 +423,7 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
         }
         if (__builtin_expect(any_walk, 0)) {
 #pragma unroll
-            for (int i = 1; i < kSPT; i++) {
+            for (int i = (g0 == 0 ? 1 : 0); i < HS; i++) {
                 if (walk_on[i]) {
                     int ix = idxA[i];
                     while (ix < kLutN - 1 && sD[ix] < sA[i]) ix++;
@@ -343,9 +431,10 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
                 }
             }
         }
+        if constexpr (HALVES > 1) idx = idxA[HS - 1];   // the next half walks on from this half's last entry
         // A2: parameters and property-table entries
 #pragma unroll
-        for (int i = 0; i < kSPT; i++) {
+        for (int i = 0; i < HS; i++) {
             const double s = sA[i];
             const int idx = idxA[i];
             const double d0 = sD[idx - 1];
@@ -361,26 +450,27 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
             double t = fma(wslope, s - d0, t0);
             if constexpr (!INTERIOR) t = s >= total ? end_param : t;
             bool near;
-            jjv[i] = table_index_fast(t, tab_n, inv_tstep, near);
+            jjv[g0 + i] = table_index_fast(t, tab_n, inv_tstep, near);
             tA[i] = t;
             redo[i] = near && !exact;
             any_redo |= redo[i];
         }
         if (__builtin_expect(any_redo, 0)) {
 #pragma unroll
-            for (int i = 0; i < kSPT; i++) {
+            for (int i = 0; i < HS; i++) {
                 if (redo[i]) {   // the reference's own rounding (SM:311-317)
                     const int ix = idxA[i];
                     const double d0 = sD[ix - 1], t0 = (double)(ix - 1) * lstep;
                     const double t1 = (ix == kLutN - 1) ? t_max : (double)ix * lstep;
                     tA[i] = t0 + (t1 - t0) * (sA[i] - d0) / (sD[ix] - d0);
-                    jjv[i] = table_index(tA[i], tab_n, end_param);
+                    jjv[g0 + i] = table_index(tA[i], tab_n, end_param);
                 }
             }
         }
 #pragma unroll
-        for (int i = 0; i < kSPT; i++) {
-            const double t = tA[i];
+        for (int q = 0; q < HS; q++) {
+            const int i = g0 + q;
+            const double t = tA[q];
             const int jj = jjv[i];
             const double tp = (jj == tab_n - 1) ? end_param : (double)jj * tstep;
             double lt;
@@ -417,7 +507,7 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
                 } else if (writer) {
                     const int ke = kbase + i - 1;
                     const double v0 = (INTERIOR || ke < N) ? kap_even : 0.0, v1 = (INTERIOR || ke + 1 < N) ? kap : 0.0;
-                    if (INTERIOR || ((S & 1) == 0 && ke + 2 <= S)) {
+                    if (INTERIOR || (aligned_hi && ke + 2 <= S)) {
                         *reinterpret_cast<double2 *>(ok64 + row + ke) = make_double2(v0, v1);
                     } else {
                         if (ke < S) ok64[row + ke] = v0;
@@ -428,7 +518,6 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
             vh[i] = heading_of<OT>(ey, ex);                                       // SM:536
             d1x[i] = ex;
             d1y[i] = ey;
-            jjv[i] = jj;
             // SM:204-215 get_point_at_parameter(t) at the sample's own parameter
             normalize_inside(t, G, lt, sg);
             c = coef + sg * kCoefDoubles;
@@ -437,72 +526,31 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
                 const float ltf = (float)lt;
                 vx[i] = horner5f(cf, ltf);
                 vy[i] = horner5f(cf + 6, ltf);
+                // (formed here, not after the barrier where they are stored: until then the twelve coefficients and the
+                // parameter would wait in registers in place of the two values)
+                asm volatile("" : "+v"(vx[i]), "+v"(vy[i]));
             } else {
                 vx[i] = horner5(c + kCoefP, lt);
                 vy[i] = horner5(c + kCoefP + 6, lt);
             }
             vd[i] = (OT)0;
         }
-        const int pb = tiles_done & 1;
-        tiles_done++;
-        s_dx[pb][tid] = d1x[0];
-        s_dy[pb][tid] = d1y[0];
-        s_j[pb][tid] = jjv[0];
-        s_th[pb][tid] = vh[0];
+        if (h == 0) {   // the thread's first sample is its left-hand neighbour's right-hand neighbour
+            Neighbour *nb = &s_nb[pb][tid];
+            nb->dx = d1x[0];
+            nb->dy = d1y[0];
+            nb->j = jjv[0];
+            nb->th = vh[0];
+        }
+        if constexpr (HALVES == 2) {
+            // the first half's samples but its last: their neighbours are at hand, and their tangents need not wait
+            if (h == 0) dtheta_range(std::integral_constant<int, 0>{}, std::integral_constant<int, HS - 2>{});
+        }
+        }   // halves
         __syncthreads();
         if (writer) {
-            // |heading[k+1] - heading[k]| of the reference's raw (un-unwrapped) atan2 values
-            if constexpr (HI && sizeof(OT) == 4) {
-                // the four samples side by side, no branch per sample: the series for all of them, ONE rarely taken block
-                // for samples outside its range, then the 2*pi multiples (the same operations as dtheta_f64)
-                double dl[kSPT];
-                bool act[kSPT], gen[kSPT];
-                double nxv[kSPT], nyv[kSPT];
-                OT nthv[kSPT];
-                bool any_gen = false;
-#pragma unroll
-                for (int i = 0; i < kSPT; i++) {
-                    const int k = kbase + i;
-                    nxv[i] = (i + 1 < kSPT) ? d1x[(i + 1) % kSPT] : s_dx[pb][tid + 1];
-                    nyv[i] = (i + 1 < kSPT) ? d1y[(i + 1) % kSPT] : s_dy[pb][tid + 1];
-                    const int nj = (i + 1 < kSPT) ? jjv[(i + 1) % kSPT] : s_j[pb][tid + 1];
-                    nthv[i] = (i + 1 < kSPT) ? vh[(i + 1) % kSPT] : s_th[pb][tid + 1];
-                    act[i] = (INTERIOR || k < N - 1) && nj != jjv[i];
-                    dl[i] = dtheta_f64_series(d1x[i], d1y[i], nxv[i], nyv[i], gen[i]);
-                    gen[i] = gen[i] && act[i];
-                    any_gen |= gen[i];
-                }
-                if (__builtin_expect(any_gen, 0)) {
-#pragma unroll
-                    for (int i = 0; i < kSPT; i++)
-                        if (gen[i]) dl[i] = dtheta_f64_general(d1x[i], d1y[i], nxv[i], nyv[i]);
-                }
-#pragma unroll
-                for (int i = 0; i < kSPT; i++) {
-                    const double v = dtheta_f64_wrap(dl[i], vh[i], nthv[i]);
-                    vd64[i] = act[i] ? v : vd64[i];
-                    vd[i] = (INTERIOR || kbase + i < N - 1) ? (OT)vd64[i] : vd[i];
-                }
-            } else {
-#pragma unroll
-            for (int i = 0; i < kSPT; i++) {
-                const int k = kbase + i;
-                if (INTERIOR || k < N - 1) {
-                    const double nx = (i + 1 < kSPT) ? d1x[(i + 1) % kSPT] : s_dx[pb][tid + 1];
-                    const double ny = (i + 1 < kSPT) ? d1y[(i + 1) % kSPT] : s_dy[pb][tid + 1];
-                    const int nj = (i + 1 < kSPT) ? jjv[(i + 1) % kSPT] : s_j[pb][tid + 1];
-                    const OT nth = (i + 1 < kSPT) ? vh[(i + 1) % kSPT] : s_th[pb][tid + 1];
-                    if constexpr (sizeof(OT) == 8) {
-                        vd[i] = fabs(nth - vh[i]);
-                    } else if constexpr (HI) {
-                        if (nj != jjv[i]) vd64[i] = dtheta_f64(d1x[i], d1y[i], nx, ny, vh[i], nth);
-                        vd[i] = (OT)vd64[i];   // (only stored when the staged API asked for the fp32 row as well)
-                    } else {
-                        if (nj != jjv[i]) vd[i] = dtheta_f32(d1x[i], d1y[i], nx, ny, vh[i], nth);
-                    }
-                }
-            }
-            }
+            // the rest: from the first half's last sample (its neighbour is the second half's first) to the thread's last
+            dtheta_range(std::integral_constant<int, (HALVES == 2 ? HS - 1 : 0)>{}, std::integral_constant<int, kSPT - 1>{});
             if (!INTERIOR && k0 + kSampleChunk > N) {   // only the path's last tile has samples to blank
 #pragma unroll
                 for (int i = 0; i < kSPT; i++)
@@ -513,14 +561,25 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
             }
             store_vec(ox, vx); store_vec(oy, vy); store_vec(oh, vh); store_vec(ok, vk);
             if constexpr (HI) store_hi(odth64, vd64);
-            store_vec(odth, vd);
+            if constexpr (HI && sizeof(OT) == 4) {
+                // vd64 is zero wherever the fp32 row is (samples without a right-hand neighbour, blanked samples): the
+                // fp32 row is its rounding, formed only when there is a row to store
+                if (odth) {
+#pragma unroll
+                    for (int i = 0; i < kSPT; i++) vd[i] = (OT)vd64[i];
+                    store_vec(odth, vd);
+                }
+            } else {
+                store_vec(odth, vd);
+            }
         }
             };
-        const bool interior = k0 > 0 && k0 + kSampleThreads * kSPT < N - 1 && aligned && (S & 1) == 0 && k0 + kSampleThreads * kSPT <= S;
+        const bool interior = k0 > 0 && k0 + kSampleThreads * kSPT < N - 1 && aligned && aligned_hi && k0 + kSampleThreads * kSPT <= S;
         if (interior) tile_body(std::true_type{});
         else tile_body(std::false_type{});
     }
     }   // paths of this workgroup
+#ifdef VAP_SAMPLE_STATS
     if (stats && (tid & 63) == 0) {
         long long *st = stats + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + (tid >> 6)) * 4;
         st[0] = ts1 - ts0;                                 // staging + barrier
@@ -528,6 +587,7 @@ __global__ __launch_bounds__(kSampleThreads, 3) void k_sample(int B, int W, int 
         st[2] = 0;
         st[3] = 0;
     }
+#endif
 }
 
 hipError_t launch_sample(hipStream_t st, bool f64, int B, int W, int S, const double *pw, const double *lut,
@@ -549,22 +609,37 @@ hipError_t launch_sample(hipStream_t st, bool f64, int B, int W, int S, const do
     const int ppb = (n_tiles == 1 && B >= 8192 && in_lds && (W - 1) <= 16) ? 2 : 1;
     const dim3 grid((n_tiles + tiles_per_block - 1) / tiles_per_block, (B + ppb - 1) / ppb);
     const size_t lds = in_lds ? sizeof(double) * (size_t)ppb * (W - 1) * kCoefDoubles : 0;
-    // developer knob: VAP_SAMPLE_STATS=1 prints in-kernel cycle shares per wave (synchronises!)
+    // 16-byte stores: the row length and the row bases, tested here once per launch (bit 0: the caller's rows, bit 1:
+    // the fp64 side rows)
+    const size_t vw = f64 ? 2 : 4;
+    const uintptr_t bases = (uintptr_t)x | (uintptr_t)y | (uintptr_t)h | (uintptr_t)k | (uintptr_t)dth;
+    const uintptr_t bases_hi = (uintptr_t)k64 | (uintptr_t)dth64;
+    const int align_bits = (((size_t)S % vw) == 0 && (bases & 15) == 0 ? 1 : 0) | ((S & 1) == 0 && (bases_hi & 15) == 0 ? 2 : 0);
+#ifdef VAP_SAMPLE_STATS
+    // developer build (-DVAP_SAMPLE_STATS): VAP_SAMPLE_STATS=1 prints in-kernel cycle shares per wave (synchronises!)
     static const bool want_stats = getenv("VAP_SAMPLE_STATS") != nullptr;
     long long *stats = nullptr;
     const size_t n_waves = (size_t)grid.x * grid.y * 4;
     if (want_stats) (void)hipMalloc(&stats, n_waves * 4 * sizeof(long long));
-#define VAP_SAMPLE(OT_, LDS_, HI_, PPB_)                                                                            \
-    hipLaunchKernelGGL((k_sample<OT_, LDS_, HI_, PPB_>), grid, dim3(kSampleThreads), lds, st, B, W, S, tile, tiles_per_block, pw, seg, lut, \
-                       slopes, meta, aux, runs, (OT_ *)x, (OT_ *)y, (OT_ *)h, (OT_ *)k, (OT_ *)dth, k64, dth64, stats)
+#define VAP_STATS_ARG , stats
+#else
+#define VAP_STATS_ARG
+#endif
+#define VAP_SAMPLE(OT_, LDS_, HI_, PPB_, HALVES_)                                                                   \
+    hipLaunchKernelGGL((k_sample<OT_, LDS_, HI_, PPB_, HALVES_>), grid, dim3(kSampleThreads), lds, st, B, W, S, tile, tiles_per_block, \
+                       align_bits, pw, seg, lut, slopes, meta, aux, runs, (OT_ *)x, (OT_ *)y, (OT_ *)h, (OT_ *)k, (OT_ *)dth, k64,   \
+                       dth64 VAP_STATS_ARG)
+    // HALVES = 2 (four waves per SIMD) where the instantiation fits 128 registers without a spill
     if (ppb == 2) {
-        if (f64) VAP_SAMPLE(double, true, false, 2);
-        else if (hi) VAP_SAMPLE(float, true, true, 2);
-        else VAP_SAMPLE(float, true, false, 2);
-    } else if (f64) { if (in_lds) VAP_SAMPLE(double, true, false, 1); else VAP_SAMPLE(double, false, false, 1); }
-    else if (hi) { if (in_lds) VAP_SAMPLE(float, true, true, 1); else VAP_SAMPLE(float, false, true, 1); }
-    else { if (in_lds) VAP_SAMPLE(float, true, false, 1); else VAP_SAMPLE(float, false, false, 1); }
+        if (f64) VAP_SAMPLE(double, true, false, 2, 1);
+        else if (hi) VAP_SAMPLE(float, true, true, 2, 2);
+        else VAP_SAMPLE(float, true, false, 2, 1);
+    } else if (f64) { if (in_lds) VAP_SAMPLE(double, true, false, 1, 1); else VAP_SAMPLE(double, false, false, 1, 1); }
+    else if (hi) { if (in_lds) VAP_SAMPLE(float, true, true, 1, 2); else VAP_SAMPLE(float, false, true, 1, 2); }
+    else { if (in_lds) VAP_SAMPLE(float, true, false, 1, 1); else VAP_SAMPLE(float, false, false, 1, 1); }
 #undef VAP_SAMPLE
+#undef VAP_STATS_ARG
+#ifdef VAP_SAMPLE_STATS
     if (stats) {
         std::vector<long long> h(n_waves * 4);
         (void)hipStreamSynchronize(st);
@@ -576,6 +651,7 @@ hipError_t launch_sample(hipStream_t st, bool f64, int B, int W, int S, const do
         fprintf(stderr, "[sample grid %ux%u, %d tiles/block] per-wave mean ticks: stage %.0f tiles %.0f\n", grid.x,
                 grid.y, tiles_per_block, sum[0] / n_waves, sum[1] / n_waves);
     }
+#endif
     return hipGetLastError();
 }
 
