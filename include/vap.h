@@ -63,7 +63,21 @@ typedef struct {
     double max_vel, max_acc, max_dec, friction_coef, max_jerk, track_width;
 } vap_constraints;
 
-/* Per-path flag bits written to flags[b]. */
+/* Per-path flag bits written to flags[b].
+ *
+ * A path flagged VAP_FLAG_DEGENERATE (two equal neighbouring waypoints, a path of zero length, a NaN or infinite
+ * coordinate, coordinates whose squared distances overflow or underflow) lives in its batch on these terms, held by
+ * tests/test_gpu_bad_paths.py:
+ *   - its rows (x, y, heading, curvature, velocity, time-domain rows) are unspecified and may be non-finite; meta[0..2]
+ *     may be NaN;
+ *   - its meta[3] is an integer in [0, S] and its time-domain row count lies in [0, capacity_rows]: nothing is written
+ *     outside the rows the caller gave it;
+ *   - no other path's outputs or flags depend on it: the rows, meta and flags of every other path of the call are, bit for
+ *     bit, those of the same batch with a good path in its place — in the fused and the staged calls, vap_profile_routes,
+ *     fp32 / fp64 rows and the fp32 recurrence, every velocity kernel option but VAP_VELOCITY_RELAX_ROUNDS and the long-row
+ *     look-back kernel (a row per launch group: no sharing), the three time-domain kernels, vap_time_insert_events,
+ *     vap_route_limits + vap_velocity_pass_limits, vap_curve_caps, vap_velocity_conditioning and vap_closest_points;
+ *   - vap_search_update reads its flag as cost +inf and ranks it behind every finite candidate. */
 #define VAP_FLAG_DEGENERATE 1u /* zero-length segment or non-finite value met during fit/LUT */
 #define VAP_FLAG_TRUNCATED 2u  /* grid needed more than S samples; the first S were produced */
 #define VAP_FLAG_NOCONVERGE 4u /* velocity relaxation hit its round limit (never expected) */

@@ -321,6 +321,18 @@ __device__ __forceinline__ int table_index(double t, int tab_n, double end_param
     return (int)(frac > 0.5 ? j - 1 : j);
 }
 
+// i held to [0, hi] (hi >= 0) in ONE instruction: the median of i, 0 and hi.  The compiler forms v_med3_i32 only from
+// two constant bounds; written as max and min against a bound in a register it costs one instruction more than the
+// upper bound alone did, on every sample.
+// hi must be WAVE-UNIFORM (a kernel argument or something derived from one, as tab_n - 1 and G - 1 are): it is a scalar
+// register operand, and for a bound that differs between lanes the compiler would quietly take lane 0's for all of them.
+__device__ __forceinline__ int index_inside(int i, int hi)
+{
+    int r;
+    asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(i), "s"(hi));
+    return r;
+}
+
 // Fast form of the same index: with x = t * (1/step), ceil(x) is the searchsorted-left position
 // unless x sits within 1e-8 of an integer (x is within ~1e-9 of t/step and of the NumPy-rounded
 // table parameters), and the "t % 1 > 0.5" decision is safe unless t is within 1e-11 of an integer
@@ -330,8 +342,8 @@ __device__ __forceinline__ int table_index_fast(double t, int tab_n, double inv_
 {
     const double x = t * inv_step;
     const double cx = ceil(x);
-    int j = (int)cx;
-    j = j > tab_n - 1 ? tab_n - 1 : j;
+    // (both ends: a flagged path's parameter can be negative or non-finite — NaN converts to 0, -inf to INT_MIN)
+    const int j = index_inside((int)cx, tab_n - 1);
     const double dxi = cx - x;                 // in [0,1): distance (in entries) up to the chosen entry
     const double frac = t - floor(t);          // t % 1 for t >= 0
     const double fh = fabs(frac - 0.5);
@@ -344,8 +356,7 @@ __device__ __forceinline__ int table_index_fast(double t, int tab_n, double inv_
 // from 1 to 1-2^-53; that is the only difference.)
 __device__ __forceinline__ void normalize_inside(double t, int G, double &lt, int &idx)
 {
-    int i = (int)t;
-    i = i > G - 1 ? G - 1 : i;
+    const int i = index_inside((int)t, G - 1);   // (the lower bound is for a flagged path's parameter only)
     lt = t - (double)i;
     idx = i;
 }

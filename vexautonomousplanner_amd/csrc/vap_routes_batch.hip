@@ -325,7 +325,8 @@ __global__ __launch_bounds__(kRouteThreads) void k_sample_routes(int W, int NS, 
             }
             // global entry e = si*1000 + j is the first with distances[e] >= s.  e == 0 cannot be (s > 0 = distances[0]);
             // j == 0 of a later spline: its predecessor is the previous spline's last entry (SM:457-462 concatenation)
-            const int ps = j > 0 ? si : si - 1, pj = j > 0 ? j - 1 : kLutN - 1;
+            // (a route whose length is NaN sends s = NaN here, and the search answers e == 0: it reads its own first entry)
+            const int ps = (j > 0 || si == 0) ? si : si - 1, pj = j > 0 ? j - 1 : (si == 0 ? 0 : kLutN - 1);
             const double d0 = dist_at(ps, pj), d1 = dist_at(si, j);
             const double t0 = (pj == kLutN - 1 ? s_sp[ps * kSplineStride + 0] : (double)pj * s_step[ps]) + s_sp[ps * kSplineStride + 2];
             const double t1 = (j == kLutN - 1 ? s_sp[si * kSplineStride + 0] : (double)j * s_step[si]) + s_sp[si * kSplineStride + 2];

@@ -574,7 +574,10 @@ __global__ __launch_bounds__(kSampleThreads, k_sample_waves(HALVES, PPB)) void k
             }
         }
             };
-        const bool interior = k0 > 0 && k0 + kSampleThreads * kSPT < N - 1 && aligned && aligned_hi && k0 + kSampleThreads * kSPT <= S;
+        // (a path without a usable length — flagged VAP_FLAG_DEGENERATE, its table NaN from some entry on — still has N = S on
+        // the fixed grid: it never takes the interior body, whose table search may answer entry 0 for it and then reads sD[-1])
+        const bool interior = k0 > 0 && k0 + kSampleThreads * kSPT < N - 1 && aligned && aligned_hi && k0 + kSampleThreads * kSPT <= S &&
+                              total > 0.0 && total < __builtin_inf();
         if (interior) tile_body(std::true_type{});
         else tile_body(std::false_type{});
     }
