@@ -245,10 +245,17 @@ int vap_velocity_pass(vap_ctx *ctx, vap_dtype dt, int B, int S, const vap_constr
  * A node (parameter = its index) or action point (parameter t) takes effect at the first loop sample whose
  * parameter has reached it (MPG:125, 141-145) — a node before an action point on the same sample, and an
  * action point that would fall on its predecessor's sample never does, nor do those after it (the
- * reference looks at one pending action point per sample).
+ * reference looks at one pending action point per sample).  The list is taken in the order given, never sorted:
+ * one whose parameter lies behind its predecessor's sample is such a case.  An action point at t <= 0 never takes
+ * effect (the previous parameter starts at 0 and must be below t, MPG:144) and blocks the rest of the list, as does
+ * one at t >= W - 1 (every loop parameter is below it) or NaN; +inf is the padding.  Nodes are counted, not looked up:
+ * the j-th loop step whose parameter wraps ((prev_t % 1) > (t % 1), MPG:124) carries node j's attributes, so where one
+ * step of the grid passes two nodes (a segment shorter than dd) the later nodes take effect one node late and the
+ * last of them never.  stop, max_velocity and max_acceleration of the LAST node are never read; of node 0 only
+ * max_velocity and max_acceleration are (MPG:100-107), its stop is not.
  *   d_node_max_velocity / d_node_max_acceleration [B][W]  (<= 0: none; NULL array: none)  MPG:100-107, 129-137
  *   d_node_stop                                   [B][W]  int32 (NULL: none)              MPG:126-127
- *   d_action_t                                    [B][M]  in route order, > 0; pad with +inf
+ *   d_action_t                                    [B][M]  in the list's order (see above); pad with +inf
  *   d_action_max_velocity / _max_acceleration / _stop [B][M]  (NULL arrays: none)         MPG:146-160
  *   d_vcap, d_acc_forward, d_acc_backward [B][S], d_dec_backward [B] out, of type vap_limit_rows_dtype(ctx, dt):
  *                                    the three acceleration outputs are optional as a set (routes that do not
@@ -350,7 +357,11 @@ int vap_time_profile(vap_ctx *ctx, vap_dtype dt, int B, int W, int S, const doub
  * position / velocity / acceleration / angular velocity, the last heading and point) where it is passed,
  * and every later row moves by as many rows and time steps; actions_map records the row count at which
  * each action point fires (the reference's own test, MPG:546-553: one that lands exactly on a row's
- * parameter, or shares a row interval with its predecessor, never fires and blocks the ones after it).
+ * parameter, or shares a row interval with its predecessor, never fires and blocks the ones after it; so
+ * does one at t <= 0, at t >= W - 1, NaN, or behind its predecessor in an unsorted list — the list is taken in
+ * the order given, and what fires here is decided by the rows alone, not by the distance grid of
+ * vap_route_limits).  The wait of node 0 comes before row 0 with node 0's own heading (MPG:459-476); the wait of
+ * the last node is never inserted (the loop ends before it is passed).
  *   d_rows_in [B][capacity_in][8], d_counts_in [B][2], d_nodes_map_in [B][W]   from vap_time_profile
  *   d_node_wait   [B][W]  seconds (NULL: none)       d_action_t / d_action_wait [B][M] (pad t with +inf)
  *   d_rows_out    [B][capacity_out][8]  (must not alias d_rows_in)

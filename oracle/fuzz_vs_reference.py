@@ -3,7 +3,10 @@
 tests/golden/ pins the oracle on ~40 curated cases; this script draws random routes (plain, stops,
 per-node / action-point limits, tangent overrides, reverse / turn nodes, waits) and random robots,
 runs both the reference (imported from /root/reference, build container only) and the oracle, and
-compares forward_backward_pass and the 9-tuple of generate_motion_profile.
+compares forward_backward_pass and the 9-tuple of generate_motion_profile.  About every other route that is not plain
+takes a second draw (edge_route): action points on an integer, at 0, at or behind W - 1, on or within 1e-7 of their
+predecessor, unsorted; stop and wait on the first and last node; reverse at node 0; turns of +-180, 360 and 0.5 degrees;
+waits of 0.29, 0.3, 0.07 and 0.009 s; dt of 0.02 and 1/60 s; one segment shorter than dd.
 
     python oracle/fuzz_vs_reference.py [seconds] [seed]
 
@@ -60,6 +63,66 @@ def random_route(rng, W):
     return na, aps
 
 
+EDGE_DRAWS = ("ap_integer", "ap_zero", "ap_end", "ap_repeat", "ap_unsorted", "end_nodes", "rev_node0", "turn", "wait", "dt", "short_seg")
+
+
+def edge_route(rng, W, wp, na, aps, taken):
+    """The second draw (about every other route): the positions at which the reference DECIDES (tests/golden/events/,
+    DESIGN.md section 35) mixed into a route of random_route.  Returns (waypoints, nodes, action points, dt); `taken` counts
+    the edge draws."""
+    def take(key, p):
+        if rng.random() < p:
+            taken[key] = taken.get(key, 0) + 1
+            return True
+        return False
+
+    def ap_attrs(t):
+        a = {"t": float(t)}
+        if rng.random() < 0.5:
+            a["max_velocity"] = float(rng.uniform(1.0, 4.0))
+        if rng.random() < 0.3:
+            a["max_acceleration"] = float(rng.uniform(2.0, 10.0))
+        if rng.random() < 0.4:
+            a["stop"] = True
+        if rng.random() < 0.5:
+            a["wait_time"] = float(rng.choice([0.29, 0.3, 0.07, 0.009]))
+        return a
+    aps = list(aps)
+    if W > 2 and take("ap_integer", 0.3):
+        aps.append(ap_attrs(float(rng.integers(1, W - 1))))
+        aps.sort(key=lambda a: a["t"])
+    if aps and take("ap_repeat", 0.3):
+        i = int(rng.integers(0, len(aps)))
+        aps.insert(i + 1, ap_attrs(aps[i]["t"] + float(rng.choice([0.0, 1e-7, 5e-8]))))
+    if take("ap_zero", 0.2):
+        aps.insert(0, ap_attrs(float(rng.choice([0.0, -0.5]))))
+    if take("ap_end", 0.25):
+        aps.append(ap_attrs(float(rng.choice([W - 1.0, W - 0.5, W - 1.0 - 1e-4]))))
+    if len(aps) > 1 and take("ap_unsorted", 0.2):
+        i = int(rng.integers(0, len(aps) - 1))
+        aps[i], aps[i + 1] = aps[i + 1], aps[i]
+    if take("end_nodes", 0.3):
+        for i in (0, W - 1):
+            na[i]["stop"] = True
+            na[i]["wait_time"] = float(rng.choice([0.29, 0.3, 0.07, 0.009]))
+    if take("rev_node0", 0.2):
+        na[0]["is_reverse_node"] = True
+    if W > 2 and take("turn", 0.3):
+        i = int(rng.integers(1, W - 1))
+        na[i].pop("is_reverse_node", None)
+        na[i]["turn"] = float(rng.choice([180.0, -180.0, 360.0, 0.5]))
+    if take("wait", 0.3):
+        na[int(rng.integers(0, W))]["wait_time"] = float(rng.choice([0.29, 0.3, 0.07, 0.009]))
+    dt = 0.01
+    if take("dt", 0.4):
+        dt = float(rng.choice([0.02, 1.0 / 60.0]))
+    if W > 3 and take("short_seg", 0.2):
+        i = int(rng.integers(1, W - 2))
+        wp = wp.copy()
+        wp[i + 1] = (wp[i] + (0.002, 0.001)).astype(np.float32)
+    return wp, na, aps, dt
+
+
 def main():
     if not refimport.available():
         print("reference tree absent: nothing to do")
@@ -68,7 +131,8 @@ def main():
     rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 7)
     sm_mod, _, mpg = refimport.load()
     worst_v = worst_p = 0.0
-    n = fails = 0
+    n = fails = n_edge = 0
+    taken = {}
     t0 = time.time()
     while time.time() - t0 < budget:
         W = int(rng.integers(2, 9))
@@ -82,15 +146,20 @@ def main():
             cons[2] = float(rng.uniform(2.0, 14.0))
             cons[5] = float(rng.uniform(0.6, 1.6))
         dd = float(rng.choice([0.005, 0.003, 0.011]))
-        tag = f"W={W} plain={plain} cons={[round(c, 3) for c in cons]} dd={dd} nodes={na} aps={aps}"
+        dt = 0.01
+        edge = not plain and rng.random() < 0.5
+        if edge:
+            n_edge += 1
+            wp, na, aps, dt = edge_route(rng, W, wp, na, aps, taken)
+        tag = f"W={W} plain={plain} edge={edge} cons={[round(c, 3) for c in cons]} dd={dd} dt={dt} wp={wp.tolist() if edge else '-'} nodes={na} aps={aps}"
         try:
             mgr = build_manager(sm_mod, wp, na, aps)
             mgr.rebuild_tables()
             v_ref = np.array(mpg.forward_backward_pass(mgr, mpg.Constraints(*cons), dd))
             mgr2 = build_manager(sm_mod, wp, na, aps)
-            res = mpg.generate_motion_profile(mgr2, mpg.Constraints(*cons), dd=dd)
+            res = mpg.generate_motion_profile(mgr2, mpg.Constraints(*cons), dt=dt, dd=dd)
         except Exception as e:     # the reference itself fails on some routes (quirk list): skip those
-            print("reference raised", type(e).__name__, "|", tag[:160])
+            print("reference raised", type(e).__name__, "|", tag[:160].replace("\n", " "))
             continue
         arrs = node_arrays(W, na)
         nodes = dict(is_reverse=arrs["node_is_reverse_node"], turn=arrs["node_turn"], stop=arrs["node_stop"],
@@ -104,7 +173,7 @@ def main():
         op = oracle.OraclePath(wp, nodes=nodes, actions=actions)
         op.rebuild_tables()
         v_or = op.forward_backward(cons, dd=dd)["velocity"]
-        rows, nmap, amap = op.generate_motion_profile(cons, dd=dd)
+        rows, nmap, amap = op.generate_motion_profile(cons, dt=dt, dd=dd)
         n += 1
         ok = len(v_or) == len(v_ref)
         ev = np.max(np.abs(v_or - v_ref) / np.abs(v_ref)) if ok else np.inf
@@ -118,6 +187,7 @@ def main():
         if not (ok and ev <= 1e-10 and ep <= 1e-8):
             fails += 1
             print(f"MISMATCH velocity {ev:.2e} profile {ep:.2e} rows {rows.shape[0]} vs {T} | {tag}", flush=True)
+    print(f"edge routes {n_edge}; edge draws taken: " + ", ".join(f"{k} {taken.get(k, 0)}" for k in EDGE_DRAWS))
     print(f"{n} routes in {time.time() - t0:.0f} s, {fails} mismatches; worst velocity {worst_v:.2e}, worst profile {worst_p:.2e}")
     return 1 if fails else 0
 

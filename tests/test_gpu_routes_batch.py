@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import golden_util as gu
+from events_util import full_profile
 
 pytestmark = pytest.mark.gpu
 
@@ -138,32 +139,6 @@ def test_batched_random_routes_match_oracle(torch_mod, dtype, tol):
                 assert err <= (1e-5 if dtype == "f32" else (tol if k == "velocity" else 1e-9)), (W, b, k, err)
             eh = np.max(np.abs(r["heading"][b, :N].cpu().numpy().astype(np.float64) - refs[b]["heading"])) / np.pi
             assert eh <= (1e-5 if dtype == "f32" else 1e-9), (W, b, eh)
-
-
-def full_profile(torch, gen, route, cons, copies=2):
-    """profile_routes -> apply_node_limits -> time_profile(node_reverse) -> insert_waits(node_turn, waits, action
-    points): the whole generate_motion_profile tuple of a route given as a dict of arrays, `copies` times in a batch."""
-    rep = lambda a: np.repeat(np.asarray(a)[None], copies, axis=0)
-    wp = torch.tensor(rep(route["waypoints"]), dtype=gen.tdtype, device=gen.device)
-    aps = None
-    if "ap_t" in route and len(route["ap_t"]):
-        one = [{"t": float(t), "max_velocity": float(mv), "max_acceleration": float(ma), "stop": bool(st), "wait_time": float(w)}
-               for t, mv, ma, st, w in zip(route["ap_t"], route["ap_max_velocity"], route["ap_max_acceleration"], route["ap_stop"],
-                                           route["ap_wait_time"])]
-        aps = [one for _ in range(copies)]
-    res = gen.profile_routes(wp, node_reverse=rep(route["node_is_reverse_node"]), node_turn=rep(route["node_turn"]),
-                             node_tangent=rep(route["node_tangent"]), node_magnitudes=rep(route["node_magnitudes"]),
-                             constraints=cons, dd=0.005, capacity=16384)
-    gen.apply_node_limits(res, cons, node_max_velocity=rep(route["node_max_velocity"]), node_stop=rep(route["node_stop"]),
-                          node_max_acceleration=rep(route["node_max_acceleration"]), action_points=aps)
-    tp = gen.time_profile(res, cons, dt=0.01, capacity_rows=4096, node_reverse=rep(route["node_is_reverse_node"]))
-    out = gen.insert_waits(res, tp, node_wait_time=rep(route["node_wait_time"]), action_points=aps, dt=0.01,
-                           node_turn=rep(route["node_turn"]), node_reverse=rep(route["node_is_reverse_node"]), constraints=cons)
-    torch.cuda.synchronize()
-    assert not res["flags"].any().item()
-    assert torch.equal(out["rows"][0, :int(out["counts"][0, 0])], out["rows"][copies - 1, :int(out["counts"][copies - 1, 0])])
-    T, nn, na = (int(v) for v in out["counts"][0])
-    return (out["rows"][0, :T].cpu().numpy(), [int(v) for v in out["nodes_map"][0, :nn]], [int(v) for v in out["actions_map"][0, :na]])
 
 
 @pytest.mark.parametrize("dtype,tol", [("f64", 1e-8), ("f32", 1e-5)])

@@ -10,8 +10,9 @@
 //   k_event_samples   one thread per (path, node / action point): the sample it would take effect on — a guess
 //                     from the inverse of the arc-length table, then settled with the reference's own numbers
 //                     (the path's running-sum grid and SM:291-318 distance_to_time) on the neighbouring samples;
-//   k_event_merge     one thread per path: the action points the reference never reaches (one pending action
-//                     point per sample), and one event list ordered by sample, nodes first;
+//   k_event_merge     one thread per path: the nodes numbered as the reference numbers them (it counts wrapping steps,
+//                     so a step that passes two nodes is one node), the action points the reference never reaches
+//                     (one pending action point per sample), and one event list ordered by sample, nodes first;
 //   k_limit_fill      one thread per sample: the limit in force (events at earlier samples), 0.01 where
 //                     an event with stop falls on the sample, end_vel at the end sample;
 //   k_limit_fill      also the per-sample max_acceleration rows the two sweeps see (boundary_map / max_accels,
@@ -26,9 +27,12 @@ namespace vap {
 
 constexpr int kNever = 0x7fffffff;
 
-// first loop sample k (1 <= k <= N-2) whose parameter has reached T, or kNever
+// first loop sample k (1 <= k <= N-2) whose parameter has reached T, or kNever.  T <= 0 is never reached (prev_t starts at
+// 0 and prev_t < T never holds, MPG:144), nor is T >= W - 1 (every loop parameter lies below it).
+// wraps (optional): does the reference's node test see that step — (prev_t % 1) > (t % 1), MPG:124?  A step that passes
+// two nodes (a segment shorter than dd) wraps once, or not at all.
 __device__ int first_sample_reaching(double T, int W, const LutView &v, const double *__restrict__ m,
-                                     const double *__restrict__ tab, int n_runs)
+                                     const double *__restrict__ tab, int n_runs, bool *wraps = nullptr)
 {
     const double total = m[1], dd = m[2];
     const int N = (int)m[3];
@@ -55,6 +59,7 @@ __device__ int first_sample_reaching(double T, int W, const LutView &v, const do
     };
     while (k > 1 && t_of(k - 1) >= T) k--;
     while (k <= N - 2 && t_of(k) < T) k++;
+    if (wraps && k <= N - 2) *wraps = fmod(t_of(k - 1), 1.0) > fmod(t_of(k), 1.0);
     return k <= N - 2 ? (int)k : kNever;
 }
 
@@ -79,8 +84,11 @@ __global__ void k_event_samples(int B, int W, int M, const double *__restrict__ 
     v.total = m[1];
     v.end_param = (double)(W - 1);
     if (e < W) {
-        // node e: index 0 is the start (sample 0), the last node is never passed inside the loop (MPG:125)
-        node_k[(size_t)b * W + e] = e == 0 ? 0 : (e == W - 1 ? kNever : first_sample_reaching((double)e, W, v, m, tab, n_runs));
+        // node e: index 0 is the start (sample 0), the last node is never passed inside the loop (MPG:125); the sample at
+        // which the grid passes it, as ~k where the reference's wrap test does not see that step (k_event_merge)
+        bool wraps = true;
+        const int k = e == 0 ? 0 : (e == W - 1 ? kNever : first_sample_reaching((double)e, W, v, m, tab, n_runs, &wraps));
+        node_k[(size_t)b * W + e] = wraps ? k : ~k;
     } else {
         const double T = ap_t[(size_t)b * M + (e - W)];
         ap_k[(size_t)b * M + (e - W)] = (T == T && T != INFINITY) ? first_sample_reaching(T, W, v, m, tab, n_runs) : kNever;
@@ -91,15 +99,28 @@ __global__ void k_event_samples(int B, int W, int M, const double *__restrict__ 
 // point that would take effect on the sample of its predecessor (or earlier) never does, and neither do those after
 // it; then nodes and action points merge into one list by sample, a node before an action point on the same sample
 // (the order the reference handles them in, MPG:125 then 141 — whatever their parameters).
-__global__ void k_event_merge(int B, int W, int M, const LimitInputs in, const int *__restrict__ node_k, int *__restrict__ ap_k,
+// Nodes first: the reference counts the steps that wrap (node_num += 1, MPG:124-125), not the nodes passed, so the j-th
+// wrapping step carries node j's attributes — a step that passes two nodes counts once (or not at all), every later node
+// takes effect where its successor is passed and the last ones never do.  node_k leaves with that numbering.
+__global__ void k_event_merge(int B, int W, int M, const LimitInputs in, int *__restrict__ node_k, int *__restrict__ ap_k,
                               int *__restrict__ ev_k, double *__restrict__ ev_mv, double *__restrict__ ev_ma,
                               int *__restrict__ ev_stop)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const int E = (W > 2 ? W - 2 : 0) + M;
-    const int *NK = node_k + (size_t)b * W;
+    int *NK = node_k + (size_t)b * W;
     int *AK = ap_k + (size_t)b * M;
+    int slot = 1, last_step = -1;
+    for (int e = 1; e <= W - 2; e++) {
+        const int raw = NK[e];
+        NK[e] = kNever;
+        if (raw == kNever) continue;
+        const int k = raw < 0 ? ~raw : raw;
+        if (k == last_step) continue;          // the step that passed the node before it
+        last_step = k;
+        if (raw >= 0) NK[slot++] = k;
+    }
     int last = -1;
     bool blocked = false;
     for (int a = 0; a < M; a++) {
